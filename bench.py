@@ -11,9 +11,14 @@ synthetic int8 I/Q IF at 18 Msps (2.16 GB resident in HBM), C/N0 45 dB-Hz, Doppl
      launch, descriptors and IF resident in HBM.  `value` = IF samples through the correlators per second with every channel
      active (channel-samples / channels), whole job, all ranks.
 
-With --config all (default at N = 1) the same line carries BASELINE.json's other configs under "configs": Galileo E1-C
-CBOC(6,1,1/11) x 8, GPS L5 + BDS B2a x 16 at 50 Msps (int8 and int16 records), and one GPU's 8-channel share of the
-all-constellation mix.  --config mix runs the whole 64-channel mix (configs[4]) sharded over the ranks by IF record (band).
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: the record, ONE closed loop (its
+per-epoch state is what the replay descriptors are cut from), the warm-up and the K timed steps, the line.  --full adds every
+other leg: the closed loops timed (host- and device-closed, after a first untimed call), the replay checked against the loop's own
+records, acquisition, and - with --config all, its default at N = 1 under --full - BASELINE.json's other configs under "configs":
+Galileo E1-C CBOC(6,1,1/11) x 8, GPS L5 + BDS B2a x 16 at 50 Msps (int8 and int16 records), one GPU's 8-channel share of the
+all-constellation mix, the closed-loop channel sweep and the CPU baselines.  --config mix runs the whole 64-channel mix
+(configs[4]) sharded over the ranks by IF record (band).  --dump-outputs DIR writes what the last timed step computed
+(replay_epl.npy: the six correlator sums of every block, float64) for output-for-output comparisons of two builds.
 
 N > 1: one rank per GPU.  `python bench.py --gpus N` starts the N ranks itself; under torch.distributed.run it joins the
 launcher's ranks.  Channels shard across GPUs (tracking.m:133: channels share nothing but the read-only record), every rank
@@ -411,6 +416,24 @@ def _cpu_model():
     return {"model": model, "logical_cpus": cores or os.cpu_count(), "sockets": len(sockets) or None}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as <path>/<name>.npy in float64.  The arrays share DUMP_LIMIT_BYTES; one larger than its share is
+    written as a fixed, seeded sample of its rows (in row order) next to <name>_rows.npy, the row numbers sampled."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0]
+            rows = np.sort(np.random.default_rng(20241008).choice(a.shape[0], size=share // (row_bytes + 8), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # =======================================================================================================================
 # main workload: GPS L1 C/A x 12
 # =======================================================================================================================
@@ -465,7 +488,8 @@ def run_l1ca(P, W, args, R: Ranks, device: int):
                                        code_phase=int(np.ceil(s.code_phase_samples)) + 1))
     p = track_params(S)
     with R.turn():
-        eng.track(p, inits)                         # first use: code loading, pinned and device allocations (as for the other configs' loops)
+        if args.full:
+            eng.track(p, inits)                     # first use: code loading, pinned and device allocations (as for the other configs' loops)
         t0 = time.time()
         fields, done, st = eng.track(p, inits)
         t_closed = time.time() - t0
@@ -474,12 +498,13 @@ def run_l1ca(P, W, args, R: Ranks, device: int):
     locked = np.mean(np.abs(fields["I_P"][:, 1000:]), axis=1) > 3 * np.mean(np.abs(fields["Q_P"][:, 1000:]), axis=1)
     blks = np.ceil((S.codeLength - fields["remCodePhase"]) / (fields["codeFreq"] / fs)).astype(np.int64)
     chan_samples = int(blks.sum())
-    with R.turn():
-        eng.track(p, inits, device_loop=True)       # first use
-        t0 = time.time()
-        dfields, ddone, dst = eng.track(p, inits, device_loop=True)
-        t_dev = time.time() - t0
-    dev_loop = None
+    dev_loop, dst = None, None
+    if args.full:
+        with R.turn():
+            eng.track(p, inits, device_loop=True)       # first use
+            t0 = time.time()
+            dfields, ddone, dst = eng.track(p, inits, device_loop=True)
+            t_dev = time.time() - t0
     if dst == 0 and int(ddone.min()) == n_epochs:
         diff = dfields["absoluteSample"] != fields["absoluteSample"]
         dev_loop = {"corr_msps": round(chan_samples / t_dev / 1e6, 1), "x_realtime": round(chan_samples / t_dev / 1e6 / nch / (fs / 1e6), 2),
@@ -514,10 +539,14 @@ def run_l1ca(P, W, args, R: Ranks, device: int):
     elapsed, kernel_ms_total = R.reduce([elapsed, kernel_ms_total])
     (total_chan_samples,) = R.reduce([chan_samples], op="sum")
 
-    out = eng.replay_fetch()[:, 0, :]
-    rec = np.stack([fields[f].T.reshape(-1) for f in ("I_E", "Q_E", "I_P", "Q_P", "I_L", "Q_L")], axis=1)
-    scale = 2.0 * 18000 * 28.0
-    replay_dev = float(np.max(np.abs(out - rec)) / scale)
+    out = eng.replay_fetch()[:, 0, :] if args.full or args.dump_outputs else None     # what the last timed step left on the device
+    if args.dump_outputs and R.rank == 0:
+        dump_outputs(args.dump_outputs, {"replay_epl": out})
+    replay_dev = None
+    if args.full:
+        rec = np.stack([fields[f].T.reshape(-1) for f in ("I_E", "Q_E", "I_P", "Q_P", "I_L", "Q_L")], axis=1)
+        scale = 2.0 * 18000 * 28.0
+        replay_dev = float(np.max(np.abs(out - rec)) / scale)
 
     ms_per_step = elapsed * 1e3 / args.steps
     corr_msps = total_chan_samples * args.steps / elapsed / 1e6
@@ -538,16 +567,18 @@ def run_l1ca(P, W, args, R: Ranks, device: int):
                                    else f"channels sharded over {R.world} GPU(s), every rank synthesises its own copy of the record (no hand-over)")},
         "corr_msps": round(corr_msps, 1), "corr_msps_unit": "Msamples/s (channel-samples, all GPUs)",
         "if_msps_per_gpu": round(value / R.world, 1), "x_realtime_replay": round(value / R.world / (fs / 1e6), 1),
-        "closed_loop": {"corr_msps": round(chan_samples / t_closed / 1e6, 1), "x_realtime": round(chan_samples / t_closed / 1e6 / nch / (fs / 1e6), 2),
-                        "us_per_epoch": round(t_closed / n_epochs * 1e6, 2), "channels_locked": int(locked.sum())},
-        "closed_loop_device": dev_loop,
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
                      "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": "corr_epl_fast_kernel<ARMS=1, I8_IQ, SPL=16> (four waves, float tables)", "kernel_ms": round(kernel_ms, 4),
                      "algorithmic_bytes_per_launch": algo_bytes},
-        "replay_vs_closed_loop_max_dev": replay_dev, "device": dev_name, "compute_units": cus, "synth_s": round(t_synth, 2),
+        "device": dev_name, "compute_units": cus, "synth_s": round(t_synth, 2),
         "libgnsscorr_sha256": _lib_sha(),
     }
+    if args.full:
+        result["closed_loop"] = {"corr_msps": round(chan_samples / t_closed / 1e6, 1), "x_realtime": round(chan_samples / t_closed / 1e6 / nch / (fs / 1e6), 2),
+                                 "us_per_epoch": round(t_closed / n_epochs * 1e6, 2), "channels_locked": int(locked.sum())}
+        result["closed_loop_device"] = dev_loop
+        result["replay_vs_closed_loop_max_dev"] = replay_dev
     if handover:
         result["handover"] = handover
     if R.world > 1:
@@ -1147,8 +1178,13 @@ def main() -> None:
     ap.add_argument("--channels", type=int, default=12)
     ap.add_argument("--no-sweep", action="store_true", help="skip closed_loop_sweep (closed loops of 12 ... 192 GPS L1 C/A and 16 ... 64 GPS L5 channels on one GPU)")
     ap.add_argument("--sweep-seconds", type=float, default=10.0, help="record length of the closed-loop channel sweep")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline: timed closed loops, replay check, acquisition, other configs, sweep, CPU baselines (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, <= 64 MB in all; main line only)")
     ap.add_argument("--config", choices=["all", "l1ca", "mix", "sweep"], default=None,
-                    help="all (default at N = 1): main line + the other BASELINE configs; l1ca (default at N > 1): main line only; mix: configs[4] as the line")
+                    help="all (default at N = 1 with --full; needs --full): main line + the other BASELINE configs; l1ca (the default otherwise): "
+                         "main line only; mix: configs[4] as the line; sweep (needs --full)")
     ap.add_argument("--prewarm-ms", type=float, default=40.0, help="untimed replay launches before the W warm-up steps, until this many milliseconds have passed (device clocks up after the idle phases); 0 = none")
     ap.add_argument("--cfg-seconds", type=float, default=60.0, help="record length of configs 3 (8 x E1 CBOC at 18 Msps: 15 000 four-millisecond epochs per channel) and 4 (L5 + B2a at 50 Msps)")
     ap.add_argument("--mix-seconds", type=float, default=10.0, help="record length of every band of the mix")
@@ -1167,6 +1203,10 @@ def main() -> None:
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.config in ("all", "sweep") and not args.full:
+        ap.error(f"--config {args.config} runs legs besides the headline: add --full")
+    if args.config == "mix" and args.dump_outputs:
+        ap.error("--dump-outputs writes the main line's outputs; --config mix has its own line")
     # More ranks than devices (a 1-GPU box asked for --gpus 8): said at once, as the ONE JSON line, before anything is launched or
     # imported - the library's own device count needs neither torch nor a context.  GC_BENCH_DEVICE pins every rank to one device
     # on purpose (functional tests of the N > 1 path on one GPU).
@@ -1209,7 +1249,7 @@ def main() -> None:
         except OSError:
             pass
     R = Ranks(rank, world, device)
-    config = args.config or ("all" if world == 1 else "l1ca")
+    config = args.config or ("all" if world == 1 and args.full else "l1ca")
 
     import bench_workloads as W
     import cu_sdr_collection_amd as P
@@ -1220,6 +1260,9 @@ def main() -> None:
         return
 
     result, main_ctx = run_l1ca(P, W, args, R, device)
+    if not args.full:
+        _finish(result, args, rank, [main_ctx["eng"].close, R.close])
+        return
     result["acquisition"] = run_acquisition(P, main_ctx["eng"], main_ctx["scene"], R)
     if rank == 0 and config == "all" and not args.no_acq_packages:
         result["acquisition"]["packages"] = run_acquisition_packages(P, device)

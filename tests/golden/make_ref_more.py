@@ -222,6 +222,20 @@ def _plain(v):
     return str(v)
 
 
+def gen_unpack_cplx(only=None):
+    """What GPS_L5C/include/unpack_cplx.m maps every input byte to: its four 256-entry lookup tables (I and Q of the low and the
+    high nibble), stored as int8 in ref_unpack_cplx.npz for tests/test_oracle_semantics.py."""
+    import re
+    text = open(os.path.join(REF, "GPS", "GPS_L5C", "include", "unpack_cplx.m"), encoding="latin-1").read()
+    out = {}
+    for name in ("LUT_I_long1", "LUT_Q_long1", "LUT_I_long2", "LUT_Q_long2"):
+        body = re.search(name + r"\s*=\s*\[(.*?)\];", text, re.S).group(1)
+        out[name] = np.array([int(x) for x in re.findall(r"-?\d+", body)], dtype=np.int8)
+        assert out[name].shape == (256,), name
+    np.savez_compressed(os.path.join(HERE, "ref_unpack_cplx.npz"), **out)
+    print("[unpack_cplx] GPS/GPS_L5C/include/unpack_cplx.m: 4 x 256 table entries", flush=True)
+
+
 def gen_settings(only=None):
     out = {}
     for pkg in PACKAGES:

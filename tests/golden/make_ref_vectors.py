@@ -14,6 +14,7 @@ Fixtures:
     ref_settings.json       settings = initSettings() of the 12 packages (the fields the hot path reads)
     ref_prerun.npz          channel = preRun(acqResults, settings) of the package families
     ref_navsync_<scene>.npz the synchronisation block of NAVdecoding.m (pattern, xcorr, index, candidate loop) of every package
+    ref_unpack_cplx.npz     the byte -> I/Q lookup tables of GPS_L5C's unpack_cplx.m (4 x 256 values)
 """
 from __future__ import annotations
 

@@ -59,7 +59,7 @@ def test_config5_sixty_four_channels_of_twelve_signals_on_eight_ranks():
 
 
 def test_sharded_l1ca_line_hands_the_record_over_and_shards_acquisition_by_prn():
-    res = _bench("--gpus", "2", "--seconds", "4", "--steps", "2", "--warmup", "1", "--no-cpu")
+    res = _bench("--gpus", "2", "--seconds", "4", "--steps", "2", "--warmup", "1", "--no-cpu", "--full")
     assert res["n_gpus"] == 2 and res["scaling"] == "weak"
     h = res["handover"]
     assert h["bytes"] >= 2 * 4 * 18000000 and h["seconds"] > 0
@@ -70,7 +70,7 @@ def test_sharded_l1ca_line_hands_the_record_over_and_shards_acquisition_by_prn()
     a = res["acquisition"]
     assert a["prns_per_rank"] == 16 and a["all_scene_prns_found"] and a["code_phases_within_two_samples_of_the_scene"]
     # A/B: without the hand-over every rank synthesises its own copy - same scene, same results
-    res2 = _bench("--gpus", "2", "--seconds", "4", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-handover")
+    res2 = _bench("--gpus", "2", "--seconds", "4", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-handover", "--full")
     assert "handover" not in res2 and [r["channels_locked"] for r in res2["ranks"]] == [12, 12]
     assert res2["acquisition"]["acquired"] == a["acquired"]
 
@@ -82,10 +82,25 @@ def test_rccl_process_group_carries_the_hand_over_at_world_size_one():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = str(sk.getsockname()[1])
-    res = _bench("--gpus", "1", "--config", "l1ca", "--seconds", "4", "--steps", "2", "--warmup", "1", "--no-cpu", timeout=900,
+    res = _bench("--gpus", "1", "--config", "l1ca", "--seconds", "4", "--steps", "2", "--warmup", "1", "--no-cpu", "--full", timeout=900,
                  env_extra={"GC_BENCH_FORCE_DIST": "1", "MASTER_PORT": port}, drop=("GC_BENCH_DEVICE",))
     assert res["handover"]["backend"].startswith("nccl"), res["handover"]
     assert res["closed_loop"]["channels_locked"] == 12 and res["replay_vs_closed_loop_max_dev"] < 2e-5
+
+
+def test_plain_run_times_the_headline_only_and_dumps_what_the_full_run_computes(tmp_path):
+    """Without --full the run is the headline alone (no acquisition, no timed closed loops); --dump-outputs writes the last timed
+    step's correlator sums, and a --full run of the same arguments (untimed first closed loop, device loop, checks) computes the same."""
+    import numpy as np
+    common = ("--gpus", "1", "--seconds", "4", "--steps", "3", "--warmup", "1")
+    plain = _bench(*common, "--dump-outputs", str(tmp_path / "plain"))
+    full = _bench(*common, "--config", "l1ca", "--no-cpu", "--full", "--dump-outputs", str(tmp_path / "full"))
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["ms_per_step"] > 0
+    assert not {"acquisition", "closed_loop", "closed_loop_device", "configs", "cpu_baseline"} & set(plain)
+    assert "acquisition" in full and full["closed_loop"]["channels_locked"] == 12 and full["replay_vs_closed_loop_max_dev"] < 2e-5
+    a, b = np.load(tmp_path / "plain" / "replay_epl.npy"), np.load(tmp_path / "full" / "replay_epl.npy")
+    assert a.dtype == np.float64 and a.shape == (plain["config"]["blocks_per_step"], 6) and np.abs(a).max() > 0
+    assert np.array_equal(a, b)
 
 
 @pytest.mark.gpu

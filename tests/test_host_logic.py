@@ -412,6 +412,29 @@ def test_bench_prints_a_line_the_driver_can_parse():
     assert len(bench._error_line(8, 20, 5, "e" * 5000, failed_rank=3, stderr_tail=["t" * 1000] * 40)) < 4096
 
 
+def test_bench_dump_outputs_are_float64_within_the_limit_and_reproducible():
+    """--dump-outputs writes float64 .npy files of at most DUMP_LIMIT_BYTES in all: an array over its share becomes a fixed, seeded
+    sample of its rows (+ the row numbers), the same in every run; the legs besides the headline are asked for with --full."""
+    import os, subprocess, sys, tempfile
+    import bench
+    small = np.arange(12, dtype=np.float32).reshape(4, 3)
+    big = np.random.default_rng(1).standard_normal((1_500_000, 6))
+    runs = []
+    for _ in range(2):
+        with tempfile.TemporaryDirectory() as d:
+            bench.dump_outputs(d, {"big": big, "small": small})
+            assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= bench.DUMP_LIMIT_BYTES
+            runs.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    got = runs[0]
+    assert sorted(got) == ["big", "big_rows", "small"] and all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["small"], small)
+    rows = got["big_rows"].astype(np.int64)
+    assert 0 < rows.shape[0] < big.shape[0] and np.all(np.diff(rows) > 0) and np.array_equal(got["big"], big[rows])
+    assert all(np.array_equal(got[k], runs[1][k]) for k in got)
+    r = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--config", "all"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
 def test_bench_line_is_out_before_the_tear_down_and_survives_it():
     """the result line is printed BEFORE eng.close() / destroy_process_group, a closer that raises is reported on stderr
     and a closer that hangs is cut off by the watchdog - the line is still the one JSON line on stdout, the status is 0."""
