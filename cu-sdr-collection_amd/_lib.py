@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("GC_LIB_PATH") or os.path.join(HERE, "lib", "libgnssco
 GC_OK, GC_E_INVALID, GC_E_RANGE, GC_E_NOMEM, GC_E_HIP, GC_E_STATE, GC_E_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 GC_I8, GC_I16 = 0, 1
 GC_REAL, GC_IQ, GC_QI = 0, 1, 2
+GC_PREC_F32, GC_PREC_F64 = 0, 1   # gc_set_precision
 GC_MAX_ARMS = 3
 GC_SYNC_ZERO_IS_PLUS = 1   # gc_sync_xcorr flag
 GC_OUT_STRIDE = 6 * GC_MAX_ARMS
@@ -134,6 +135,8 @@ SYMBOLS = {
     "gc_set_code_window": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "gc_set_sampling_freq": (C.c_int, [_P, C.c_double]),
     "gc_force_generic_kernel": (C.c_int, [_P, C.c_int]),
+    "gc_set_precision": (C.c_int, [_P, C.c_int]),
+    "gc_get_precision": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "gc_correlate": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.POINTER(C.c_double)]),
     "gc_replay_prepare": (C.c_int, [_P, C.c_int64, C.POINTER(gc_block)]),
     "gc_replay_launch": (C.c_int, [_P]),

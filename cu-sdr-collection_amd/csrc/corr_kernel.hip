@@ -114,6 +114,17 @@ int gc_launch_correlator(gc_context* ctx, const gc_block* d_blocks, int64_t nblo
                          double* d_out, double* d_partial, int max_arms, int fast, int period, unsigned int notify_tag,
                          bool share_el) {
   if (nblocks <= 0) return GC_OK;
+  if (ctx->precision == GC_PREC_F64) {
+    // float64 per-sample kernel (corr_f64.hip): no tagged records - the caller reads d_out / d_partial after a synchronise
+    ctx->last_kernel = 6;
+    const int rc = gc_launch_correlator_f64(ctx, d_blocks, nblocks, splits, d_out, d_partial);
+    if (rc != GC_OK || splits == 1 || d_out == nullptr) return rc;
+    const long long n = nblocks * GC_OUT_STRIDE;
+    hipLaunchKernelGGL(combine_partials_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_partial, d_out,
+                       (long long)nblocks, splits);
+    GC_HIP(hipGetLastError());
+    return GC_OK;
+  }
   KArgs a;
   a.if_base = ctx->d_if;
   a.blocks = d_blocks;

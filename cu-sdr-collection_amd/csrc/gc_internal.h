@@ -170,6 +170,7 @@ struct gc_context {
   bool launch_derived = false;  // the launch being prepared runs the lane kernel's derived-arm instantiation
   int last_kernel = -2;  // gc_debug_last_kernel
   int last_track_mode = -1;  // gc_debug_last_track_mode: 0 launch per epoch, 1 persistent host-fed kernel, 2 device loop
+  int precision = GC_PREC_F32;  // gc_set_precision: GC_PREC_F64 routes gc_correlate and the tracking loops to corr_f64.hip
 
   // acquisition scratch (acq_coarse.hip: AcqScratch)
   void* acq_scratch = nullptr;
@@ -216,6 +217,15 @@ void gc_persistent_done(gc_context* ctx);
       return GC_E_HIP;                                                                                       \
     }                                                                                                        \
   } while (0)
+
+// corr_f64.hip (GC_PREC_F64): the float64 per-sample kernel - one launch for `nblocks` descriptors on the device (splits > 1:
+// [nblocks][splits] partial sums, added in split order by combine_partials_kernel or the host), and its persistent device-loop
+// instantiation, one workgroup per channel (`dl`: device copy of the gcorr::DevLoopArgs that gc_track_device prepared)
+int gc_launch_correlator_f64(gc_context* ctx, const gc_block* d_blocks, int64_t nblocks, int splits, double* d_out, double* d_partial);
+namespace gcorr {
+struct DevLoopArgs;
+}
+int gc_launch_devloop_f64(gc_context* ctx, const gcorr::DevLoopArgs* dl, int nch);
 
 // gc_track over one window of a record (gc_track_resume / gc_track_file, track.hip + stream.hip)
 struct GcTrackResume {

@@ -142,6 +142,21 @@ int gc_force_generic_kernel(gc_context* ctx, int on) {
   return GC_OK;
 }
 
+int gc_set_precision(gc_context* ctx, int precision) {
+  if (!ctx || (precision != GC_PREC_F32 && precision != GC_PREC_F64)) {
+    gc_set_error("gc_set_precision: precision must be GC_PREC_F32 (0) or GC_PREC_F64 (1)");
+    return GC_E_INVALID;
+  }
+  ctx->precision = precision;
+  return GC_OK;
+}
+
+int gc_get_precision(const gc_context* ctx, int* precision) {
+  if (!ctx || !precision) return GC_E_INVALID;
+  *precision = ctx->precision;
+  return GC_OK;
+}
+
 int gc_set_sampling_freq(gc_context* ctx, double fs) {
   if (!ctx || !(fs > 0)) {
     gc_set_error("gc_set_sampling_freq: fs must be positive");
@@ -969,6 +984,10 @@ int gc_replay_prepare(gc_context* ctx, int64_t nblocks, const gc_block* blocks) 
   if (!ctx || nblocks <= 0 || !blocks) {
     gc_set_error("gc_replay_prepare: bad arguments");
     return GC_E_INVALID;
+  }
+  if (ctx->precision != GC_PREC_F32) {  // replay is the benchmark's float32 path: no caller may believe it got float64 sums
+    gc_set_error("gc_replay_prepare: replay runs the float32 kernels only (gc_set_precision GC_PREC_F32)");
+    return GC_E_UNSUPPORTED;
   }
   GC_HIP(hipSetDevice(ctx->device));
   int lowrate;

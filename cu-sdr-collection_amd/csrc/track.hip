@@ -342,6 +342,8 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
     probe.el_spacing = p->el_spacing;
     share_lane_nominal = share_lane_nominal && gc_block_shares_el_lane(ctx, probe);
   }
+  // float64 (GC_PREC_F64): one launch of corr_f64.hip per epoch for all channels, the sums read after a stream synchronise
+  if (ctx->precision == GC_PREC_F64) persist = persist_lane = false;
   if (persist_lane) persist = true;
   gcorr::DevLoopArgs pa;
   std::memset(&pa, 0, sizeof pa);
@@ -796,6 +798,7 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
     ctx->launch_derived = derived;
     int fast = derived ? 0 : any_mixed ? -1 : (gc_fast_lds_ok(ctx) && !ctx->force_generic) ? 2 : 0;
     for (int k = 0; k < nb && fast > 0; ++k) fast = std::min(fast, gc_block_lowrate_level(ctx, blocks[k]));
+    if (ctx->precision == GC_PREC_F64) fast = -1;  // no tagged records: gc_launch_correlator takes corr_f64.hip
     bool share = true;
     for (int k = 0; k < nb && share; ++k) share = gc_block_shares_el(ctx, blocks[k]);
     ctx->scope_share_lane = true;
@@ -949,6 +952,7 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   int rc = gc_sync_channels(ctx);
   if (rc) return rc;
   gc_scope_reset(ctx);
+  const bool f64 = ctx->precision == GC_PREC_F64;  // corr_f64.hip's device loop: every configuration gc_track takes
   int max_arms = 1;
   bool single_r1 = true, all_derived = true;
   for (int c = 0; c < nch; ++c) {
@@ -961,7 +965,7 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
     const bool hder = gc_channel_is_derived(hcn);  // three arms, the third derived from the second inside the lane kernel
     all_derived = all_derived && hder;
     for (int a = 0; a < hcn.arms; ++a)
-      if (!hcn.d_tab[a] || (hcn.mult[a] != 1.0 && !(hder && a == 2))) {
+      if (!hcn.d_tab[a] || (!f64 && hcn.mult[a] != 1.0 && !(hder && a == 2))) {
         gc_set_error("gc_track_device: ramp multipliers other than a derived third arm are not covered (use gc_track)");
         return GC_E_UNSUPPORTED;
       }
@@ -973,7 +977,12 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   // three arms, the third derived from the second: Galileo E1-C CBOC (fold 5), BDS B1C wide-band (fold 4)
   const bool cboc = max_arms == 3 && all_derived && (p->pilot_combine == 5 || p->pilot_combine == 4);
   const bool i8c = ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL;  // int8 I/Q or Q/I record
-  if ((max_arms > 2 && !cboc) || (p->pilot_combine > 3 && !cboc) || (p->pilot_combine != 0 && max_arms < 2) || (cboc && !i8c)) {
+  if (f64) {
+    if (((p->pilot_combine == 4 || p->pilot_combine == 5) && max_arms < 3) || (p->pilot_combine != 0 && max_arms < 2)) {
+      gc_set_error("gc_track_device: pilot_combine %d does not match the channels' arms", p->pilot_combine);
+      return GC_E_INVALID;
+    }
+  } else if ((max_arms > 2 && !cboc) || (p->pilot_combine > 3 && !cboc) || (p->pilot_combine != 0 && max_arms < 2) || (cboc && !i8c)) {
     gc_set_error("gc_track_device: configuration not covered by the persistent kernels (use gc_track)");
     return GC_E_UNSUPPORTED;
   }
@@ -1118,8 +1127,11 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   a.xcd_swizzle = xcd_local ? 1 : 0;
   const unsigned int grid = xcd_local ? (unsigned int)(((nch + 7) / 8) * 8 * splits) : (unsigned int)(nch * splits);
   a.derived = cboc ? 1 : 0;
-  rc = use_fast ? gc_launch_devloop(ctx, a, grid, lowrate == 2, share) : gc_launch_devloop_lane(ctx, a, grid, max_arms, share_lane && !cboc, lane_waves);
-  if (rc == GC_E_NOFIT && splits > 1) {
+  if (f64)  // one 16-wave workgroup per channel: no team, nothing to halve when the grid does not fit
+    rc = gc_launch_devloop_f64(ctx, d_args, nch);
+  else
+    rc = use_fast ? gc_launch_devloop(ctx, a, grid, lowrate == 2, share) : gc_launch_devloop_lane(ctx, a, grid, max_arms, share_lane && !cboc, lane_waves);
+  if (rc == GC_E_NOFIT && splits > 1 && !f64) {
     // the grid does not fit the device whole: the same call again with teams half the size (see gc_track's persistent launch);
     // a structural refusal (no instantiation for these tables / arms) is not retried
     cleanup();

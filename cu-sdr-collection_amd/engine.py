@@ -1,6 +1,7 @@
 """Thin object wrapper over the C-ABI (one context = one GPU = one host thread)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -15,6 +16,20 @@ def device_count() -> int:
     n = C.c_int(0)
     L.check(L.load().gc_device_count(C.byref(n)))
     return int(n.value)
+
+
+# precision= keyword of the tracking calls -> gc_set_precision value
+PRECISIONS = {"single": L.GC_PREC_F32, "double": L.GC_PREC_F64}
+
+
+def precision_code(precision) -> int | None:
+    """gc_set_precision value of a precision= keyword ("single" | "double"; None: the context's setting as it is).
+    Raises ValueError for anything else, before any library call."""
+    if precision is None:
+        return None
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"precision must be 'single' or 'double', not {precision!r}")
+    return PRECISIONS[precision]
 
 
 class Engine:
@@ -146,6 +161,36 @@ class Engine:
     def force_generic_kernel(self, on: bool):
         L.check(self._lib.gc_force_generic_kernel(self._ctx, int(bool(on))))
 
+    def set_precision(self, precision: str):
+        """gc_set_precision: "single" (float32 kernels, the default) or "double" (the float64 kernel, corr_f64.hip) for
+        gc_correlate and every tracking call of this context until changed."""
+        code = precision_code(precision)
+        if code is None:
+            raise ValueError("precision must be 'single' or 'double', not None")
+        L.check(self._lib.gc_set_precision(self._ctx, code))
+
+    @property
+    def precision(self) -> str:
+        """The context's setting (gc_get_precision): "single" or "double"."""
+        v = C.c_int(-1)
+        L.check(self._lib.gc_get_precision(self._ctx, C.byref(v)))
+        return "double" if v.value == L.GC_PREC_F64 else "single"
+
+    @contextlib.contextmanager
+    def _precision_for_call(self, code):
+        """The precision= keyword of one call: set, and the previous setting restored whatever happens (a session-wide engine
+        must not carry one test's float64 into the next)."""
+        if code is None:
+            yield
+            return
+        prev = C.c_int(L.GC_PREC_F32)
+        L.check(self._lib.gc_get_precision(self._ctx, C.byref(prev)))
+        L.check(self._lib.gc_set_precision(self._ctx, code))
+        try:
+            yield
+        finally:
+            self._lib.gc_set_precision(self._ctx, prev.value)
+
     def set_sampling_freq(self, fs: float):
         L.check(self._lib.gc_set_sampling_freq(self._ctx, float(fs)))
 
@@ -214,9 +259,11 @@ class Engine:
         return ms.value
 
     # ---- closed-loop tracking ------------------------------------------------------------
-    def track(self, params: L.gc_track_params, inits, device_loop: bool = False):
+    def track(self, params: L.gc_track_params, inits, device_loop: bool = False, precision: str | None = None):
         """Runs gc_track (or gc_track_device: loop closed on the GPU, one persistent launch).
+        precision: "single" | "double" for this call only (gc_set_precision, restored afterwards); None: the context's setting.
         Returns (fields dict name -> [nch, n_epochs], epochs_done, status)."""
+        code = precision_code(precision)
         nch = len(inits)
         arr = (L.gc_channel_init * nch)(*inits)
         n_ep = params.n_epochs
@@ -225,8 +272,9 @@ class Engine:
         fn = self._lib.gc_track_device if device_loop else self._lib.gc_track
         cno = self._cno_buffer(params, nch)
         try:
-            st = fn(self._ctx, C.byref(params), nch, arr,
-                                    out.ctypes.data_as(C.POINTER(C.c_double)), done)
+            with self._precision_for_call(code):
+                st = fn(self._ctx, C.byref(params), nch, arr,
+                                        out.ctypes.data_as(C.POINTER(C.c_double)), done)
         finally:
             if cno is not None:
                 self._lib.gc_set_cno_output(self._ctx, None, 0)
@@ -266,17 +314,19 @@ class Engine:
         return {name: out[:, i, :] for i, name in enumerate(L.TRK_FIELDS)}, np.array(list(done)), st, state, bool(paused.value)
 
     def track_file(self, path: str, params: L.gc_track_params, inits, window_samples: int, dtype: int = L.GC_I8,
-                   layout: int = L.GC_IQ, skip_bytes: int = 0):
+                   layout: int = L.GC_IQ, skip_bytes: int = 0, precision: str | None = None):
         """gc_track_file: tracking(fid, channel, settings) on a file of any size, at most 2 * window_samples samples resident
-        (the next window is read and uploaded while the current one is tracked).  Returns as track()."""
+        (the next window is read and uploaded while the current one is tracked).  precision as track().  Returns as track()."""
+        code = precision_code(precision)
         nch = len(inits)
         arr = (L.gc_channel_init * nch)(*inits)
         out = np.zeros((nch, L.GC_TRK_NFIELDS, params.n_epochs))
         done = (C.c_int32 * nch)()
         cno = self._cno_buffer(params, nch)
         try:
-            st = self._lib.gc_track_file(self._ctx, os.fsencode(path), int(skip_bytes), int(dtype), int(layout), int(window_samples),
-                                         C.byref(params), nch, arr, out.ctypes.data_as(C.POINTER(C.c_double)), done)
+            with self._precision_for_call(code):
+                st = self._lib.gc_track_file(self._ctx, os.fsencode(path), int(skip_bytes), int(dtype), int(layout), int(window_samples),
+                                             C.byref(params), nch, arr, out.ctypes.data_as(C.POINTER(C.c_double)), done)
         finally:
             if cno is not None:
                 self._lib.gc_set_cno_output(self._ctx, None, 0)
@@ -288,9 +338,11 @@ class Engine:
         return fields, np.array(list(done)), st
 
     @staticmethod
-    def track_multi(jobs, device_loop: bool = False):
+    def track_multi(jobs, device_loop: bool = False, precision: str | None = None):
         """gc_track_multi: jobs = [(engine, gc_track_params, [gc_channel_init, ...]), ...], one engine (context) per job,
-        all tracking loops run concurrently.  Returns [(fields, epochs_done, status), ...] in job order."""
+        all tracking loops run concurrently.  precision as track(), for every job's context.
+        Returns [(fields, epochs_done, status), ...] in job order."""
+        code = precision_code(precision)
         lib = L.load()
         n = len(jobs)
         arr = (L.gc_track_job * n)()
@@ -309,7 +361,10 @@ class Engine:
             arr[k].nch = nch
             arr[k].device_loop = int(bool(device_loop))
         try:
-            st = lib.gc_track_multi(n, arr)
+            with contextlib.ExitStack() as stack:
+                for eng in dict.fromkeys(j[0] for j in jobs):  # each context once, in job order
+                    stack.enter_context(eng._precision_for_call(code))
+                st = lib.gc_track_multi(n, arr)
         finally:
             for item in keep:
                 if item[4] is not None:

@@ -18,7 +18,7 @@ import numpy as np
 from . import _lib as L
 from .settings import skip_samples
 from . import codes
-from .engine import Engine
+from .engine import Engine, precision_code
 
 
 def _round(x: float) -> int:
@@ -357,7 +357,8 @@ def _tracking_finish(job, fields, done, status):
     return results, channel
 
 
-def tracking(fid: Engine, channel, settings, signal: str = "GPS_L1CA", device_loop: bool = False, pilot_fields: str | None = None):
+def tracking(fid: Engine, channel, settings, signal: str = "GPS_L1CA", device_loop: bool = False, pilot_fields: str | None = None,
+             precision: str | None = None):
     """[trackResults, channel] = tracking(fid, channel, settings) — `signal` selects the reference
     package whose tracking.m is mirrored ("GPS_L1CA": GPS/GPS_L1CA/include/tracking.m;
     "GAL_E1C": GAL/GAL_E1C/include/tracking.m, data + pilot arms, BOC(1,1) half-chip tables; ... signals.SIGNALS).
@@ -365,20 +366,28 @@ def tracking(fid: Engine, channel, settings, signal: str = "GPS_L1CA", device_lo
     Returns (trackResults, channel).  On a short read the reference prints a message and
     returns what it has (tracking.m:241-245); here the partially filled results are returned
     the same way and `trackResults[i].status` stays '-' for channels that did not finish.
+
+    precision: "double" runs the correlations in float64 (include/gnsscorr.h gc_set_precision) - trackResults then follow a
+    MATLAB run of tracking.m epoch for epoch; "single" the float32 kernels; None (default) the engine's setting.  Set for this
+    call only.
     """
+    precision_code(precision)  # ValueError before anything runs
     job = _tracking_prepare(fid, channel, settings, signal, pilot_fields)
     if not job.active:
         return job.results, channel
-    fields, done, status = fid.track(job.p, job.inits, device_loop=device_loop)   # device_loop: gc_track_device (include/gnsscorr.h)
+    fields, done, status = fid.track(job.p, job.inits, device_loop=device_loop,   # device_loop: gc_track_device (include/gnsscorr.h)
+                                     precision=precision)
     return _tracking_finish(job, fields, done, status)
 
 
-def tracking_file(fid: Engine, path: str, channel, settings, window_samples: int, signal: str = "GPS_L1CA", pilot_fields: str | None = None):
+def tracking_file(fid: Engine, path: str, channel, settings, window_samples: int, signal: str = "GPS_L1CA", pilot_fields: str | None = None,
+                  precision: str | None = None):
     """tracking(fid, channel, settings) on a record FILE that need not fit the device: at most 2 * window_samples samples are
     resident at any time (include/gnsscorr.h gc_track_file: two alternating device windows, the next one read and uploaded
     while the current one is tracked).  The reference freads block by block (tracking.m:226-245) and so handles any file
     length; results are identical to tracking() on the fully loaded record.  settings.fileType / dataType / the package's
-    sample order say how the file is laid out, as in postProcessing.m:59-96."""
+    sample order say how the file is laid out, as in postProcessing.m:59-96.  precision as tracking()."""
+    precision_code(precision)
     job = _tracking_prepare(fid, channel, settings, signal, pilot_fields)
     if not job.active:
         return job.results, channel
@@ -386,17 +395,19 @@ def tracking_file(fid: Engine, path: str, channel, settings, window_samples: int
     # GLONASS front ends deliver Q first (GLO_GL1/include/tracking.m:227)
     layout = L.GC_REAL if settings.fileType == 1 else (L.GC_QI if signal.startswith("GLO_") else L.GC_IQ)
     fid.set_sampling_freq(settings.samplingFreq)
-    fields, done, status = fid.track_file(path, job.p, job.inits, int(window_samples), dtype=dtype, layout=layout)
+    fields, done, status = fid.track_file(path, job.p, job.inits, int(window_samples), dtype=dtype, layout=layout, precision=precision)
     return _tracking_finish(job, fields, done, status)
 
 
-def tracking_multi(calls, device_loop: bool = False, pilot_fields: str | None = None):
+def tracking_multi(calls, device_loop: bool = False, pilot_fields: str | None = None, precision: str | None = None):
     """Several packages' tracking() at once (BASELINE config 5, include/gnsscorr.h gc_track_multi):
     calls = [(fid, channel, settings, signal), ...] with one Engine per call - engines that read the same record share it
-    with Engine.share_if.  Returns [(trackResults, channel), ...] in call order, each exactly what tracking() returns."""
+    with Engine.share_if.  precision as tracking(), for every call.  Returns [(trackResults, channel), ...] in call order,
+    each exactly what tracking() returns."""
+    precision_code(precision)
     jobs = [_tracking_prepare(*c, pilot_fields=pilot_fields) for c in calls]
     live = [j for j in jobs if j.active]
-    got = Engine.track_multi([(j.fid, j.p, j.inits) for j in live], device_loop=device_loop) if live else []
+    got = Engine.track_multi([(j.fid, j.p, j.inits) for j in live], device_loop=device_loop, precision=precision) if live else []
     out = []
     it = iter(got)
     for j in jobs:

@@ -131,6 +131,17 @@ typedef struct gc_block {
  * fast single-transition kernel applies, so both can be checked against the oracle. */
 int gc_force_generic_kernel(gc_context* ctx, int on);
 
+/* Arithmetic of the correlations behind gc_correlate and every tracking entry point (gc_track, gc_track_resume,
+ * gc_track_file, gc_track_device, gc_track_multi through each job's context).  GC_PREC_F32 (the default): the float32
+ * kernels.  GC_PREC_F64: one float64 per-sample kernel (csrc/corr_f64.hip) restating tracking.m:247-300 operation by
+ * operation - float64 carrier argument, cos / sin, baseband mix and sums, in a fixed order of additions (bitwise
+ * reproducible) - so a closed loop follows the reference's trajectory epoch for epoch instead of statistically.
+ * Replay (gc_replay_prepare: GC_E_UNSUPPORTED under GC_PREC_F64) and acquisition are not affected.  A setting of the
+ * context; any other value returns GC_E_INVALID. */
+enum gc_precision { GC_PREC_F32 = 0, GC_PREC_F64 = 1 };
+int gc_set_precision(gc_context* ctx, int precision);
+int gc_get_precision(const gc_context* ctx, int* precision);
+
 /* Sampling frequency used for the carrier replica (settings.samplingFreq, tracking.m:280). */
 int gc_set_sampling_freq(gc_context* ctx, double fs);
 
@@ -234,7 +245,10 @@ enum gc_track_field {
  * per epoch for all channels, discriminators + loop filters on the host between launches.
  * `epochs_done[ch]` receives the number of completed epochs (== n_epochs unless the IF
  * buffer ran out, in which case the call returns GC_E_RANGE after filling what it could —
- * the reference's early return, tracking.m:241-245). */
+ * the reference's early return, tracking.m:241-245).  Under GC_PREC_F64 (gc_set_precision) every epoch is one launch of the
+ * float64 kernel for all channels and the host loop reads the sums after a stream synchronise; with gc_track_device the same
+ * kernel runs persistently, one workgroup per channel, closing each channel's loop itself (devloop.h): both follow tracking.m
+ * epoch for epoch (absoluteSample identical, every other field to ~1e-10 relative on the reference's scenes). */
 int gc_track(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init,
              double* out, int32_t* epochs_done);
 /* Where the next tracking calls of this context put trackResults.CNo.VSMValue: cno[ch * (n_epochs / cno_interval) + k] for
@@ -280,7 +294,8 @@ int gc_track_file(gc_context* ctx, const char* path, uint64_t skip_bytes, int dt
  * channels of any rate and index scale with pilot_combine 0-3 on the lane kernel (GPS L5, BDS B2a / B3I, Galileo E5a /
  * E5b / E1 B+C, BDS B1C narrow-band), and the three-arm Galileo E1-C CBOC fold (pilot_combine 5, third arm derived).
  * Other three-arm or mixed-multiplier channels (pilot_combine 4), windowed tables (GPS L2C CL), int16 and real records
- * return GC_E_UNSUPPORTED: use gc_track. */
+ * return GC_E_UNSUPPORTED: use gc_track.  Under GC_PREC_F64 every configuration gc_track takes is covered (one float64
+ * workgroup per channel; only a grid that does not fit the device next to other persistent kernels returns GC_E_UNSUPPORTED). */
 int gc_track_device(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init,
                     double* out, int32_t* epochs_done);
 
@@ -528,7 +543,8 @@ int gc_debug_tables_derivable(const int8_t* t1, int n1, const int8_t* t6, int n6
 /* Test hook: which correlator kernel the last gc_correlate / gc_replay_launch / gc_track launch used:
  * 0 lane kernel (any chipping rate), 1 fast kernel with one-wave workgroups (float2 tables), 2 fast kernel with
  * four-wave workgroups and int8-pair tables, 3 the same with plain float tables, -1 exact per-sample kernel
- * (mixed ramp multipliers); -2 before the first launch.  Lets the parity tests prove which path they covered. */
+ * (mixed ramp multipliers), 6 the float64 per-sample kernel (GC_PREC_F64, gc_correlate and the host-closed loop);
+ * -2 before the first launch.  Lets the parity tests prove which path they covered. */
 int gc_debug_last_kernel(const gc_context* ctx);
 
 /* Test hook: how the last gc_track / gc_track_device call on this context ran its loop: 0 a correlator launch per epoch,

@@ -36,6 +36,8 @@
  *   [name, cus] = gnsscorr_mex('device_info', h)
  *   [ties, maxDev, eps] = gnsscorr_mex('acq_guard_stats', h)                         % float64 guard of the last search (gc_acq_guard_stats)
  *   n    = gnsscorr_mex('device_count')                                              % HIP devices visible: one context per device
+ *   prev = gnsscorr_mex('set_precision', h, 'double'|'single')                    % float64 correlations for every later correlate /
+ *          track call of this context (gc_set_precision), 'single' = the float32 kernels (default); returns the previous setting
  */
 #include <string.h>
 
@@ -171,6 +173,15 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                         !strcmp(dtype, "int16") ? GC_I16 : GC_I8, layout))
       fail("gc_open_if_file");
     if (gc_set_sampling_freq(handle(prhs[1]), mxGetScalar(prhs[7]))) fail("gc_set_sampling_freq");
+  } else if (!strcmp(cmd, "set_precision")) {
+    char prec[16];
+    if (nrhs < 3 || mxGetString(prhs[2], prec, sizeof prec)) mexErrMsgIdAndTxt("gnsscorr:usage", "set_precision: h, 'single' or 'double'");
+    const int want = !strcmp(prec, "double") ? GC_PREC_F64 : !strcmp(prec, "single") ? GC_PREC_F32 : -1;
+    if (want < 0) mexErrMsgIdAndTxt("gnsscorr:usage", "set_precision: 'single' or 'double', not '%s'", prec);
+    gc_context* c = handle(prhs[1]);
+    int prev = GC_PREC_F32;
+    if (gc_get_precision(c, &prev) || gc_set_precision(c, want)) fail("gc_set_precision");
+    plhs[0] = mxCreateString(prev == GC_PREC_F64 ? "double" : "single");
   } else if (!strcmp(cmd, "share_if")) {
     if (gc_share_if(handle(prhs[1]), handle(prhs[2]))) fail("gc_share_if");
   } else if (!strcmp(cmd, "load_if")) {

@@ -143,6 +143,12 @@ for k = 1:numel(active)
 end
 
 %--- the loops -----------------------------------------------------------------------------------------------------------------------
+% settings.gnsscorrPrecision: 'single' (default) runs the float32 kernels; 'double' the float64 correlator (gc_set_precision), whose
+% loops follow tracking.m epoch for epoch - for every branch below, the context's previous setting restored afterwards (every call
+% sets it from settings, so a call that errors out leaves nothing behind for the next one either)
+precision = 'single';
+if isfield(settings, 'gnsscorrPrecision'), precision = settings.gnsscorrPrecision; end
+prevPrecision = gnsscorr_mex('set_precision', h, precision);
 if windowed
     [trk, epochs, status, cno] = gnsscorr_mex('track_file', h, p, chanTable, fileName, settings.gnsscorrWindowSamples, settings.dataType, ...
                                               settings.fileType, order);
@@ -157,6 +163,7 @@ else
         [trk, epochs, status, cno] = gnsscorr_mex('track', h, p, chanTable);  % trk(epoch, (k-1)*21 + field), fields as gc_track_field
     end
 end
+gnsscorr_mex('set_precision', h, prevPrecision);
 
 %--- records (tracking.m:212-216,249,277,314,332,338-348) ------------------------------------------------------------------------
 names = {'absoluteSample','codeFreq','carrFreq','I_E','Q_E','I_P','Q_P','I_L','Q_L','dllDiscr','dllDiscrFilt','pllDiscr','pllDiscrFilt', ...
