@@ -469,6 +469,34 @@ int ensure_scratch(gc_context* ctx, int n, long long nbh, int nprn, int nbins, i
   *out = s;
   return GC_OK;
 }
+
+int guard_exact_values(gc_context* ctx, AcqScratch* s, const GcExactSetup& ex, const std::vector<GcExactCell>& cells, std::vector<double>& vals) {
+  GC_HIP(hipMemcpyAsync(s->b_cells.p, cells.data(), cells.size() * sizeof(GcExactCell), hipMemcpyHostToDevice, ctx->stream));
+  int rc = gc_exact_cells(ctx->stream, ex, (const GcExactCell*)s->b_cells.p, (int)cells.size(), (double*)s->b_exact.p);
+  if (rc) return rc;
+  vals.resize(cells.size() * (size_t)ex.nhops);
+  GC_HIP(hipMemcpyAsync(vals.data(), s->b_exact.p, vals.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  GC_HIP(hipStreamSynchronize(ctx->stream));
+  return GC_OK;
+}
+
+int guard_collect_cells(gc_context* ctx, AcqScratch* s, const float* r, int rows, long long row_stride, int valid, float thr, std::vector<int2>& list,
+                        bool* overflow) {
+  int* const d_count = (int*)s->b_list.p;
+  int2* const d_list = (int2*)((char*)s->b_list.p + 64);
+  list.clear();
+  GC_HIP(hipMemsetAsync(d_count, 0, sizeof(int), ctx->stream));
+  int rc = gc_collect_cells(ctx->stream, r, rows, row_stride, valid, thr, d_count, d_list, kGuardListCap);
+  if (rc) return rc;
+  int count = 0;
+  GC_HIP(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+  GC_HIP(hipStreamSynchronize(ctx->stream));
+  *overflow = count > kGuardListCap;
+  if (count <= 0 || *overflow) return GC_OK;
+  list.resize((size_t)count);
+  GC_HIP(hipMemcpy(list.data(), d_list, list.size() * sizeof(int2), hipMemcpyDeviceToHost));
+  return GC_OK;
+}
 }  // namespace gcacq
 
 // The guard's slow path for ONE PRN whose runner-up is within eps of its winner: `rerun(ip)` searches the PRN again with the sums of all
@@ -481,17 +509,12 @@ int guard_resolve(gc_context* ctx, AcqScratch* s, const GcExactSetup& ex, int ip
                   long long first, Rerun rerun, int* bin, int* col, double* val) {
   int rc = rerun(ip);
   if (rc) return rc;
-  int* const d_count = (int*)s->b_list.p;
-  int2* const d_list = (int2*)((char*)s->b_list.p + 64);
-  GC_HIP(hipMemsetAsync(d_count, 0, sizeof(int), ctx->stream));
-  rc = gc_collect_cells(ctx->stream, s->results, nbins, (long long)n, valid, thr, d_count, d_list, kGuardListCap);
+  std::vector<int2> list;
+  bool overflow = false;
+  rc = guard_collect_cells(ctx, s, s->results, nbins, (long long)n, valid, thr, list, &overflow);
   if (rc) return rc;
-  int count = 0;
-  GC_HIP(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
-  GC_HIP(hipStreamSynchronize(ctx->stream));
-  if (count <= 0 || count > kGuardListCap) return GC_OK;
-  std::vector<int2> list((size_t)count);
-  GC_HIP(hipMemcpy(list.data(), d_list, list.size() * sizeof(int2), hipMemcpyDeviceToHost));
+  if (list.empty()) return GC_OK;  // (also when it overflowed)
+  const int count = (int)list.size();
   std::vector<GcExactCell> cells((size_t)count);
   for (int k = 0; k < count; ++k) {
     GcExactCell& c = cells[(size_t)k];
@@ -502,12 +525,9 @@ int guard_resolve(gc_context* ctx, AcqScratch* s, const GcExactSetup& ex, int ip
     c.freq = f0_row - fstep * (double)c.bin;
     c.first = first;
   }
-  GC_HIP(hipMemcpyAsync(s->b_cells.p, cells.data(), cells.size() * sizeof(GcExactCell), hipMemcpyHostToDevice, ctx->stream));
-  rc = gc_exact_cells(ctx->stream, ex, (const GcExactCell*)s->b_cells.p, count, (double*)s->b_exact.p);
+  std::vector<double> part;
+  rc = guard_exact_values(ctx, s, ex, cells, part);
   if (rc) return rc;
-  std::vector<double> part((size_t)count * H);
-  GC_HIP(hipMemcpyAsync(part.data(), s->b_exact.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  GC_HIP(hipStreamSynchronize(ctx->stream));
   double best = -1.0;
   int bb = 0, bc = 0;
   for (int k = 0; k < count; ++k) {

@@ -350,5 +350,12 @@ struct AcqBack {
 int acq_read_back(gc_context* ctx, AcqScratch* s, const AcqBack* parts, int nparts);
 int launch_abs_pass(gc_context* ctx, AcqScratch* s, PassArgs& a, long long nbins, unsigned long long* keys = nullptr, int valid = 0,
                     int ip = 0, int nprn = 1, bool* rows_fused = nullptr, int bin0 = 0, long long nbins_total = 0);
+// The float64 guard's two round trips on the context's stream, which they synchronise (acq_guard.h; b_cells, b_exact and b_list are
+// the caller's to reserve).  Cells up, gc_exact_cells, their values back: vals[cell * ex.nhops + hop], the hops the caller's to add.
+int guard_exact_values(gc_context* ctx, AcqScratch* s, const GcExactSetup& ex, const std::vector<GcExactCell>& cells, std::vector<double>& vals);
+// gc_collect_cells on r from a zeroed counter, the list back: {row, col} of the cells at or above thr.  More than kGuardListCap of
+// them: *overflow, and the list stays empty.
+int guard_collect_cells(gc_context* ctx, AcqScratch* s, const float* r, int rows, long long row_stride, int valid, float thr, std::vector<int2>& list,
+                        bool* overflow);
 
 }  // namespace gcacq

@@ -2,6 +2,8 @@
 // shifts of it inside the inverse transform; per-PRN calls and the whole-package batch call with its float64 guard.
 // Reference: GPS/GPS_L2C/include/acquisition.m:40-118, BDS/B1I/include/acquisition.m:76-176, BDS/B1C/include/acquisition.m:137-235.
 // Split out of acq.hip in round 6 (same code, one translation unit per part of the search; shared declarations: acq_internal.h).
+#include <functional>
+
 #include "acq_internal.h"
 
 using namespace gcacq;
@@ -403,10 +405,34 @@ struct ShiftPickDev {
   int pad_;
 };
 
+// Where the second peak is looked for: the row's first `period` samples outside +-exclude samples of the first maximum `cp` - the
+// reference's three range cases (B1I :141-156, L2C :77-91; 1-based there as here: e1 = codePhase - exclude, e2 = codePhase + exclude;
+// e1 < 2: e2 .. period + e1; e2 >= period: e2 - period + 1 .. e1; else 1 .. e1 and e2 .. period).  period <= 0: nowhere.
+struct SecondWindow {
+  int lo0 = 1, hi0 = 0, lo1 = 1, hi1 = 0;  // 1-based inclusive ranges
+  __host__ __device__ bool holds(int c1) const { return (c1 >= lo0 && c1 <= hi0) || (c1 >= lo1 && c1 <= hi1); }
+};
+__host__ __device__ inline SecondWindow second_window(int cp, int exclude, int period) {
+  SecondWindow w;
+  if (period <= 0) return w;
+  const int e1 = cp - exclude, e2 = cp + exclude;
+  if (e1 < 2) {
+    w.lo0 = e2;
+    w.hi0 = period + e1;
+  } else if (e2 >= period) {
+    w.lo0 = e2 - period + 1;
+    w.hi0 = e1;
+  } else {
+    w.lo0 = 1;
+    w.hi0 = e1;
+    w.lo1 = e2;
+    w.hi1 = period;
+  }
+  return w;
+}
+
 // One workgroup per PRN: the first maximum of the winning row (BDS/B1I acquisition.m:126, GPS_L2C :72) and the largest value of the
-// row's first `period` samples outside +-exclude samples of it - the reference's three range cases (B1I :141-156, L2C :77-91;
-// 1-based there: e1 = codePhase - exclude, e2 = codePhase + exclude; e1 < 2: e2 .. period + e1; e2 >= period: e2 - period + 1 .. e1;
-// else 1 .. e1 and e2 .. period).  period <= 0: no second peak (GC_SHIFT_PICK_GLOBAL).  For the float64 guard: how many cells lie
+// row inside second_window() of it.  period <= 0: no second peak (GC_SHIFT_PICK_GLOBAL).  For the float64 guard: how many cells lie
 // within eps (relative) of either value - more than one means the float32 ordering decided something it cannot.
 __global__ __launch_bounds__(1024) void shift_pick_kernel(const float* __restrict__ rows, long long row_stride, int n, int exclude, int period, float eps,
                                                          ShiftPickDev* __restrict__ picks) {
@@ -441,22 +467,8 @@ __global__ __launch_bounds__(1024) void shift_pick_kernel(const float* __restric
   const float peak = sv[0];
   const int cp = si[0] + 1;  // 1-based, as the reference's ranges
   __syncthreads();
-  const int e1 = cp - exclude, e2 = cp + exclude;
-  int lo0 = 1, hi0 = 0, lo1 = 1, hi1 = 0;  // 1-based inclusive ranges
-  if (period > 0) {
-    if (e1 < 2) {
-      lo0 = e2;
-      hi0 = period + e1;
-    } else if (e2 >= period) {
-      lo0 = e2 - period + 1;
-      hi0 = e1;
-    } else {
-      lo0 = 1;
-      hi0 = e1;
-      lo1 = e2;
-      hi1 = period;
-    }
-  }
+  const SecondWindow w = second_window(cp, exclude, period);
+  const int lo0 = w.lo0, hi0 = w.hi0, lo1 = w.lo1, hi1 = w.hi1;
   float second = -1.0f;
   int sc = 0x7fffffff;
   auto see = [&](int i) {
@@ -559,6 +571,165 @@ int pick_sequential(const gc_acq_shift_params& p, const T* rmax, bool pairs) {
     }
   return row;
 }
+
+// ---- the float64 guard of the batch call (acq_guard.h) ---------------------------------------------------------------------------
+// Row maxima, first maxima and second peaks come out of float32 transforms; the reference's sequential `>` tests (B1I :98-119,
+// L2C :46-66), `[~, codePhase] = max(corr)` and `max_peak / second > threshold` (B1I :126-166) are float64.  Wherever two candidates
+// are closer than eps the cells that close are evaluated again as float64 correlations at one lag, and peak / second_peak of every
+// PRN always are (the two numbers the caller divides and thresholds).
+//
+// The decisions below (pick_row, resolve_peaks) are the same for both ways the batch call runs; what differs is where a row's float32
+// sums come from, so that comes in as `row_cells`.  They launch nothing themselves.
+struct ShiftGuard {
+  const gc_acq_shift_params& p;
+  int rule, exclude, period;
+  bool guard;  // false (GC_ACQ_NO_GUARD in the tuning build): the float32 decisions stand
+  double eps;  // gc_acq_tie_eps of the transform
+  GcExactSetup ex;
+  // cells {row, col} of PRN k's public row `row` at or above thr (<= kGuardListCap of them, else *overflow and none)
+  std::function<int(int k, int row, float thr, std::vector<int2>& list, bool* overflow)> row_cells;
+  // float64 values of cells {row, col} of PRN k's results
+  std::function<int(int k, const std::vector<int2>& cells, std::vector<double>& vals)> exact_values;
+  bool second() const { return rule != GC_SHIFT_PICK_GLOBAL; }
+};
+
+// the cell (public row, col) of PRN k's results
+GcExactCell shift_exact_cell(const gc_acq_shift_params& p, int k, int row, int col) {
+  GcExactCell c;
+  const int carrier = row / (p.n_signals * p.n_bins), sig = (row / p.n_bins) % p.n_signals, bin = row % p.n_bins;
+  c.code = k;
+  c.col = col;
+  c.shift = bin;  // circshift(IQfreqDom, bin): the signal times exp(+2i*pi*bin*m/n)
+  c.bin = row;
+  c.freq = p.carrier_f0 + p.carrier_step * (double)carrier;
+  c.first = p.first_sample + (long long)sig * p.n;
+  return c;
+}
+
+// The guard of the search in place: replicas in b_codes ([nprn * narms][p.n], the first code_samples entries of each are not zero
+// padding), every arm's weight (nullptr: 1).  row_cells is the caller's to set.
+ShiftGuard shift_guard(gc_context* ctx, AcqScratch* s, int narms, const double* arm_weight, int code_samples, int rule, int exclude, int period) {
+  const gc_acq_shift_params& p = s->shift;
+  ShiftGuard g{p, rule, exclude, period, GC_TUNE_ENV("GC_ACQ_NO_GUARD") == nullptr, gc_acq_tie_eps(s->plan.n)};
+  const bool cond = p.source == GC_ACQ_SOURCE_CONDITIONED;
+  g.ex.if_i8 = cond ? nullptr : (const int8_t*)ctx->d_if;
+  g.ex.if_f32 = cond ? (const float2*)ctx->acqbuf[gc_context::ACQ_COND_SIG].p : nullptr;
+  g.ex.blk = p.n;
+  g.ex.cl = code_samples;
+  g.ex.hop_stride = 0;
+  g.ex.nhops = 1;
+  g.ex.narms = narms;
+  for (int arm = 0; arm < narms; ++arm) g.ex.w[arm] = arm_weight ? arm_weight[arm] : 1.0;
+  g.ex.codes = (const int8_t*)s->b_codes.p;
+  g.ex.code_stride = p.n;
+  g.ex.fs = p.sampling_freq;
+  g.exact_values = [ctx, s, ex = g.ex](int k, const std::vector<int2>& list, std::vector<double>& vals) {
+    std::vector<GcExactCell> cells(list.size());
+    for (size_t i = 0; i < list.size(); ++i) cells[i] = shift_exact_cell(s->shift, k, list[i].x, list[i].y);
+    return guard_exact_values(ctx, s, ex, cells, vals);
+  };
+  return g;
+}
+
+// the guard's buffers for up to `cells` cells at a time
+bool shift_guard_reserve(AcqScratch* s, size_t cells) {
+  return gc_buf_reserve(s->b_cells, cells * sizeof(GcExactCell), false) == hipSuccess &&
+         gc_buf_reserve(s->b_exact, cells * sizeof(double), false) == hipSuccess &&
+         gc_buf_reserve(s->b_list, (size_t)kGuardListCap * sizeof(int2) + 64, false) == hipSuccess;
+}
+
+// cells of ONE row's sums (on the device, s->shift.n of them count) at or above thr, as {row, col} of public row `row`
+int shift_collect_row(gc_context* ctx, AcqScratch* s, const float* sums, int row, float thr, std::vector<int2>& list, bool* overflow) {
+  int rc = guard_collect_cells(ctx, s, sums, 1, (long long)s->plan.n, s->shift.n, thr, list, overflow);
+  for (int2& c : list) c.x = row;  // (the collector numbered the one row it saw 0)
+  return rc;
+}
+
+// the largest of the cells' float64 values and the smallest column that holds it (MATLAB's first occurrence)
+void first_maximum(const std::vector<int2>& cells, const std::vector<double>& vals, double* best, int* col) {
+  *best = -1.0;
+  *col = 0;
+  for (size_t i = 0; i < cells.size(); ++i)
+    if (vals[i] > *best || (vals[i] == *best && cells[i].y < *col)) {
+      *best = vals[i];
+      *col = cells[i].y;
+    }
+}
+
+// the package's selection rule on the row maxima rmd and their columns rad (public row order)
+void apply_rule(const ShiftGuard& g, const std::vector<double>& rmd, const std::vector<int>& rad, gc_acq_shift_pick& pk) {
+  if (g.rule == GC_SHIFT_PICK_GLOBAL) {
+    // BDS/B1C acquisition.m:193-197: the row of max(max(results,[],2)) (first), the first column holding the global maximum
+    const int rows = (int)rmd.size();
+    int best = 0;
+    for (int r = 1; r < rows; ++r)
+      if (rmd[(size_t)r] > rmd[(size_t)best]) best = r;
+    int col = rad[(size_t)best];
+    for (int r = 0; r < rows; ++r)
+      if (rmd[(size_t)r] == rmd[(size_t)best] && rad[(size_t)r] < col) col = rad[(size_t)r];
+    pk.row = best;
+    pk.code_phase = col;
+    pk.peak = rmd[(size_t)best];
+  } else {
+    pk.row = pick_sequential(g.p, rmd.data(), g.rule == GC_SHIFT_PICK_SEQUENTIAL_PAIRS);
+  }
+}
+
+// PRN k's row: the rule on the float32 row maxima, then rows whose maximum is within eps of the chosen one - which of them the rule
+// takes is decided on their float64 maxima (rmd / rad are overwritten with those).  More than 64 such rows: the float32 choice stands.
+int pick_row(const ShiftGuard& g, int k, std::vector<double>& rmd, std::vector<int>& rad, gc_acq_shift_pick& pk, int& ties) {
+  pk.row = -1;
+  pk.code_phase = 0;
+  pk.peak = 0.0;
+  pk.second_peak = 0.0;
+  apply_rule(g, rmd, rad, pk);
+  if (!g.guard || pk.row < 0) return GC_OK;
+  const double near = rmd[(size_t)pk.row] * (1.0 - g.eps);
+  std::vector<int> tied;
+  for (int r = 0; r < (int)rmd.size(); ++r)
+    if (rmd[(size_t)r] >= near && rmd[(size_t)r] > 0.0) tied.push_back(r);
+  if (tied.size() <= 1 || tied.size() > 64) return GC_OK;
+  ++ties;
+  for (int r : tied) {
+    std::vector<int2> list;
+    bool overflow = false;
+    int rc = g.row_cells(k, r, (float)(rmd[(size_t)r] * (1.0 - g.eps)), list, &overflow);
+    if (rc) return rc;
+    if (overflow || list.empty()) continue;  // a plateau: the float32 maximum stands for this row
+    std::vector<double> vals;
+    rc = g.exact_values(k, list, vals);
+    if (rc) return rc;
+    first_maximum(list, vals, &rmd[(size_t)r], &rad[(size_t)r]);
+  }
+  apply_rule(g, rmd, rad, pk);
+  return GC_OK;
+}
+
+// PRN k's first maximum and second peak when shift_pick_kernel (or the row's runner-up) found another cell within eps of either, `d`
+// holding the float32 values: every cell of the chosen row that could be the first maximum or the second peak - all those at or
+// above the smaller of the two float32 values less eps (the peak's lobe is among them) - then the reference's rules on the float64
+// values.  An overflowed or empty list: pk stays.  No collected cell in the window around the new first maximum: second_peak stays.
+int resolve_peaks(const ShiftGuard& g, int k, const ShiftPickDev& d, gc_acq_shift_pick& pk, int& ties) {
+  if (d.near_peak <= 1 && d.near_second <= 1) return GC_OK;
+  ++ties;
+  const float low = g.second() && d.second_col >= 0 ? std::min(d.peak, d.second) : d.peak;
+  std::vector<int2> list;
+  bool overflow = false;
+  int rc = g.row_cells(k, pk.row, (float)((double)low * (1.0 - g.eps)), list, &overflow);
+  if (rc) return rc;
+  if (overflow || list.empty()) return GC_OK;
+  std::vector<double> vals;
+  rc = g.exact_values(k, list, vals);
+  if (rc) return rc;
+  first_maximum(list, vals, &pk.peak, &pk.code_phase);
+  if (!g.second()) return GC_OK;
+  const SecondWindow w = second_window(pk.code_phase + 1, g.exclude, g.period);
+  double sec = -1.0;
+  for (size_t i = 0; i < list.size(); ++i)
+    if (w.holds(list[i].y + 1)) sec = std::max(sec, vals[i]);
+  if (sec >= 0.0) pk.second_peak = sec;
+  return GC_OK;
+}
 }  // namespace
 
 // gc_acq_shift_search_batch where the passes WRITE the rows (no per-tile candidates): PRN by PRN inside the call - rows and columns
@@ -571,27 +742,8 @@ static int shift_batch_written(gc_context* ctx, AcqScratch* s, int nprn, int nar
   const Plan& pl = s->plan;
   const int rows = p.n_carriers * p.n_signals * p.n_bins;
   const size_t N = (size_t)pl.n;
-  const bool pairs = rule == GC_SHIFT_PICK_SEQUENTIAL_PAIRS, second = rule != GC_SHIFT_PICK_GLOBAL;
-  const bool guard = GC_TUNE_ENV("GC_ACQ_NO_GUARD") == nullptr;
-  const double eps = gc_acq_tie_eps(pl.n);
-  const double ones[4] = {1.0, 1.0, 1.0, 1.0};
-  const double* const wts = arm_weight ? arm_weight : ones;
-  GcExactSetup ex;
-  ex.if_i8 = p.source == GC_ACQ_SOURCE_CONDITIONED ? nullptr : (const int8_t*)ctx->d_if;
-  ex.if_f32 = p.source == GC_ACQ_SOURCE_CONDITIONED ? (const float2*)ctx->acqbuf[gc_context::ACQ_COND_SIG].p : nullptr;
-  ex.blk = p.n;
-  ex.cl = code_samples;
-  ex.hop_stride = 0;
-  ex.nhops = 1;
-  ex.narms = narms;
-  for (int arm = 0; arm < narms; ++arm) ex.w[arm] = wts[arm];
-  ex.codes = (const int8_t*)s->b_codes.p;
-  ex.code_stride = p.n;
-  ex.fs = p.sampling_freq;
-  if (gc_buf_reserve(s->b_cells, (size_t)kGuardListCap * sizeof(GcExactCell), false) != hipSuccess ||
-      gc_buf_reserve(s->b_exact, (size_t)kGuardListCap * sizeof(double), false) != hipSuccess ||
-      gc_buf_reserve(s->b_list, (size_t)kGuardListCap * sizeof(int2) + 64, false) != hipSuccess ||
-      gc_buf_reserve(s->b_rowsec, (size_t)rows * sizeof(float), false) != hipSuccess ||
+  ShiftGuard g = shift_guard(ctx, s, narms, arm_weight, code_samples, rule, exclude, period);
+  if (!shift_guard_reserve(s, (size_t)kGuardListCap) || gc_buf_reserve(s->b_rowsec, (size_t)rows * sizeof(float), false) != hipSuccess ||
       gc_buf_reserve(s->b_pick, sizeof(ShiftPickDev), false) != hipSuccess) {
     (void)hipGetLastError();
     gc_set_error("gc_acq_shift_search_batch: device allocation failed");
@@ -601,41 +753,9 @@ static int shift_batch_written(gc_context* ctx, AcqScratch* s, int nprn, int nar
   s->guard_max_dev = 0.0;
   s->rowsecond = nullptr;
   auto irow_of = [&](int row) { return s->shift_padded ? shift_internal_row(p, row) : row; };
-  auto exact_values = [&](int k, const std::vector<int2>& rc_list, std::vector<double>& vals) -> int {
-    std::vector<GcExactCell> cells(rc_list.size());
-    for (size_t i = 0; i < rc_list.size(); ++i) {
-      GcExactCell& c = cells[i];
-      const int row = rc_list[i].x;
-      c.code = k;
-      c.col = rc_list[i].y;
-      c.shift = row % p.n_bins;
-      c.bin = row;
-      c.freq = p.carrier_f0 + p.carrier_step * (double)(row / (p.n_signals * p.n_bins));
-      c.first = p.first_sample + (long long)((row / p.n_bins) % p.n_signals) * p.n;
-    }
-    GC_HIP(hipMemcpyAsync(s->b_cells.p, cells.data(), cells.size() * sizeof(GcExactCell), hipMemcpyHostToDevice, ctx->stream));
-    int rc2 = gc_exact_cells(ctx->stream, ex, (const GcExactCell*)s->b_cells.p, (int)cells.size(), (double*)s->b_exact.p);
-    if (rc2) return rc2;
-    vals.resize(cells.size());
-    GC_HIP(hipMemcpyAsync(vals.data(), s->b_exact.p, vals.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GC_OK;
-  };
-  // cells of public row `row` (as it lies in s->results) at or above thr
-  auto row_cells = [&](int row, float thr, std::vector<int2>& list, bool* overflow) -> int {
-    int* const d_count = (int*)s->b_list.p;
-    int2* const d_list = (int2*)((char*)s->b_list.p + 64);
-    GC_HIP(hipMemsetAsync(d_count, 0, sizeof(int), ctx->stream));
-    int rc2 = gc_collect_cells(ctx->stream, s->results + (size_t)irow_of(row) * N, 1, (long long)N, p.n, thr, d_count, d_list, kGuardListCap);
-    if (rc2) return rc2;
-    int count = 0;
-    GC_HIP(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    *overflow = count > kGuardListCap;
-    list.assign((size_t)std::max(0, std::min(count, kGuardListCap)), make_int2(0, 0));
-    if (!list.empty()) GC_HIP(hipMemcpy(list.data(), d_list, list.size() * sizeof(int2), hipMemcpyDeviceToHost));
-    for (int2& c : list) c.x = row;
-    return GC_OK;
+  // (the row as it lies in s->results)
+  g.row_cells = [&](int, int row, float thr, std::vector<int2>& list, bool* overflow) {
+    return shift_collect_row(ctx, s, s->results + (size_t)irow_of(row) * N, row, thr, list, overflow);
   };
   std::vector<float> hm((size_t)rows), hs((size_t)rows);
   std::vector<int> ha((size_t)rows);
@@ -643,10 +763,6 @@ static int shift_batch_written(gc_context* ctx, AcqScratch* s, int nprn, int nar
   std::vector<int> rad((size_t)rows);
   for (int k = 0; k < nprn; ++k) {
     gc_acq_shift_pick& pk = out[k];
-    pk.row = -1;
-    pk.code_phase = 0;
-    pk.peak = 0.0;
-    pk.second_peak = 0.0;
     bool all_fused = false;
     int rc = shift_search_passes(ctx, s, narms, cspec + (size_t)k * narms * N, arm_weight, &all_fused, s->tmp);
     if (rc) return rc;
@@ -662,52 +778,9 @@ static int shift_batch_written(gc_context* ctx, AcqScratch* s, int nprn, int nar
       rmd[(size_t)r] = (double)hm[(size_t)irow_of(r)];
       rad[(size_t)r] = ha[(size_t)irow_of(r)];
     }
-    auto apply_rule = [&]() {
-      if (rule == GC_SHIFT_PICK_GLOBAL) {
-        int best = 0;
-        for (int r = 1; r < rows; ++r)
-          if (rmd[(size_t)r] > rmd[(size_t)best]) best = r;
-        int col = rad[(size_t)best];
-        for (int r = 0; r < rows; ++r)
-          if (rmd[(size_t)r] == rmd[(size_t)best] && rad[(size_t)r] < col) col = rad[(size_t)r];
-        pk.row = best;
-        pk.code_phase = col;
-        pk.peak = rmd[(size_t)best];
-      } else {
-        pk.row = pick_sequential(p, rmd.data(), pairs);
-      }
-    };
-    apply_rule();
+    rc = pick_row(g, k, rmd, rad, pk, s->guard_ties);
+    if (rc) return rc;
     if (pk.row < 0) continue;
-    if (guard) {
-      const double near = rmd[(size_t)pk.row] * (1.0 - eps);
-      std::vector<int> tied;
-      for (int r = 0; r < rows; ++r)
-        if (rmd[(size_t)r] >= near && rmd[(size_t)r] > 0.0) tied.push_back(r);
-      if (tied.size() > 1 && tied.size() <= 64) {
-        ++s->guard_ties;
-        for (int r : tied) {
-          std::vector<int2> list;
-          bool overflow = false;
-          rc = row_cells(r, (float)(rmd[(size_t)r] * (1.0 - eps)), list, &overflow);
-          if (rc) return rc;
-          if (overflow || list.empty()) continue;
-          std::vector<double> vals;
-          rc = exact_values(k, list, vals);
-          if (rc) return rc;
-          double best = -1.0;
-          int bc = 0;
-          for (size_t i = 0; i < list.size(); ++i)
-            if (vals[i] > best || (vals[i] == best && list[i].y < bc)) {
-              best = vals[i];
-              bc = list[i].y;
-            }
-          rmd[(size_t)r] = best;
-          rad[(size_t)r] = bc;
-        }
-        apply_rule();
-      }
-    }
     // first maximum and second peak of the chosen row, from the row in memory
     ShiftPickDev d;
     std::memset(&d, 0, sizeof d);
@@ -715,67 +788,27 @@ static int shift_batch_written(gc_context* ctx, AcqScratch* s, int nprn, int nar
     d.second_col = -1;
     GC_HIP(hipMemcpyAsync(s->b_pick.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(shift_pick_kernel, dim3(1), dim3(1024), 0, ctx->stream, s->results + (size_t)irow_of(pk.row) * N, (long long)N, p.n, exclude,
-                       second ? period : 0, (float)eps, (ShiftPickDev*)s->b_pick.p);
+                       g.second() ? period : 0, (float)g.eps, (ShiftPickDev*)s->b_pick.p);
     GC_HIP(hipGetLastError());
     rc = shift_read_back(ctx, s, &d, s->b_pick.p, sizeof d);
     if (rc) return rc;
-    if (second) pk.code_phase = d.code_phase;
+    if (g.second()) pk.code_phase = d.code_phase;
     pk.peak = (double)d.peak;
-    pk.second_peak = second ? (double)d.second : 0.0;
-    if (!guard) continue;
+    pk.second_peak = g.second() ? (double)d.second : 0.0;
+    if (!g.guard) continue;
     {
       std::vector<int2> two;
       two.push_back(make_int2(pk.row, pk.code_phase));
-      if (second && d.second_col >= 0) two.push_back(make_int2(pk.row, d.second_col));
+      if (g.second() && d.second_col >= 0) two.push_back(make_int2(pk.row, d.second_col));
       std::vector<double> vals;
-      rc = exact_values(k, two, vals);
+      rc = g.exact_values(k, two, vals);
       if (rc) return rc;
       if (vals[0] > 0.0) s->guard_max_dev = std::max(s->guard_max_dev, std::fabs(pk.peak - vals[0]) / vals[0]);
       pk.peak = vals[0];
       if (two.size() > 1) pk.second_peak = vals[1];
     }
-    if (d.near_peak <= 1 && d.near_second <= 1) continue;
-    ++s->guard_ties;
-    const float low = second && d.second_col >= 0 ? std::min(d.peak, d.second) : d.peak;
-    std::vector<int2> list;
-    bool overflow = false;
-    rc = row_cells(pk.row, (float)((double)low * (1.0 - eps)), list, &overflow);
+    rc = resolve_peaks(g, k, d, pk, s->guard_ties);
     if (rc) return rc;
-    if (overflow || list.empty()) continue;
-    std::vector<double> vals;
-    rc = exact_values(k, list, vals);
-    if (rc) return rc;
-    double best = -1.0;
-    int bc = 0;
-    for (size_t i = 0; i < list.size(); ++i)
-      if (vals[i] > best || (vals[i] == best && list[i].y < bc)) {
-        best = vals[i];
-        bc = list[i].y;
-      }
-    pk.code_phase = bc;
-    pk.peak = best;
-    if (second) {
-      const int cp = bc + 1, e1 = cp - exclude, e2 = cp + exclude;
-      int lo0, hi0, lo1 = 1, hi1 = 0;
-      if (e1 < 2) {
-        lo0 = e2;
-        hi0 = period + e1;
-      } else if (e2 >= period) {
-        lo0 = e2 - period + 1;
-        hi0 = e1;
-      } else {
-        lo0 = 1;
-        hi0 = e1;
-        lo1 = e2;
-        hi1 = period;
-      }
-      double sec = -1.0;
-      for (size_t i = 0; i < list.size(); ++i) {
-        const int c1 = list[i].y + 1;
-        if ((c1 >= lo0 && c1 <= hi0) || (c1 >= lo1 && c1 <= hi1)) sec = std::max(sec, vals[i]);
-      }
-      if (sec >= 0.0) pk.second_peak = sec;
-    }
   }
   // no single PRN's search is "the last one" for gc_acq_shift_row after this call
   s->shift_rows_fused = true;
@@ -814,7 +847,6 @@ extern "C" int gc_acq_shift_search_batch(gc_context* ctx, int nprn, int narms, c
   const Plan& pl = s->plan;
   const int rows = p.n_carriers * p.n_signals * p.n_bins;
   const size_t N = (size_t)pl.n;
-  const bool second = rule != GC_SHIFT_PICK_GLOBAL;
   if (gc_buf_reserve(s->b_codes, (size_t)nprn * narms * p.n, false) != hipSuccess ||
       gc_buf_reserve(s->b_codespec, (size_t)nprn * narms * N * sizeof(float2), false) != hipSuccess ||
       gc_buf_reserve(s->b_rowmax, (size_t)nprn * rows * sizeof(float), false) != hipSuccess ||
@@ -924,162 +956,54 @@ extern "C" int gc_acq_shift_search_batch(gc_context* ctx, int nprn, int narms, c
   rc = shift_read_back(ctx, s, hmax.data(), s->b_rowmax.p, sizeof(float) * hmax.size(), harg.data(), s->b_rowarg.p, sizeof(int) * harg.size(),
                        hsecond.data(), s->b_rowsec.p, sizeof(float) * hsecond.size());
   if (rc) return rc;
-  // ---- the float64 guard (acq_guard.h) --------------------------------------------------------------------------------------------
-  // Row maxima, first maxima and second peaks come out of float32 transforms; the reference's sequential `>` tests (B1I :98-119,
-  // L2C :46-66), `[~, codePhase] = max(corr)` and `max_peak / second > threshold` (B1I :126-166) are float64.  Wherever two candidates
-  // are closer than eps the cells that close are evaluated again as float64 correlations at one lag, and peak / second_peak of every
-  // PRN always are (the two numbers the caller divides and thresholds).
-  const bool guard = GC_TUNE_ENV("GC_ACQ_NO_GUARD") == nullptr;
-  const double eps = gc_acq_tie_eps(pl.n);
+  // ---- the float64 guard (ShiftGuard above) ---------------------------------------------------------------------------------------
   const double ones[4] = {1.0, 1.0, 1.0, 1.0};
   const double* const wts = arm_weight ? arm_weight : ones;
-  GcExactSetup ex;
-  ex.if_i8 = p.source == GC_ACQ_SOURCE_CONDITIONED ? nullptr : (const int8_t*)ctx->d_if;
-  ex.if_f32 = p.source == GC_ACQ_SOURCE_CONDITIONED ? (const float2*)ctx->acqbuf[gc_context::ACQ_COND_SIG].p : nullptr;
-  ex.blk = p.n;
-  ex.cl = sample_index ? n_index : p.n;  // (replica entries beyond the index vector are the zero padding)
-  ex.hop_stride = 0;
-  ex.nhops = 1;
-  ex.narms = narms;
-  for (int arm = 0; arm < narms; ++arm) ex.w[arm] = wts[arm];
-  ex.codes = (const int8_t*)s->b_codes.p;
-  ex.code_stride = p.n;
-  ex.fs = p.sampling_freq;
-  auto cell_of = [&](int k, int row, int col) {
-    GcExactCell c;
-    const int carrier = row / (p.n_signals * p.n_bins), sig = (row / p.n_bins) % p.n_signals, bin = row % p.n_bins;
-    c.code = k;
-    c.col = col;
-    c.shift = bin;                                            // circshift(IQfreqDom, bin): the signal times exp(+2i*pi*bin*m/n)
-    c.bin = row;
-    c.freq = p.carrier_f0 + p.carrier_step * (double)carrier;
-    c.first = p.first_sample + (long long)sig * p.n;
-    return c;
-  };
+  ShiftGuard g = shift_guard(ctx, s, narms, arm_weight, sample_index ? n_index : p.n, rule, exclude, period);  // (replica entries beyond the index vector are the zero padding)
   s->guard_ties = 0;
   s->guard_max_dev = 0.0;
-  const size_t cells_cap = (size_t)std::max(2 * nprn, kGuardListCap);
-  if (guard && (gc_buf_reserve(s->b_cells, cells_cap * sizeof(GcExactCell), false) != hipSuccess ||
-                gc_buf_reserve(s->b_exact, cells_cap * sizeof(double), false) != hipSuccess ||
-                gc_buf_reserve(s->b_list, (size_t)kGuardListCap * sizeof(int2) + 64, false) != hipSuccess ||
-                gc_buf_reserve(s->b_rows, (size_t)nprn * N * sizeof(float), false) != hipSuccess)) {
+  if (g.guard && (!shift_guard_reserve(s, (size_t)std::max(2 * nprn, kGuardListCap)) ||
+                  gc_buf_reserve(s->b_rows, (size_t)nprn * N * sizeof(float), false) != hipSuccess)) {
     (void)hipGetLastError();
     gc_set_error("gc_acq_shift_search_batch: device allocation failed");
     return GC_E_NOMEM;
   }
-  // float64 values of cells {row, col} of PRN k's results
-  auto exact_values = [&](int k, const std::vector<int2>& rc_list, std::vector<double>& vals) -> int {
-    std::vector<GcExactCell> cells(rc_list.size());
-    for (size_t i = 0; i < rc_list.size(); ++i) cells[i] = cell_of(k, rc_list[i].x, rc_list[i].y);
-    GC_HIP(hipMemcpyAsync(s->b_cells.p, cells.data(), cells.size() * sizeof(GcExactCell), hipMemcpyHostToDevice, ctx->stream));
-    int rc2 = gc_exact_cells(ctx->stream, ex, (const GcExactCell*)s->b_cells.p, (int)cells.size(), (double*)s->b_exact.p);
-    if (rc2) return rc2;
-    vals.resize(cells.size());
-    GC_HIP(hipMemcpyAsync(vals.data(), s->b_exact.p, vals.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GC_OK;
+  // PRN k's row `row` transformed again into the PRN's slot of b_rows (its sums were never written)
+  auto row_again = [&](int k, int row) {
+    return shift_row_passes(ctx, s, row, narms, cspec + (size_t)k * narms * N, wts, (float*)s->b_rows.p + (size_t)k * N, /*to_slot=*/true);
   };
-  // Row `row` of PRN k transformed again into the PRN's slot of b_rows; its cells at or above thr collected (<= kGuardListCap, else
-  // *overflow) as {row, col}
-  auto row_cells = [&](int k, int row, float thr, std::vector<int2>& list, bool* overflow) -> int {
-    int rc2 = shift_row_passes(ctx, s, row, narms, cspec + (size_t)k * narms * N, wts, (float*)s->b_rows.p + (size_t)k * N, /*to_slot=*/true);
-    if (rc2) return rc2;
-    int* const d_count = (int*)s->b_list.p;
-    int2* const d_list = (int2*)((char*)s->b_list.p + 64);
-    GC_HIP(hipMemsetAsync(d_count, 0, sizeof(int), ctx->stream));
-    rc2 = gc_collect_cells(ctx->stream, (const float*)s->b_rows.p + (size_t)k * N, 1, (long long)N, p.n, thr, d_count, d_list, kGuardListCap);
-    if (rc2) return rc2;
-    int count = 0;
-    GC_HIP(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    *overflow = count > kGuardListCap;
-    list.assign((size_t)std::max(0, std::min(count, kGuardListCap)), make_int2(0, 0));
-    if (!list.empty()) GC_HIP(hipMemcpy(list.data(), d_list, list.size() * sizeof(int2), hipMemcpyDeviceToHost));
-    for (int2& c : list) c.x = row;  // (the collector numbered the one row it saw 0)
-    return GC_OK;
+  g.row_cells = [&](int k, int row, float thr, std::vector<int2>& list, bool* overflow) {
+    const int rc2 = row_again(k, row);
+    return rc2 ? rc2 : shift_collect_row(ctx, s, (const float*)s->b_rows.p + (size_t)k * N, row, thr, list, overflow);
   };
-
   // the package's selection rule on the row maxima (host: nprn x rows numbers)
   std::vector<double> rmd((size_t)rows);
   std::vector<int> rad((size_t)rows);
   for (int k = 0; k < nprn; ++k) {
-    const float* rm = hmax.data() + (size_t)k * rows;
-    const int* ra = harg.data() + (size_t)k * rows;
-    gc_acq_shift_pick& pk = out[k];
-    pk.row = -1;
-    pk.code_phase = 0;
-    pk.peak = 0.0;
-    pk.second_peak = 0.0;
     for (int r = 0; r < rows; ++r) {
-      rmd[(size_t)r] = (double)rm[r];
-      rad[(size_t)r] = ra[r];
+      rmd[(size_t)r] = (double)hmax[(size_t)k * rows + r];
+      rad[(size_t)r] = harg[(size_t)k * rows + r];
     }
-    auto apply_rule = [&]() {
-      if (rule == GC_SHIFT_PICK_GLOBAL) {
-        // BDS/B1C acquisition.m:193-197: the row of max(max(results,[],2)) (first), the first column holding the global maximum
-        int best = 0;
-        for (int r = 1; r < rows; ++r)
-          if (rmd[(size_t)r] > rmd[(size_t)best]) best = r;
-        int col = rad[(size_t)best];
-        for (int r = 0; r < rows; ++r)
-          if (rmd[(size_t)r] == rmd[(size_t)best] && rad[(size_t)r] < col) col = rad[(size_t)r];
-        pk.row = best;
-        pk.code_phase = col;
-        pk.peak = rmd[(size_t)best];
-      } else {
-        pk.row = pick_sequential(p, rmd.data(), pairs);
-      }
-    };
-    apply_rule();
-    if (!guard || pk.row < 0) continue;
-    // rows whose maximum is within eps of the chosen one: which of them the rule takes is decided on their float64 maxima
-    const double near = rmd[(size_t)pk.row] * (1.0 - eps);
-    std::vector<int> tied;
-    for (int r = 0; r < rows; ++r)
-      if (rmd[(size_t)r] >= near && rmd[(size_t)r] > 0.0) tied.push_back(r);
-    if (tied.size() > 1 && tied.size() <= 64) {
-      ++s->guard_ties;
-      for (int r : tied) {
-        std::vector<int2> list;
-        bool overflow = false;
-        rc = row_cells(k, r, (float)((double)rm[r] * (1.0 - eps)), list, &overflow);
-        if (rc) return rc;
-        if (overflow || list.empty()) continue;  // a plateau: the float32 maximum stands for this row
-        std::vector<double> vals;
-        rc = exact_values(k, list, vals);
-        if (rc) return rc;
-        double best = -1.0;
-        int bc = 0;
-        for (size_t i = 0; i < list.size(); ++i)
-          if (vals[i] > best || (vals[i] == best && list[i].y < bc)) {
-            best = vals[i];
-            bc = list[i].y;
-          }
-        rmd[(size_t)r] = best;
-        rad[(size_t)r] = bc;
-      }
-      apply_rule();
-    }
+    rc = pick_row(g, k, rmd, rad, out[k], s->guard_ties);
+    if (rc) return rc;
   }
-  // phase 2: the winning rows again (their sums were never written), first maximum and second peak on the device, one read-back
+  // phase 2: the winning rows again, first maximum and second peak on the device, one read-back
   std::vector<ShiftPickDev> dev((size_t)nprn);
   for (int k = 0; k < nprn; ++k) {
     std::memset(&dev[(size_t)k], 0, sizeof(ShiftPickDev));
     dev[(size_t)k].row = out[k].row;
     dev[(size_t)k].second_col = -1;
   }
-  if (!second && !guard) return GC_OK;
-  if (second) {
+  if (!g.second() && !g.guard) return GC_OK;
+  if (g.second()) {
     GC_HIP(hipMemcpyAsync(s->b_pick.p, dev.data(), (size_t)nprn * sizeof(ShiftPickDev), hipMemcpyHostToDevice, ctx->stream));
     for (int k = 0; k < nprn; ++k) {
       if (out[k].row < 0) continue;
-      const int irow = out[k].row;
-      rc = shift_row_passes(ctx, s, irow, narms, cspec + (size_t)k * narms * N, wts, (float*)s->b_rows.p + (size_t)k * N,
-                            /*to_slot=*/true);  // row irow lands at b_rows + k * N
+      rc = row_again(k, out[k].row);
       if (rc) return rc;
     }
     hipLaunchKernelGGL(shift_pick_kernel, dim3((unsigned int)nprn), dim3(1024), 0, ctx->stream, (const float*)s->b_rows.p, (long long)N, p.n, exclude, period,
-                       (float)eps, (ShiftPickDev*)s->b_pick.p);
+                       (float)g.eps, (ShiftPickDev*)s->b_pick.p);
     GC_HIP(hipGetLastError());
     rc = shift_read_back(ctx, s, dev.data(), s->b_pick.p, (size_t)nprn * sizeof(ShiftPickDev));
     if (rc) return rc;
@@ -1100,86 +1024,38 @@ extern "C" int gc_acq_shift_search_batch(gc_context* ctx, int nprn, int narms, c
       const size_t at = (size_t)k * rows + (size_t)out[k].row;
       d.code_phase = out[k].code_phase;
       d.peak = (float)out[k].peak;
-      d.near_peak = (double)hsecond[at] >= (double)hmax[at] * (1.0 - eps) ? 2 : 1;
+      d.near_peak = (double)hsecond[at] >= (double)hmax[at] * (1.0 - g.eps) ? 2 : 1;
       d.near_second = 0;
     }
   }
-  if (!guard) return GC_OK;
+  if (!g.guard) return GC_OK;
   // every PRN's peak and second-peak cells in float64 (one launch), then the PRNs whose row holds another cell within eps of either
   {
     std::vector<GcExactCell> cells;
-    std::vector<int> owner;
+    std::vector<double*> dst;
     for (int k = 0; k < nprn; ++k) {
       if (out[k].row < 0) continue;
-      cells.push_back(cell_of(k, out[k].row, second ? dev[(size_t)k].code_phase : out[k].code_phase));
-      owner.push_back(2 * k);
-      if (second && dev[(size_t)k].second_col >= 0) {
-        cells.push_back(cell_of(k, out[k].row, dev[(size_t)k].second_col));
-        owner.push_back(2 * k + 1);
+      cells.push_back(shift_exact_cell(p, k, out[k].row, out[k].code_phase));
+      dst.push_back(&out[k].peak);
+      if (dev[(size_t)k].second_col >= 0) {
+        cells.push_back(shift_exact_cell(p, k, out[k].row, dev[(size_t)k].second_col));
+        dst.push_back(&out[k].second_peak);
       }
     }
     if (!cells.empty()) {
-      GC_HIP(hipMemcpyAsync(s->b_cells.p, cells.data(), cells.size() * sizeof(GcExactCell), hipMemcpyHostToDevice, ctx->stream));
-      rc = gc_exact_cells(ctx->stream, ex, (const GcExactCell*)s->b_cells.p, (int)cells.size(), (double*)s->b_exact.p);
+      std::vector<double> vals;
+      rc = guard_exact_values(ctx, s, g.ex, cells, vals);
       if (rc) return rc;
-      std::vector<double> vals(cells.size());
-      GC_HIP(hipMemcpyAsync(vals.data(), s->b_exact.p, vals.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-      GC_HIP(hipStreamSynchronize(ctx->stream));
       for (size_t i = 0; i < cells.size(); ++i) {
-        const int k = owner[i] / 2;
-        double& dst = (owner[i] & 1) ? out[k].second_peak : out[k].peak;
-        if (vals[i] > 0.0) s->guard_max_dev = std::max(s->guard_max_dev, std::fabs(dst - vals[i]) / vals[i]);
-        dst = vals[i];
+        if (vals[i] > 0.0) s->guard_max_dev = std::max(s->guard_max_dev, std::fabs(*dst[i] - vals[i]) / vals[i]);
+        *dst[i] = vals[i];
       }
     }
   }
   for (int k = 0; k < nprn; ++k) {
-    const ShiftPickDev& d = dev[(size_t)k];
-    if (out[k].row < 0 || (d.near_peak <= 1 && d.near_second <= 1)) continue;
-    ++s->guard_ties;
-    // every cell of the winning row that could be the first maximum or the second peak: all those at or above the smaller of the two
-    // float32 values less eps (the peak's lobe is among them).  Then the reference's rules on the float64 values.
-    const float low = second && d.second_col >= 0 ? std::min(d.peak, d.second) : d.peak;
-    std::vector<int2> list;
-    bool overflow = false;
-    rc = row_cells(k, out[k].row, (float)((double)low * (1.0 - eps)), list, &overflow);
+    if (out[k].row < 0) continue;
+    rc = resolve_peaks(g, k, dev[(size_t)k], out[k], s->guard_ties);
     if (rc) return rc;
-    if (overflow || list.empty()) continue;
-    std::vector<double> vals;
-    rc = exact_values(k, list, vals);
-    if (rc) return rc;
-    double best = -1.0;
-    int bc = 0;
-    for (size_t i = 0; i < list.size(); ++i)
-      if (vals[i] > best || (vals[i] == best && list[i].y < bc)) {
-        best = vals[i];
-        bc = list[i].y;
-      }
-    out[k].code_phase = bc;
-    out[k].peak = best;
-    if (second) {
-      // the reference's three range cases around the (float64) first maximum, 1-based (B1I :141-156, L2C :77-91)
-      const int cp = bc + 1, e1 = cp - exclude, e2 = cp + exclude;
-      int lo0, hi0, lo1 = 1, hi1 = 0;
-      if (e1 < 2) {
-        lo0 = e2;
-        hi0 = period + e1;
-      } else if (e2 >= period) {
-        lo0 = e2 - period + 1;
-        hi0 = e1;
-      } else {
-        lo0 = 1;
-        hi0 = e1;
-        lo1 = e2;
-        hi1 = period;
-      }
-      double sec = -1.0;
-      for (size_t i = 0; i < list.size(); ++i) {
-        const int c1 = list[i].y + 1;
-        if ((c1 >= lo0 && c1 <= hi0) || (c1 >= lo1 && c1 <= hi1)) sec = std::max(sec, vals[i]);
-      }
-      if (sec >= 0.0) out[k].second_peak = sec;
-    }
   }
   return GC_OK;
 }
