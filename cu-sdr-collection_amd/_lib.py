@@ -151,6 +151,10 @@ SYMBOLS = {
                                   C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gc_track_file": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.POINTER(gc_track_params), C.c_int,
                                 C.POINTER(gc_channel_init), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "gc_track_device_resume": (C.c_int, [_P, C.POINTER(gc_track_params), C.c_int, C.POINTER(gc_channel_init), C.POINTER(gc_channel_state),
+                                         C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gc_track_file_device": (C.c_int, [_P, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.POINTER(gc_track_params), C.c_int,
+                                       C.POINTER(gc_channel_init), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "gc_set_cno_output": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64]),
     "gc_share_if": (C.c_int, [_P, _P]),
     "gc_track_multi": (C.c_int, [C.c_int, C.POINTER(gc_track_job)]),

@@ -177,7 +177,7 @@ __device__ __noinline__ void f64_close(const DevLoopArgs* __restrict__ dl, DevLo
 }
 
 // Device loop: workgroup c runs channel slot c from the state gc_track_device put in dl->chan[c] until its status is not 0
-// (all epochs done, record exhausted, NCO diverged).  Records and the final state go to device memory (devloop_commit).
+// (all its epochs done, record exhausted, NCO diverged, paused at the end of a window).  Records and the final state go to device memory (devloop_commit).
 template <int MODE>
 __global__ __launch_bounds__(kF64LoopWG) void corr_f64_devloop_kernel(const DevLoopArgs* __restrict__ dl, const F64Args p) {
   __shared__ double red[kF64LoopWG / 64][GC_OUT_STRIDE];

@@ -173,12 +173,13 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
   // epoch's sample fetch (pf_w below).
   [[maybe_unused]] DevLoopArgs dl_loc;
   if constexpr (DEVLOOP) dl_loc = *p.devloop;
-  const int nloop = DEVLOOP ? dl_loc.n_epochs : p.bpw;
+  int nloop = p.bpw;
   gc_block dl_next;  // DEVLOOP: the descriptor this member computed for the next epoch
   (void)dl_next;
   DevLoopChan dl_st;  // DEVLOOP: the channel's loop state, in registers across the epochs (every member keeps its own copy)
   if constexpr (DEVLOOP) dl_st = p.devloop->chan[min(wq, (long long)p.nblocks - 1)];
   (void)dl_st;
+  if constexpr (DEVLOOP) nloop = dl_st.epoch_budget;  // the channel's own number of epochs (<= n_epochs): every member reads the same
   // DEVLOOP: the next epoch's samples, fetched while this epoch's loop is being closed.  The next block starts exactly where this one
   // ends (tracking.m:219-222, 249: absoluteSample advances by blksize) - only its LENGTH waits for the closure -, so the 16-byte
   // chunk every lane will read first is known before the discriminators are: the load goes out right after the team's partial
@@ -596,6 +597,9 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
       const int cpsn = (nchn + p.splits - 1) / p.splits;
       const int cbegn = split * cpsn, cendn = min(nchn, cbegn + cpsn);
       const int itersn = (cendn - cbegn + kFW - 1) / kFW;
+      // Never past the buffer's samples, a window of a record (DevLoopArgs::pause) included: every lane's chunk lies in chunks q0n .. q1n,
+      // which end before sample s0n + blksize + SPL, and the fetch goes out only when that many samples and SPL more are there - so
+      // the epoch after which the team pauses or ends (its next block does not fit) fetches nothing it may not read.
       if (itersn > 0 && (unsigned long long)(s0n + blk.blksize + 2 * SPL) <= dl->if_nsamples) {
         const unsigned int voffn = (unsigned int)lane * CBn;
         const unsigned int vlastn = min(voffn, (unsigned int)(cendn - 1 - cbegn - (itersn - 1) * kFW) * CBn);

@@ -183,7 +183,8 @@ __global__ __launch_bounds__(DEVLOOP ? 8 * 64 : kLW * 64)  // device loop: at mo
   gc_block* sblk = reinterpret_cast<gc_block*>(smem + p.red_off + kLW * GC_OUT_STRIDE * sizeof(double));
   int* sstatus = reinterpret_cast<int*>(sblk + 1);
   double* dred = reinterpret_cast<double*>(smem + p.red_off + kLW * GC_OUT_STRIDE * sizeof(double) + 128);
-  const int nloop = DEVLOOP ? p.devloop->n_epochs : p.bpw;
+  // DEVLOOP: the channel's own number of epochs (DevLoopChan::epoch_budget <= n_epochs), the same for every member of its team
+  const int nloop = DEVLOOP ? p.devloop->chan[min(wq, (long long)p.nblocks - 1)].epoch_budget : p.bpw;
   DevLoopChan dl_st;  // DEVLOOP closer (member 0, wave 0): the channel's loop state, in registers across the epochs
   if constexpr (DEVLOOP) {
     if (member == 0 && wave == 0) dl_st = p.devloop->chan[min(wq, (long long)p.nblocks - 1)];
@@ -809,7 +810,9 @@ __global__ __launch_bounds__(DEVLOOP ? 8 * 64 : kLW * 64)  // device loop: at mo
           unsigned long long q[sizeof(gc_block) / 8];
         } u;
         u.b = nxt;
-        unsigned long long word = (unsigned long long)((st == 2 || st == 3) ? st : 0);
+        // the status word releases the other members from their poll: record exhausted, timed out, NCO diverged (no block can be cut
+        // from its geometry), paused at the end of a window
+        unsigned long long word = (unsigned long long)(st >= 2 ? st : 0);
 #pragma unroll
         for (int i = 0; i < (int)(sizeof(gc_block) / 8); ++i) word = (lane == i) ? u.q[i] : word;
         if (lane < kDescWords && bi + 1 < nloop)

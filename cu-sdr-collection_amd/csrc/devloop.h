@@ -23,9 +23,12 @@ typedef unsigned int msg_t __attribute__((ext_vector_type(4)));  // one 16-byte 
 struct DevLoopChan {
   gc_block blk;              // initial descriptor (host) / last descriptor (closer)
   int status;                // 0 running, 1 all epochs done, 2 record exhausted (tracking.m:241-245), 3 wait timed out,
-                             // 4 code NCO diverged: codeFreq not finite / not positive (MATLAB's fread(fid, NaN) errors there)
+                             // 4 code NCO diverged: codeFreq not finite / not positive (MATLAB's fread(fid, NaN) errors there),
+                             // 5 paused: the next block does not fit this window of the record (DevLoopArgs::pause)
   int epochs_done;
-  int pad0[2];
+  int epoch_budget;          // epochs this launch runs for THIS channel (<= DevLoopArgs::n_epochs): channels pause at different epochs of
+                             // a windowed record, so the calls that follow owe them different numbers of epochs
+  int pad0;
   // loop state, touched by the closing member only
   long long pos;
   double code_freq, code_freq_basis, rem_code;
@@ -56,7 +59,10 @@ struct DevLoopArgs {
   int reserved;                 // message scope (msg_load / msg_store): 0 = system
   int timing;                   // GC_DEVLOOP_TIMING: the closer accumulates its phase clocks in DevLoopChan::pad (costs ~1 us per epoch)
   int prefetch;                 // fast kernel: fetch the next epoch's first chunk during the closure (corr_fast.hip; GC_DEVLOOP_NO_PREFETCH=1 in the tuning build: 0)
-  int pad_prefetch;
+  int pause;                    // a windowed record (gc_track_device_resume): a channel whose next block does not fit the buffer stops with
+                                // status 5 (more of the record follows) instead of 2 (tracking.m:241-245 is the END of the file)
+  long long origin;             // record index of the buffer's sample 0: positions (DevLoopChan::pos, gc_block::first_sample) count from the
+                                // buffer's start, absoluteSample is recorded from the record's
   // Host-fed variant (gc_track's persistent mode): the HOST closes the loop (tracking.m:302-335 stay where the reference has
   // them) but nothing is launched per epoch: member 0 of a team polls the channel's descriptor messages in host-mapped
   // memory (tag = epoch + 1), relays them to its team through desc_msg, and every member writes its six partial sums as
@@ -166,7 +172,7 @@ __device__ inline int devloop_post(const DevLoopArgs* __restrict__ dl, DevLoopCh
       }
     }
   }
-  rec(GC_TRK_ABSOLUTE_SAMPLE, (double)st.pos);
+  rec(GC_TRK_ABSOLUTE_SAMPLE, (double)(st.pos + dl->origin));
   rec(GC_TRK_REM_CODE_PHASE, st.rem_code);
   rec(GC_TRK_REM_CARR_PHASE, st.rem_carr);
   const double rem_code_new = pre.rem_code_new;
@@ -263,12 +269,12 @@ __device__ inline int devloop_post(const DevLoopArgs* __restrict__ dl, DevLoopCh
   const double step_new = code_freq_new / p.sampling_freq;
   const int n_new = (int)ceil((p.code_length - rem_code_new) / step_new);
   int status = 0;
-  if (e + 1 >= dl->n_epochs)
+  if (e + 1 >= st.epoch_budget)
     status = 1;
   else if (!(step_new > 0.0) || !(step_new < 1e6) || !(carr_freq_new == carr_freq_new))
     status = 4;  // non-finite or non-positive code step (all-zero sums give atan(0/0) = NaN): no block can be cut from it
   else if (pos_new < 0 || (unsigned long long)(pos_new + n_new) > dl->if_nsamples)
-    status = 2;
+    status = dl->pause ? 5 : 2;  // paused: the state below is the one the next window's call starts from
   st.pos = pos_new;
   st.rem_code = rem_code_new;
   st.rem_carr = rem_carr_new;

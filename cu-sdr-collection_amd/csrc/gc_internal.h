@@ -237,6 +237,11 @@ struct GcTrackResume {
 };
 int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, double* out,
                     int32_t* epochs_done, GcTrackResume* r);
+// gc_track_device over one window of a record (gc_track_device_resume / gc_track_file_device): the persistent kernels start from
+// r->state and pause, channel by channel, where the window ends.  r == nullptr: gc_track_device.  budget[c] (nullptr: p->n_epochs
+// for all): epochs channel slot c runs at most; whole_call: zero the channels after the first ended one, as gc_track does.
+int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, double* out,
+                           int32_t* epochs_done, GcTrackResume* r, const int32_t* budget, bool whole_call);
 
 // trackResults.CNo.VSMValue of finished records on the host (the host-closed loops; the device loop has its own copy in devloop.h)
 void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const double* out, const int32_t* epochs_done);

@@ -8,6 +8,11 @@
 // window k + 1 (the channels stop in lock step, within one block of each other).  Window origins are multiples of 256
 // samples: a block's address alignment - hence the order of the kernels' float additions - is the same as with the whole
 // record resident, and the results are bit-identical to gc_track's (tests/test_gpu_stream.py).
+//
+// gc_track_file_device is the same ingest with the loop closed on the device (gc_track_device_window, track.hip): one
+// persistent launch per window, the kernels' teams pausing channel by channel where the window ends.  The channels are not in
+// lock step there - each has its own count of finished epochs, and a window is left when every running channel has paused.
+// Bit-identical to gc_track_device on the resident record (tests/test_gpu_stream_device.py).
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -38,6 +43,23 @@ extern "C" int gc_track_resume(gc_context* ctx, const gc_track_params* p, int nc
   r.pause_at_end = (flags & GC_TRACK_PAUSE_AT_END) != 0;
   r.origin = origin;
   const int rc = gc_track_window(ctx, p, nch, init, out, epochs_done, &r);
+  if (paused) *paused = r.paused ? 1 : 0;
+  return rc;
+}
+
+extern "C" int gc_track_device_resume(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init,
+                                      gc_channel_state* state, int flags, int64_t origin, double* out, int32_t* epochs_done,
+                                      int32_t* paused) {
+  if (!state || origin < 0) {
+    gc_set_error("gc_track_device_resume: bad arguments");
+    return GC_E_INVALID;
+  }
+  GcTrackResume r;
+  r.state = state;
+  r.resume = (flags & GC_TRACK_RESUME) != 0;
+  r.pause_at_end = (flags & GC_TRACK_PAUSE_AT_END) != 0;
+  r.origin = origin;
+  const int rc = gc_track_device_window(ctx, p, nch, init, out, epochs_done, &r, nullptr, true);
   if (paused) *paused = r.paused ? 1 : 0;
   return rc;
 }
@@ -86,10 +108,133 @@ struct WindowLoader {
   }
 };
 
+// The device-closed windows of gc_track_file_device, once the two buffers, the loader and the first window are in place.
+// GC_E_UNSUPPORTED from the first launch (nothing tracked yet): the caller runs the host-closed windows instead.
+struct DeviceWindows {
+  gc_context* ctx;
+  const gc_track_params* p;
+  int nch;
+  const gc_channel_init* init;
+  double* out;
+  int dtype, layout;
+  uint64_t total, W, stride, margin, k0;
+  int epw;
+  uint8_t** dbuf;
+  WindowLoader* ld;
+  std::vector<gc_channel_state>* state;
+  std::vector<int32_t>* done_total;
+  int last_rc = GC_OK;
+
+  uint64_t window_len(uint64_t k) const { return std::min<uint64_t>(W, total - k * stride); }
+  bool is_last(uint64_t k) const { return k * stride + W >= total; }
+
+  int run() {
+    const int n_total = p->n_epochs;
+    std::vector<int32_t> done_w((size_t)nch, 0), budget((size_t)nch, 0);
+    std::vector<double> out_w((size_t)nch * GC_TRK_NFIELDS * epw);
+    std::vector<gc_channel_state>& st = *state;
+    std::vector<int32_t>& done = *done_total;
+    bool first_call = true, finished = false, any_range = false, any_diverged = false;
+    int rc = GC_OK;
+    for (uint64_t k = k0; !finished; ++k) {
+      const bool last = is_last(k);
+      std::thread reader;
+      std::atomic<bool> reader_ok{true};
+      if (!last) reader = std::thread([&, k]() { reader_ok = ld->load(dbuf[(k + 1) & 1], (k + 1) * stride, window_len(k + 1)); });
+      rc = gc_attach_if(ctx, dbuf[k & 1], window_len(k), dtype, layout);
+      while (rc == GC_OK) {
+        // the channels pause at epochs of their own: every one is owed its own number of epochs
+        int most = 0;
+        for (int c = 0; c < nch; ++c) {
+          const bool running = first_call || st[c].status == 0;
+          budget[c] = running ? std::min(n_total - done[c], epw) : 0;
+          most = std::max(most, budget[c]);
+        }
+        if (most <= 0) {
+          finished = true;
+          break;
+        }
+        gc_track_params pw = *p;
+        pw.n_epochs = most;
+        GcTrackResume r;
+        r.state = st.data();
+        r.resume = !first_call;
+        r.pause_at_end = !last;
+        r.origin = (int64_t)(k * stride);
+        const int wrc = gc_track_device_window(ctx, &pw, nch, init, out_w.data(), done_w.data(), &r, budget.data(), false);
+        if (wrc == GC_E_UNSUPPORTED && first_call) {
+          rc = wrc;
+          break;
+        }
+        first_call = false;
+        if (wrc != GC_OK && wrc != GC_E_RANGE && wrc != GC_E_INVALID) {  // RANGE / INVALID: a channel ended, records are valid
+          rc = wrc;
+          break;
+        }
+        any_range |= wrc == GC_E_RANGE;
+        any_diverged |= wrc == GC_E_INVALID;
+        for (int c = 0; c < nch; ++c) {
+          for (int f = 0; f < GC_TRK_NFIELDS; ++f)
+            std::copy(out_w.data() + ((size_t)c * GC_TRK_NFIELDS + f) * pw.n_epochs,
+                      out_w.data() + ((size_t)c * GC_TRK_NFIELDS + f) * pw.n_epochs + done_w[c],
+                      out + ((size_t)c * GC_TRK_NFIELDS + f) * n_total + done[c]);
+          done[c] += done_w[c];
+        }
+        // A channel that ended - the record's end in the last window, a diverged NCO anywhere - leaves the others running to their
+        // own ends, as gc_track_device does.  Of the channels still owed epochs, one that stopped short of its budget has paused
+        // (its next block is not in this window); one that used its budget up may have more blocks here.
+        bool owed = false, can_go_on = false;
+        for (int c = 0; c < nch; ++c) {
+          if (st[c].status != 0 || done[c] >= n_total) continue;
+          owed = true;
+          can_go_on |= budget[c] > 0 && done_w[c] == budget[c];
+        }
+        if (!owed || (last && !can_go_on)) {
+          finished = true;
+          break;
+        }
+        if (can_go_on) continue;  // the paused ones pause again at once, with no epoch
+        // every channel's next block must start inside the next window
+        for (int c = 0; c < nch; ++c)
+          if (st[c].status == 0 && done[c] < n_total && (uint64_t)st[c].next_sample < (k + 1) * stride) {
+            gc_set_error("gc_track_file_device: channel slot %d fell %llu samples behind the next window (margin %llu)", c,
+                         (unsigned long long)((k + 1) * stride - (uint64_t)st[c].next_sample), (unsigned long long)margin);
+            rc = GC_E_INVALID;
+          }
+        break;  // next window
+      }
+      if (reader.joinable()) reader.join();
+      if (rc == GC_OK && !last && !reader_ok) {
+        gc_set_error("gc_track_file_device: %s while reading window %llu", ld->error.c_str(), (unsigned long long)(k + 1));
+        rc = GC_E_RANGE;
+      }
+      if (rc != GC_OK) break;
+      if (last && !finished) finished = true;
+    }
+    last_rc = any_diverged ? GC_E_INVALID : any_range ? GC_E_RANGE : GC_OK;
+    return rc;
+  }
+};
+
+int track_file_impl(gc_context* ctx, const char* path, uint64_t skip_bytes, int dtype, int layout, uint64_t window_samples,
+                    const gc_track_params* p, int nch, const gc_channel_init* init, double* out, int32_t* epochs_done, bool device_loop);
+
 }  // namespace
 
 extern "C" int gc_track_file(gc_context* ctx, const char* path, uint64_t skip_bytes, int dtype, int layout, uint64_t window_samples,
                              const gc_track_params* p, int nch, const gc_channel_init* init, double* out, int32_t* epochs_done) {
+  return track_file_impl(ctx, path, skip_bytes, dtype, layout, window_samples, p, nch, init, out, epochs_done, false);
+}
+
+extern "C" int gc_track_file_device(gc_context* ctx, const char* path, uint64_t skip_bytes, int dtype, int layout, uint64_t window_samples,
+                                    const gc_track_params* p, int nch, const gc_channel_init* init, double* out, int32_t* epochs_done) {
+  return track_file_impl(ctx, path, skip_bytes, dtype, layout, window_samples, p, nch, init, out, epochs_done, true);
+}
+
+namespace {
+
+int track_file_impl(gc_context* ctx, const char* path, uint64_t skip_bytes, int dtype, int layout, uint64_t window_samples,
+                    const gc_track_params* p, int nch, const gc_channel_init* init, double* out, int32_t* epochs_done, bool device_loop) {
   if (!ctx || !path || !p || nch <= 0 || nch > GC_MAX_CHANNELS || !init || !out || !epochs_done || p->n_epochs <= 0 ||
       !(p->sampling_freq > 0) || !(p->code_length > 0) || !(p->code_freq_basis > 0)) {
     gc_set_error("gc_track_file: bad arguments");
@@ -118,6 +263,10 @@ extern "C" int gc_track_file(gc_context* ctx, const char* path, uint64_t skip_by
     close(fd);
     int rc = gc_open_if_file(ctx, path, skip_bytes, 0, dtype, layout);
     if (rc) return rc;
+    if (device_loop) {
+      rc = gc_track_device(ctx, p, nch, init, out, epochs_done);
+      if (rc != GC_E_UNSUPPORTED) return rc;
+    }
     return gc_track(ctx, p, nch, init, out, epochs_done);
   }
   // nominal block length (one code period) with head room for the code NCO; the overlap between windows
@@ -186,7 +335,17 @@ extern "C" int gc_track_file(gc_context* ctx, const char* path, uint64_t skip_by
   }
   int rc = GC_OK, last_rc = GC_OK;
   bool first_call = true, finished = false;
-  for (uint64_t k = k0; !finished; ++k) {
+  bool host_windows = !device_loop;
+  if (device_loop) {
+    DeviceWindows dw{ctx, p, nch, init, out, dtype, layout, total, W, stride, margin, k0, epw, dbuf, &ld, &state, &done_total};
+    rc = dw.run();
+    last_rc = dw.last_rc;
+    if (rc == GC_E_UNSUPPORTED) {  // not a configuration of the persistent kernels: nothing was tracked, window k0 is loaded
+      rc = GC_OK;
+      host_windows = true;
+    }
+  }
+  for (uint64_t k = k0; host_windows && !finished; ++k) {
     const bool last = is_last(k);
     std::thread reader;
     std::atomic<bool> reader_ok{true};
@@ -266,3 +425,5 @@ extern "C" int gc_track_file(gc_context* ctx, const char* path, uint64_t skip_by
   gc_fill_cno_host(ctx, p, nch, out, epochs_done);
   return last_rc;
 }
+
+}  // namespace

@@ -402,7 +402,10 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
     pa.host_tagged = ctx->h_tagged_pinned;
     std::vector<gcorr::DevLoopChan> hc((size_t)nch);
     std::memset(hc.data(), 0, sizeof(gcorr::DevLoopChan) * (size_t)nch);
-    for (int c = 0; c < nch; ++c) hc[c].blk.channel = init[c].channel;  // table staging needs the channel of each team
+    for (int c = 0; c < nch; ++c) {
+      hc[c].blk.channel = init[c].channel;  // table staging needs the channel of each team
+      hc[c].epoch_budget = n_epochs;        // the host ends the run
+    }
     auto take = [&](int slot, size_t bytes, bool host) -> hipError_t { return gc_buf_reserve(ctx->trk[slot], bytes, host); };
     hipError_t e = take(gc_context::TRK_CHAN, sizeof(gcorr::DevLoopChan) * (size_t)nch, false);
     if (e == hipSuccess) e = take(gc_context::TRK_DESC, sizeof(gcorr::msg_t) * (size_t)nch * gcorr::kDescWords, false);
@@ -932,12 +935,23 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
 }
 
 // ---- device-side loop closure (devloop.h) -----------------------------------------------------------------------
-// Same contract as gc_track for the signals the persistent kernel is instantiated for: single-arm channels whose
-// blocks qualify for the transition-mask kernel with float2 tables (GPS L1 C/A, GLONASS L1OF, BDS B1I), int8 I/Q or Q/I
-// records, no pilot.  Anything else returns GC_E_UNSUPPORTED and the caller uses gc_track.
-extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init,
-                               double* out, int32_t* epochs_done) {
-  if (!ctx || !p || nch <= 0 || nch > GC_MAX_CHANNELS || !init || !out || !epochs_done || p->n_epochs <= 0) {
+// Same contract as gc_track for what the persistent kernels are instantiated for (tests/test_gpu_ref_vectors.py runs every
+// package of the reference through it): single-arm R = 1 channels on the transition-mask kernel; one- and two-arm channels of
+// any rate, index scale and record format (int8 / int16, I/Q, Q/I, real), windowed tables (GPS L2C CL) included, on the lane
+// kernel; the three-arm folds with a derived third arm (Galileo E1-C CBOC, BDS B1C wide-band) on int8 I/Q records; everything
+// gc_track takes under GC_PREC_F64.  Anything else returns GC_E_UNSUPPORTED and the caller uses gc_track.
+//
+// gc_track_device_window is that loop on one window of a record (GcTrackResume, as gc_track_window): the DevLoopChan of a
+// channel is filled from r->state - the first block cut from it exactly as devloop_post cuts any later one - and converted
+// back after the launch.  Positions on the device count from the buffer's first sample, absoluteSample is recorded from the
+// record's (DevLoopArgs::origin).  With r->pause_at_end a channel whose next block does not fit the buffer stops with status 5
+// instead of 2; channels pause independently, so `budget[c]` (null: p->n_epochs) is the number of epochs channel c runs at
+// most.  `whole_call`: this is a caller's complete call - the channels after the first ended one are zeroed as gc_track does;
+// gc_track_file_device, which assembles a call from many windows, does that once at its end.
+int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, double* out,
+                           int32_t* epochs_done, GcTrackResume* r, const int32_t* budget, bool whole_call) {
+  if (r) r->paused = false;
+  if (!ctx || !p || nch <= 0 || nch > GC_MAX_CHANNELS || !init || !out || !epochs_done || p->n_epochs <= 0 || (r && (!r->state || r->origin < 0))) {
     gc_set_error("gc_track_device: bad arguments");
     return GC_E_INVALID;
   }
@@ -989,32 +1003,67 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   const int n_epochs = p->n_epochs;
   std::vector<gcorr::DevLoopChan> hc((size_t)nch);
   std::memset(hc.data(), 0, sizeof(gcorr::DevLoopChan) * (size_t)nch);
+  int nominal_blksize = 0;
   int lowrate = 2;
   bool share = true;
+  const int64_t origin = r ? r->origin : 0;
   for (int c = 0; c < nch; ++c) {
     gcorr::DevLoopChan& s = hc[c];
-    s.pos = p->skip_samples + init[c].code_phase - 1;
+    s.pos = p->skip_samples + init[c].code_phase - 1 - origin;
     s.code_freq = s.code_freq_basis = init[c].code_freq;
     s.carr_freq = s.carr_basis = init[c].acquired_freq;
     s.table_phase = init[c].table_phase;
+    s.epoch_budget = budget ? std::max(0, std::min(budget[c], n_epochs)) : n_epochs;
+    // what selects the kernel and sizes the teams - hence the order of the float additions - comes from the channel's NOMINAL first
+    // block (remainder 0, the acquired code frequency), which a resident call's first block is: every window of a record takes the
+    // same kernel with the same teams as the whole record would
+    gc_block nominal;
+    std::memset(&nominal, 0, sizeof nominal);
+    nominal.channel = init[c].channel;
+    nominal.code_phase_step = init[c].code_freq / p->sampling_freq;
+    nominal.blksize = (int)std::ceil(p->code_length / nominal.code_phase_step);
+    nominal.el_spacing = p->el_spacing;
+    if (c == 0) nominal_blksize = nominal.blksize;
+    if (r && r->resume) {  // continue where the previous window stopped (gc_track_window's counterpart)
+      const gc_channel_state& g = r->state[c];
+      if (g.status != 0) s.status = 2;  // ended before: does not run
+      s.pos = g.next_sample - origin;
+      s.code_freq = g.code_freq;
+      s.rem_code = g.rem_code_phase;
+      s.carr_freq = g.carr_freq;
+      s.rem_carr = g.rem_carr_phase;
+      s.old_code_nco = g.old_code_nco;
+      s.old_code_err = g.old_code_error;
+      s.old_carr_nco = g.old_carr_nco;
+      s.old_carr_err = g.old_carr_error;
+      s.d_carr_err = g.d_carr_error;
+      s.d2_carr_err = g.d2_carr_error;
+      s.table_phase = g.table_phase;
+    }
+    // the first block: the statements devloop_post ends every epoch with (tracking.m:219-222, GPS_L2C tracking.m:261)
     const double step = s.code_freq / p->sampling_freq;
-    const int n = (int)std::ceil((p->code_length - s.rem_code) / step);
+    const bool finite = step > 0.0 && step < 1e6 && s.carr_freq == s.carr_freq;
+    const int n = finite ? (int)std::ceil((p->code_length - s.rem_code) / step) : 0;
     gc_block& b = s.blk;
     b.channel = init[c].channel;
     if (p->table_phase_count > 0 && s.table_phase > 0)  // GPS_L2C tracking.m:261: index + codeLength*(CLCodePhase-1)
       b.table_offset[1] = (int32_t)p->code_length * (s.table_phase - 1);
     b.blksize = n;
     b.first_sample = s.pos;
-    b.rem_code_phase = 0.0;
+    b.rem_code_phase = s.rem_code;
     b.code_phase_step = step;
     b.el_spacing = p->el_spacing;
     b.carr_freq = s.carr_freq;
-    b.rem_carr_phase = 0.0;
-    if (s.pos < 0 || (uint64_t)(s.pos + n) > ctx->if_nsamples) s.status = 2;  // not even one block: tracking.m:241-245
-    gc_block probe = b;
-    probe.code_phase_step = step * 1.001;  // head-room for the code NCO
+    b.rem_carr_phase = s.rem_carr;
+    if (s.status == 0) {
+      if (!finite) s.status = 4;
+      else if (s.pos < 0 || (uint64_t)(s.pos + n) > ctx->if_nsamples) s.status = (r && r->pause_at_end) ? 5 : 2;  // not even one block: tracking.m:241-245
+      else if (s.epoch_budget <= 0) s.status = 1;
+    }
+    gc_block probe = nominal;
+    probe.code_phase_step = nominal.code_phase_step * 1.001;  // head-room for the code NCO
     lowrate = std::min(lowrate, gc_block_lowrate_level(ctx, probe));
-    share = share && gc_block_shares_el(ctx, b);
+    share = share && gc_block_shares_el(ctx, nominal);
   }
   if (!i8c) lowrate = std::min(lowrate, 1);  // 16-sample chunks are an int8 I/Q format (corr_fast.hip)
   // transition-mask kernel (one-wave members) where it applies, else the lane kernel (16-wave member workgroups)
@@ -1035,7 +1084,7 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   } else {
     for (int c = 0; c < nch; ++c) share_lane = share_lane && gc_block_shares_el_lane(ctx, hc[c].blk);
     // member workgroups per channel: about four 64-sample steps per lane; the closer polls (members - 1) * 6 * arms <= 64 messages
-    const int nsamp = hc[0].blk.blksize;
+    const int nsamp = nominal_blksize;
     lane_waves = 8;  // measured best for both the 1-ms and the 4-ms packages (scripts/devloop_lane_sweep.py)
     if (const char* e = GC_TUNE_ENV("GC_DEVLOOP_WAVES")) lane_waves = std::max(1, std::min(8, std::atoi(e)));  // the device-loop instantiations are bounded to 8 waves
     const int max_members = max_arms == 1 ? 8 : max_arms == 2 ? 6 : 4;  // (members - 1) * 6 * arms messages <= 64 lanes
@@ -1061,6 +1110,8 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   ha.if_nsamples = ctx->if_nsamples;
   ha.n_epochs = n_epochs;
   ha.splits = splits;
+  ha.pause = (r && r->pause_at_end) ? 1 : 0;
+  ha.origin = origin;
   ha.code_index_scale_is_one = 1;
   if (const char* e = GC_TUNE_ENV("GC_DEVLOOP_SCOPE")) ha.reserved = std::atoi(e);  // message scope (devloop.h): 0 system (default), 2 agent
   ha.timing = GC_TUNE_ENV("GC_DEVLOOP_TIMING") ? std::atoi(GC_TUNE_ENV("GC_DEVLOOP_TIMING")) : 0;  // 1: host + in-kernel phase clocks, 2: host only
@@ -1074,7 +1125,8 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   if (e == hipSuccess) e = gc_buf_reserve(ctx->trk[gc_context::TRK_DESC], desc_bytes, false);
   if (e == hipSuccess) e = gc_buf_reserve(ctx->trk[gc_context::TRK_RECORDS], rec_bytes, false);
   if (e == hipSuccess) e = gc_buf_reserve(ctx->trk[gc_context::TRK_ARGS], sizeof ha, false);
-  const int cno_nk = (p->cno_interval > 1 && ctx->cno_out && p->cno_mode == GC_CNO_VSM) ? n_epochs / p->cno_interval : 0;
+  // the estimator's running sums are local to the launch (e % K): a call on a window delivers no in-loop C/N0, as gc_track_resume
+  const int cno_nk = (!r && p->cno_interval > 1 && ctx->cno_out && p->cno_mode == GC_CNO_VSM) ? n_epochs / p->cno_interval : 0;
   const bool want_cno = cno_nk > 0 && (long long)nch * cno_nk <= ctx->cno_cap;
   const size_t cno_bytes = sizeof(double) * (size_t)nch * (size_t)std::max(cno_nk, 1);
   if (e == hipSuccess && want_cno) e = gc_buf_reserve(ctx->trk[gc_context::TRK_CNO], cno_bytes, false);
@@ -1099,7 +1151,7 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   for (int c = 0; c < nch; ++c) {
     unsigned long long q[gcorr::kDescWords] = {0};
     std::memcpy(q, &hc[c].blk, sizeof(gc_block));
-    q[gcorr::kDescWords - 1] = (unsigned long long)(hc[c].status == 2 ? 2 : 0);
+    q[gcorr::kDescWords - 1] = (unsigned long long)hc[c].status;  // not 0: the team leaves before its first epoch
     for (int i = 0; i < gcorr::kDescWords; ++i) hdesc[(size_t)c * gcorr::kDescWords + i] = gcorr::msg_t{(unsigned int)q[i], (unsigned int)(q[i] >> 32), 1u, 0u};
   }
   if (e == hipSuccess) e = hipMemcpyAsync(ha.desc_msg, hdesc.data(), desc_bytes, hipMemcpyHostToDevice, ctx->stream);
@@ -1137,7 +1189,7 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
     cleanup();
     const int cap0 = ctx->persist_member_cap;
     ctx->persist_member_cap = (splits + 1) / 2;
-    rc = gc_track_device(ctx, p, nch, init, out, epochs_done);
+    rc = gc_track_device_window(ctx, p, nch, init, out, epochs_done, r, budget, whole_call);
     ctx->persist_member_cap = cap0;
     return rc;
   }
@@ -1164,7 +1216,7 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
   if (rc) return rc;
   // same early-return semantics as gc_track: channels after the first exhausted one are never run
   int first_aborted = nch;
-  bool timeout = false, diverged = false;
+  bool timeout = false, diverged = false, ranged = false;
   for (int c = 0; c < nch; ++c) {
     timeout |= hc[c].status == 3;
     diverged |= hc[c].status == 4;
@@ -1172,13 +1224,16 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
       std::fprintf(stderr, "devloop ch %d: correlate %.2f us, wait partials %.2f us, close+publish %.2f us per epoch (closer)\n", c,
                    hc[c].pad[0] / hc[c].epochs_done * 0.01, hc[c].pad[1] / hc[c].epochs_done * 0.01, hc[c].pad[2] / hc[c].epochs_done * 0.01);
     if ((hc[c].status == 2 || hc[c].status == 4) && first_aborted == nch) first_aborted = c;
+    // a channel that came in ended (resumed state) is not this call's short read
+    ranged |= hc[c].status == 2 && !(r && r->resume && r->state[c].status != 0);
+    if (r && hc[c].status == 5) r->paused = true;
   }
   if (timeout) {
     gc_set_error("gc_track_device: a team member timed out waiting for its epoch descriptor");
     return GC_E_HIP;
   }
   for (int c = 0; c < nch; ++c) {
-    if (c > first_aborted) {
+    if (whole_call && c > first_aborted) {
       double* o = out + (size_t)c * GC_TRK_NFIELDS * n_epochs;
       std::fill(o, o + (size_t)GC_TRK_NFIELDS * n_epochs, 0.0);
       epochs_done[c] = 0;
@@ -1186,14 +1241,39 @@ extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nc
       epochs_done[c] = hc[c].epochs_done;
     }
   }
-  if (p->cno_mode != GC_CNO_VSM) gc_fill_cno_host(ctx, p, nch, out, epochs_done);  // Calc_CNo_PLD: from the records, as everywhere
+  if (r) {  // the loop state the next window's call starts from, in record coordinates
+    for (int c = 0; c < nch; ++c) {
+      const gcorr::DevLoopChan& s = hc[c];
+      gc_channel_state& g = r->state[c];
+      g.next_sample = s.pos + origin;
+      g.code_freq = s.code_freq;
+      g.rem_code_phase = s.rem_code;
+      g.carr_freq = s.carr_freq;
+      g.rem_carr_phase = s.rem_carr;
+      g.old_code_nco = s.old_code_nco;
+      g.old_code_error = s.old_code_err;
+      g.old_carr_nco = s.old_carr_nco;
+      g.old_carr_error = s.old_carr_err;
+      g.d_carr_error = s.d_carr_err;
+      g.d2_carr_error = s.d2_carr_err;
+      g.table_phase = s.table_phase;
+      g.status = (s.status == 2 || s.status == 4) ? 2 : 0;  // running or paused | ended
+      g.reserved = 0;
+    }
+  }
+  if (!r && p->cno_mode != GC_CNO_VSM) gc_fill_cno_host(ctx, p, nch, out, epochs_done);  // Calc_CNo_PLD: from the records, as everywhere
   if (diverged) {
     gc_set_error("gc_track_device: a channel's code / carrier NCO became non-finite (all-zero correlator sums?); its records end there");
     return GC_E_INVALID;
   }
-  if (first_aborted < nch) {
+  if (ranged) {
     gc_set_error("Not able to read the specified number of samples for tracking (channel slot %d)", first_aborted);
     return GC_E_RANGE;
   }
   return GC_OK;
+}
+
+extern "C" int gc_track_device(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init,
+                               double* out, int32_t* epochs_done) {
+  return gc_track_device_window(ctx, p, nch, init, out, epochs_done, nullptr, nullptr, true);
 }

@@ -295,9 +295,12 @@ class Engine:
         L.check(self._lib.gc_set_cno_output(self._ctx, cno.ctypes.data_as(C.POINTER(C.c_double)), cno.size))
         return cno
 
-    def track_resume(self, params: L.gc_track_params, inits, state=None, origin: int = 0, pause_at_end: bool = False):
+    def track_resume(self, params: L.gc_track_params, inits, state=None, origin: int = 0, pause_at_end: bool = False,
+                     device_loop: bool = False):
         """gc_track_resume on the window currently loaded (its first sample = record sample `origin`): continues from `state`
         (a ctypes array of gc_channel_state from a previous call; None starts from `inits`).
+        device_loop: gc_track_device_resume - the loop closed on the GPU, every channel pausing at an epoch of its own; a state
+        written by either loop continues under the other.
         Returns (fields, epochs_done, status, state, paused)."""
         nch = len(inits)
         arr = (L.gc_channel_init * nch)(*inits)
@@ -307,16 +310,19 @@ class Engine:
         out = np.zeros((nch, L.GC_TRK_NFIELDS, params.n_epochs))
         done = (C.c_int32 * nch)()
         paused = C.c_int32(0)
-        st = self._lib.gc_track_resume(self._ctx, C.byref(params), nch, arr, state, flags, int(origin),
-                                       out.ctypes.data_as(C.POINTER(C.c_double)), done, C.byref(paused))
+        fn = self._lib.gc_track_device_resume if device_loop else self._lib.gc_track_resume
+        st = fn(self._ctx, C.byref(params), nch, arr, state, flags, int(origin),
+                out.ctypes.data_as(C.POINTER(C.c_double)), done, C.byref(paused))
         if st not in (L.GC_OK, L.GC_E_RANGE):
             L.check(st)
         return {name: out[:, i, :] for i, name in enumerate(L.TRK_FIELDS)}, np.array(list(done)), st, state, bool(paused.value)
 
     def track_file(self, path: str, params: L.gc_track_params, inits, window_samples: int, dtype: int = L.GC_I8,
-                   layout: int = L.GC_IQ, skip_bytes: int = 0, precision: str | None = None):
+                   layout: int = L.GC_IQ, skip_bytes: int = 0, precision: str | None = None, device_loop: bool = False):
         """gc_track_file: tracking(fid, channel, settings) on a file of any size, at most 2 * window_samples samples resident
-        (the next window is read and uploaded while the current one is tracked).  precision as track().  Returns as track()."""
+        (the next window is read and uploaded while the current one is tracked).  precision as track().
+        device_loop: gc_track_file_device - one persistent launch per window closes the loop on the GPU (host-closed windows where
+        the device loop does not cover the configuration: last_track_mode() tells).  Returns as track()."""
         code = precision_code(precision)
         nch = len(inits)
         arr = (L.gc_channel_init * nch)(*inits)
@@ -325,8 +331,9 @@ class Engine:
         cno = self._cno_buffer(params, nch)
         try:
             with self._precision_for_call(code):
-                st = self._lib.gc_track_file(self._ctx, os.fsencode(path), int(skip_bytes), int(dtype), int(layout), int(window_samples),
-                                             C.byref(params), nch, arr, out.ctypes.data_as(C.POINTER(C.c_double)), done)
+                fn = self._lib.gc_track_file_device if device_loop else self._lib.gc_track_file
+                st = fn(self._ctx, os.fsencode(path), int(skip_bytes), int(dtype), int(layout), int(window_samples),
+                        C.byref(params), nch, arr, out.ctypes.data_as(C.POINTER(C.c_double)), done)
         finally:
             if cno is not None:
                 self._lib.gc_set_cno_output(self._ctx, None, 0)

@@ -283,7 +283,8 @@ int gc_track_resume(gc_context* ctx, const gc_track_params* p, int nch, const gc
                     int32_t* paused);
 /* tracking(fid, channel, settings) on a file of any size: the record is read in windows of `window_samples` samples into two
  * device buffers (the next window's read + upload runs while the current one is tracked: at most 2 * window_samples
- * samples are resident), results as gc_track's.  `skip_bytes`: file offset of record sample 0.  Host-closed loop. */
+ * samples are resident), results as gc_track's.  `skip_bytes`: file offset of record sample 0.  Host-closed loop;
+ * gc_track_file_device (below) is the same with the loop closed on the device. */
 int gc_track_file(gc_context* ctx, const char* path, uint64_t skip_bytes, int dtype, int layout, uint64_t window_samples,
                   const gc_track_params* p, int nch, const gc_channel_init* init, double* out, int32_t* epochs_done);
 
@@ -292,12 +293,30 @@ int gc_track_file(gc_context* ctx, const char* path, uint64_t skip_bytes, int dt
  * no fences) and execute tracking.m:302-335 in float64 themselves (csrc/devloop.h).  Covered: int8 I/Q or Q/I records;
  * single-arm R = 1 channels on the transition-mask kernel (GPS L1 C/A, GLONASS L1OF, BDS B1I) and one- or two-arm
  * channels of any rate and index scale with pilot_combine 0-3 on the lane kernel (GPS L5, BDS B2a / B3I, Galileo E5a /
- * E5b / E1 B+C, BDS B1C narrow-band), and the three-arm Galileo E1-C CBOC fold (pilot_combine 5, third arm derived).
- * Other three-arm or mixed-multiplier channels (pilot_combine 4), windowed tables (GPS L2C CL), int16 and real records
- * return GC_E_UNSUPPORTED: use gc_track.  Under GC_PREC_F64 every configuration gc_track takes is covered (one float64
- * workgroup per channel; only a grid that does not fit the device next to other persistent kernels returns GC_E_UNSUPPORTED). */
+ * E5b / E1 B+C, BDS B1C narrow-band, GPS L2C with its windowed CL table) in every record format (int8 / int16; I/Q, Q/I,
+ * real), and the three-arm folds with a derived third arm on int8 I/Q or Q/I records (Galileo E1-C CBOC, pilot_combine 5;
+ * BDS B1C wide-band, pilot_combine 4): every package of the reference (tests/test_gpu_ref_vectors.py).  Other three-arm or
+ * mixed-multiplier channels return GC_E_UNSUPPORTED: use gc_track.  Under GC_PREC_F64 every configuration gc_track takes is
+ * covered (one float64 workgroup per channel; only a grid that does not fit the device next to other persistent kernels
+ * returns GC_E_UNSUPPORTED). */
 int gc_track_device(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init,
                     double* out, int32_t* epochs_done);
+/* gc_track_resume with the loop closed on the device: the persistent kernels start every channel from `state` (or, without
+ * GC_TRACK_RESUME, from `init`), count positions from `origin` and, with GC_TRACK_PAUSE_AT_END, pause a channel whose next
+ * block does not fit the IF buffer instead of ending it.  The channels are NOT in lock step: each pauses at an epoch of its
+ * own (epochs_done[c] differ by an epoch or so at a window's end), *paused = 1 when at least one did.  Arguments, flags, `state`
+ * and the results' layout are gc_track_resume's - a state written by either function is accepted by the other -, the return
+ * codes gc_track_device's (GC_E_UNSUPPORTED exactly where it returns it).  No in-loop C/N0 (gc_set_cno_output) on a window, as
+ * with gc_track_resume.  Detect by symbol: GC_API_VERSION is unchanged. */
+int gc_track_device_resume(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init,
+                           gc_channel_state* state, int flags, int64_t origin, double* out, int32_t* epochs_done,
+                           int32_t* paused);
+/* gc_track_file with the loop closed on the device: same windows, reader thread, overlap and first window; one persistent
+ * launch per window (gc_track_device_resume).  Results are bit-identical to gc_track_device on the resident record; a file that
+ * fits one window goes to gc_track_device.  Where the device loop answers GC_E_UNSUPPORTED the call runs gc_track_file's
+ * host-closed windows (gc_debug_last_track_mode tells which loop ran). */
+int gc_track_file_device(gc_context* ctx, const char* path, uint64_t skip_bytes, int dtype, int layout, uint64_t window_samples,
+                         const gc_track_params* p, int nch, const gc_channel_init* init, double* out, int32_t* epochs_done);
 
 /* ---- several tracking() calls at once (BASELINE config 5: the all-constellation mix) ---------------------------
  * The reference tracks the channels of ONE package per call (tracking.m:133 loops over settings.numberOfChannels with one

@@ -238,10 +238,13 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxFree(blk);
     if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
     if (rc) fail("gc_correlate");
-  } else if (!strcmp(cmd, "track") || !strcmp(cmd, "track_device") || !strcmp(cmd, "track_file")) {
+  } else if (!strcmp(cmd, "track") || !strcmp(cmd, "track_device") || !strcmp(cmd, "track_file") || !strcmp(cmd, "track_file_device")) {
     /* [trk, epochs, status] = gnsscorr_mex('track', h, p, chanTable)
        [trk, epochs, status] = gnsscorr_mex('track_file', h, p, chanTable, fileName, windowSamples, dataType, fileType[, 'QI']):
-       the same on a file of any size, at most 2 * windowSamples samples resident (gc_track_file) */
+       the same on a file of any size, at most 2 * windowSamples samples resident (gc_track_file)
+       [trk, epochs, status] = gnsscorr_mex('track_file_device', ...same arguments...): the windows' loops closed on the GPU
+       (gc_track_file_device; host-closed windows where the device loop does not cover the configuration) */
+    const int file_device = !strcmp(cmd, "track_file_device");
     gc_track_params p;
     track_params_from(prhs[2], &p);
     int nch = 0;
@@ -259,7 +262,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       if (gc_set_cno_output(handle(prhs[1]), mxGetDoubles(cno), (int64_t)(nv * nk * (mwSize)nch))) fail("gc_set_cno_output");
     }
     int rc;
-    if (!strcmp(cmd, "track_file")) {
+    if (!strcmp(cmd, "track_file") || file_device) {
       char path[4096], dtype[16];
       mxGetString(prhs[4], path, sizeof path);
       mxGetString(prhs[6], dtype, sizeof dtype);
@@ -270,8 +273,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (!strcmp(order, "QI")) layout = GC_QI;
       }
       if (gc_set_sampling_freq(handle(prhs[1]), p.sampling_freq)) fail("gc_set_sampling_freq");
-      rc = gc_track_file(handle(prhs[1]), path, 0, !strcmp(dtype, "int16") ? GC_I16 : GC_I8, layout, (uint64_t)mxGetScalar(prhs[5]), &p,
-                         nch, init, mxGetDoubles(plhs[0]), done);
+      rc = (file_device ? gc_track_file_device : gc_track_file)(handle(prhs[1]), path, 0, !strcmp(dtype, "int16") ? GC_I16 : GC_I8, layout,
+                                                                (uint64_t)mxGetScalar(prhs[5]), &p, nch, init, mxGetDoubles(plhs[0]), done);
     } else {
       /* track_device: the same loop closed on the GPU in one persistent launch (gc_track_device); GC_E_UNSUPPORTED for the
          configurations it does not cover - the caller then falls back to 'track' */

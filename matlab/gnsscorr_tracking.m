@@ -60,7 +60,8 @@ if isempty(active), return; end
 
 %--- the record: uploaded once per file, from byte 0, so that absoluteSample stays file-relative (ftell, tracking.m:212-216) ---
 % A record larger than the device: settings.gnsscorrWindowSamples > 0 tracks it window by window instead (gc_track_file: two
-% alternating device buffers of that many samples, the next window read and uploaded while the current one is tracked).
+% alternating device buffers of that many samples, the next window read and uploaded while the current one is tracked;
+% gc_track_file_device when settings.gnsscorrDeviceLoop is set too).
 fileName = fopen(fid);
 order = 'IQ';
 if pkg.qiOrder, order = 'QI'; end
@@ -150,7 +151,11 @@ precision = 'single';
 if isfield(settings, 'gnsscorrPrecision'), precision = settings.gnsscorrPrecision; end
 prevPrecision = gnsscorr_mex('set_precision', h, precision);
 if windowed
-    [trk, epochs, status, cno] = gnsscorr_mex('track_file', h, p, chanTable, fileName, settings.gnsscorrWindowSamples, settings.dataType, ...
+    % with settings.gnsscorrDeviceLoop as well: every window's loops closed on the GPU, one persistent launch per window
+    % (gc_track_file_device; the host-closed windows where the device loop does not cover the configuration)
+    fileCmd = 'track_file';
+    if isfield(settings, 'gnsscorrDeviceLoop') && settings.gnsscorrDeviceLoop, fileCmd = 'track_file_device'; end
+    [trk, epochs, status, cno] = gnsscorr_mex(fileCmd, h, p, chanTable, fileName, settings.gnsscorrWindowSamples, settings.dataType, ...
                                               settings.fileType, order);
 else
     status = -6;
