@@ -863,8 +863,16 @@ static int validate_blocks(gc_context* ctx, int64_t n, const gc_block* b, int* a
                    (unsigned long long)ctx->if_nsamples);
       return GC_E_RANGE;  // tracking.m:241-245
     }
-    // highest table index the ramps can reach must stay inside the staged window
+    // highest and lowest table index the ramps can reach must stay inside the staged window, which starts at the entry
+    // table_offset names: the early ramp's first sample (rem - d) * R * mult > -1, i.e. index ceil(.) >= 0 (MATLAB index >= 1;
+    // tracking.m would stop with an index error on 0)
     for (int a = 0; a < c.arms; ++a) {
+      const double tmin = (k.rem_code_phase - k.el_spacing) * c.index_scale * c.mult[a];
+      if (!(std::ceil(tmin) >= 0.0)) {
+        gc_set_error("block %lld: early code ramp starts at index %g, below the table entry at table_offset (arm %d)", (long long)i,
+                     std::ceil(tmin), a);
+        return GC_E_INVALID;
+      }
       const double tmax = ((k.blksize - 1) * k.code_phase_step + k.rem_code_phase + k.el_spacing) *
                           c.index_scale * c.mult[a];
       const int stage = (c.window[a] > 0) ? std::min(c.window[a], c.nent[a]) : c.nent[a];

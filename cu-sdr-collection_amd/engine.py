@@ -222,7 +222,8 @@ class Engine:
 
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition
-        (corr_multi.hip), -1 mixed."""
+        (corr_multi.hip), 5 hybrid for channels with a derived six-fold arm (corr_cboc.hip), 6 float64 (corr_f64.hip), -1 mixed
+        (exact per-sample kernel); -2 before the first launch."""
         return int(self._lib.gc_debug_last_kernel(self._ctx))
 
     def last_track_mode(self) -> int:

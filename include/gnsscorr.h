@@ -112,7 +112,15 @@ int gc_set_code_window(gc_context* ctx, int channel, int arm, int window_entries
 
 /* ---- correlator (replaces tracking.m:247-300) --------------------------------------- */
 /* One integrate-and-dump block = the five scalars the reference records per epoch
- * (tracking.m:212-216,249,277,314,332) + block geometry. */
+ * (tracking.m:212-216,249,277,314,332) + block geometry.
+ * The fields of a descriptor that are accepted (other values are GC_E_INVALID, samples beyond the IF buffer GC_E_RANGE; a channel
+ * that is not configured, a missing table, record or sampling frequency are GC_E_STATE): blksize >= 1, first_sample >= 0,
+ * code_phase_step > 0, el_spacing >= 0, rem_code_phase > -1, finite carr_freq and rem_carr_phase, and for every arm a
+ * (R = index_scale, m_a = arm_mult, counted from the entry table_offset[a] names, where the staged table starts):
+ *   el_spacing * R * max_a(m_a) < 1,
+ *   (rem_code_phase - el_spacing) * R * m_a > -1        the early ramp's first index ceil(.) is >= 0: MATLAB index >= 1,
+ *                                                       where tracking.m would stop with an index error on 0,
+ *   ceil(((blksize - 1) * code_phase_step + rem_code_phase + el_spacing) * R * m_a) inside the table (or its window). */
 typedef struct gc_block {
   int32_t channel;          /* index given to gc_set_channel */
   int32_t blksize;          /* N, tracking.m:222 */
