@@ -4,13 +4,18 @@
 // written by ONE store instruction and read by ONE load instruction, both at system scope (sc0 sc1: no cache on the
 // way), so no flag, counter, atomic or fence is needed:
 //   fast kernel (corr_fast.hip): all-gather - every member stores its six partial sums as two messages {f, f, f, tag}, polls the
-//   whole team's messages (one per lane), adds them in double in a fixed order and closes the loop ITSELF (discriminators,
-//   loop filters, next block geometry - the same float64 statements as gc_track's host loop, tracking.m:302-335); identical
-//   inputs give identical descriptors, so nothing is broadcast: ONE one-way propagation delay per epoch.  Member 0 writes
-//   the epoch's records.
+//   whole team's messages (one per lane), adds them in double in a fixed order and closes the loop ITSELF (devloop_pre /
+//   devloop_post below); identical inputs give identical descriptors, so nothing is broadcast: ONE one-way propagation delay
+//   per epoch.  Member 0 writes the epoch's records.
 //   lane kernel (corr_lane.hip): gather and broadcast - member 0 (the closer) polls the other members' messages, closes the
 //   loop, writes the records and publishes the next descriptor as ten messages {word, tag} that the other members poll.
 // Channels never wait for each other.  All team workgroups must be co-resident: the launch is cooperative.  Polls are bounded.
+//
+// The closure itself - tracking.m:219-222, 241-245, 273-283, 302-348 in float64, statement for statement in the reference's
+// operation order - exists ONCE, here, as __host__ __device__ code: devloop_cut (the next block), devloop_pre / devloop_post
+// (one epoch), gcorr::cno_ratio (the C/N0 tail) and the loop state DevLoopChan with its conversion from and to the public
+// gc_channel_state.  The device loops call it from their kernels, gc_track's host loop (track.hip) from the thread that polls
+// the records, tests/loop_closure_shim.hip from a CPU test that replays the reference's recorded sums through it.
 #pragma once
 #include "gc_internal.h"
 
@@ -75,43 +80,150 @@ struct DevLoopArgs {
   void* host_tagged;            // TaggedSlot [nch][splits][GC_OUT_STRIDE], host-mapped
 };
 
-#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
-// Message scope (g_msg_scope, set per launch from DevLoopArgs::reserved): 0 = system (sc0 sc1: past every cache),
-// 1 = workgroup (sc0: past the CU's L1 only — the team's L2 is the meeting point; valid when the whole team runs on ONE
-// XCD, which the launch arranges and the kernel verifies through HW_REG_XCC_ID before switching to it), 2 = agent (sc1).
-__device__ __forceinline__ msg_t msg_load(const msg_t* p, int scope = 0) {
-  msg_t v;
-  if (scope == 1)
-    asm volatile("global_load_dwordx4 %0, %1, off sc0\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-  else if (scope == 2)
-    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-  else
-    asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-__device__ __forceinline__ void msg_store(msg_t* p, msg_t v, int scope = 0) {
-  if (scope == 1)
-    asm volatile("global_store_dwordx4 %0, %1, off sc0" : : "v"(p), "v"(v) : "memory");
-  else if (scope == 2)
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
-  else
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
+// ---- host: what an entry point fills in before the loop runs -------------------------------------------------------
+// Common/calcLoopCoef.m:41-45
+inline void calc_loop_coef(double lbw, double zeta, double k, double* tau1, double* tau2) {
+  const double wn = lbw * 8 * zeta / (4 * zeta * zeta + 1);
+  *tau1 = k / (wn * wn);
+  *tau2 = 2.0 * zeta / wn;
 }
 
-// Closing member: lane-uniform float64 restatement of tracking.m:273-348 for one channel and epoch — the same statements
-// as gc_track's host loop (track.hip), pilot handling modes 0-3 included — in two parts, so that the closer of the fast
-// kernel can run the first one while the other members' partial sums are still on their way:
+// The closure's own inputs of DevLoopArgs: the parameters, the loop coefficients and their quotients, the window of the record.
+inline void devloop_set_loop(DevLoopArgs& a, const gc_track_params& p, unsigned long long if_nsamples, long long origin, bool pause) {
+  a.prm = p;
+  calc_loop_coef(p.dll_noise_bw, p.dll_damping, 1.0, &a.tau1code, &a.tau2code);   // tracking.m:100-102
+  calc_loop_coef(p.pll_noise_bw, p.pll_damping, 0.25, &a.tau1carr, &a.tau2carr);  // tracking.m:109-110
+  a.k1code = a.tau2code / a.tau1code;
+  a.k2code = p.int_time / a.tau1code;
+  a.k1carr = a.tau2carr / a.tau1carr;
+  a.k2carr = p.int_time / a.tau1carr;
+  a.if_nsamples = if_nsamples;
+  a.origin = origin;
+  a.pause = pause ? 1 : 0;
+}
+
+// Loop state of a channel that starts (g == nullptr: tracking.m:150-168) or continues where the previous window stopped.
+// gc_channel_state counts positions from the start of the record, DevLoopChan from the buffer's sample 0 = record sample `origin`.
+inline void devloop_state_in(DevLoopChan& s, const gc_track_params& p, const gc_channel_init& in, const gc_channel_state* g, long long origin) {
+  s.pos = p.skip_samples + in.code_phase - 1 - origin;       // :150-152
+  s.code_freq = s.code_freq_basis = in.code_freq;           // :163 / GPS_L5C :165
+  s.carr_freq = s.carr_basis = in.acquired_freq;            // :167-168
+  s.table_phase = in.table_phase;
+  s.blk.channel = in.channel;
+  s.blk.el_spacing = p.el_spacing;
+  if (!g) return;
+  if (g->status != 0) s.status = 2;  // ended before: does not run
+  s.pos = g->next_sample - origin;
+  s.code_freq = g->code_freq;
+  s.rem_code = g->rem_code_phase;
+  s.carr_freq = g->carr_freq;
+  s.rem_carr = g->rem_carr_phase;
+  s.old_code_nco = g->old_code_nco;
+  s.old_code_err = g->old_code_error;
+  s.old_carr_nco = g->old_carr_nco;
+  s.old_carr_err = g->old_carr_error;
+  s.d_carr_err = g->d_carr_error;
+  s.d2_carr_err = g->d2_carr_error;
+  s.table_phase = g->table_phase;
+}
+inline void devloop_state_out(gc_channel_state& g, const DevLoopChan& s, long long origin) {
+  g.next_sample = s.pos + origin;
+  g.code_freq = s.code_freq;
+  g.rem_code_phase = s.rem_code;
+  g.carr_freq = s.carr_freq;
+  g.rem_carr_phase = s.rem_carr;
+  g.old_code_nco = s.old_code_nco;
+  g.old_code_error = s.old_code_err;
+  g.old_carr_nco = s.old_carr_nco;
+  g.old_carr_error = s.old_carr_err;
+  g.d_carr_error = s.d_carr_err;
+  g.d2_carr_error = s.d2_carr_err;
+  g.table_phase = s.table_phase;
+  g.status = (s.status == 2 || s.status == 4) ? 2 : 0;  // ended | running, paused or out of epochs
+  g.reserved = 0;
+}
+
+// ---- host and device: the closure ----------------------------------------------------------------------------------
+// |Pav / (2*Nv)| of CNoVSM.m:38-47 / Calc_CNo_PLD.m:47-68 from the mean and the N-1 variance of Z = I^2 + Q^2:
+// Pav = sqrt(Zm^2 - Zv), Nv = (Zm - Pav)/2; the square root of a negative number is imaginary, abs() of the complex quotient
+__host__ __device__ inline double cno_ratio(double zm, double zv) {
+  const double d = zm * zm - zv;
+  if (d >= 0.0) {
+    const double pav = sqrt(d);
+    return fabs(pav / (zm - pav));
+  }
+  const double s2 = -d;  // Pav imaginary: |i*s / (Zm - i*s)|
+  return sqrt(s2 / (zm * zm + s2));
+}
+
+// The block a channel correlates next (tracking.m:219-222), cut from the four numbers of its loop state that decide it.  status: 0,
+// or why there is no such block: 4 the code step is not finite / not positive or the carrier frequency NaN (all-zero sums give
+// atan(0/0)): no block can be cut from it; 2 the block does not lie inside the buffer (:241-245), 5 instead when more of the record
+// follows this window (DevLoopArgs::pause).  `spent`: the channel has run its epochs, 1 whatever the block is like.  Of dl it reads
+// prm, if_nsamples and pause.  Arguments and result are values: devloop_post calls it on the epoch's new state while the old one is
+// still in `st`, which keeps the device loops' instruction stream what it was when these statements stood there.
+struct DevLoopCut {
+  double step;  // code chips per sample
+  int n;        // samples
+  int status;
+};
+
+// (int)ceil(x).  Host C++ leaves the conversion of a NaN or of a value beyond int undefined - a diverged code NCO gets here -
+// where the device's instruction saturates: the host saturates by hand, the device loops keep the instruction they had.
+__host__ __device__ inline int ceil_to_int(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (int)ceil(x);
+#else
+  return (x >= -2147483648.0 && x < 2147483647.0) ? (int)ceil(x) : 2147483647;
+#endif
+}
+
+__host__ __device__ inline DevLoopCut devloop_cut(const DevLoopArgs* __restrict__ dl, long long pos, double rem_code, double code_freq, double carr_freq,
+                                                  int epochs_done = 0, int epoch_budget = 1) {
+  const gc_track_params& p = dl->prm;
+  const double step = code_freq / p.sampling_freq;
+  const int n = ceil_to_int((p.code_length - rem_code) / step);
+  int status = 0;
+  if (epochs_done >= epoch_budget)
+    status = 1;
+  else if (!(step > 0.0) || !(step < 1e6) || !(carr_freq == carr_freq))
+    status = 4;
+  else if (pos < 0 || (unsigned long long)(pos + n) > dl->if_nsamples)
+    status = dl->pause ? 5 : 2;  // paused: the state is the one the next window's call starts from
+  return DevLoopCut{step, n, status};
+}
+
+// The cut block's geometry into the descriptor; channel, correlator spacing and table offsets of b stay as they are.
+__host__ __device__ inline void devloop_put(gc_block& b, const DevLoopCut& c, long long pos, double rem_code, double carr_freq, double rem_carr) {
+  b.blksize = c.n;
+  b.first_sample = pos;
+  b.rem_code_phase = rem_code;
+  b.code_phase_step = c.step;
+  b.carr_freq = carr_freq;
+  b.rem_carr_phase = rem_carr;
+}
+
+// A channel's first block of a call, cut from the state devloop_state_in left, as devloop_post cuts every later one.
+inline void devloop_first(const DevLoopArgs* dl, DevLoopChan& s) {
+  const DevLoopCut c = devloop_cut(dl, s.pos, s.rem_code, s.code_freq, s.carr_freq);
+  if (dl->prm.table_phase_count > 0 && s.table_phase > 0) s.blk.table_offset[1] = (int)dl->prm.code_length * (s.table_phase - 1);  // GPS_L2C tracking.m:261
+  devloop_put(s.blk, c, s.pos, s.rem_code, s.carr_freq, s.rem_carr);
+  s.status = c.status;
+}
+
+// One channel, one epoch: lane-uniform float64 restatement of tracking.m:273-348, every pilot handling mode included, in two
+// parts, so that the closer of the fast kernel can run the first one while the other members' partial sums are still on their way:
 //   devloop_pre   what depends only on the epoch's own geometry and NCO state: the remainders the next block starts from
 //                 (tracking.m:273-283: one fmod, one division);
 //   devloop_post  what needs the sums: discriminators, loop filters, records, the next block (tracking.m:302-335, 219-222).
-// `st` is the caller's copy of the loop state (the fast kernel keeps it in registers across epochs), `gch` the channel's slot
-// in device memory, kept up to date for the host by lane 0.  `sums`: 6 per arm; R: the channel's index scale.  On return b
-// holds the next epoch's block geometry; the return value is the channel status (0 = keep going).
+// `st` is the caller's copy of the loop state (the fast kernel keeps it in registers across epochs; the host loop's own).
+// `sums`: 6 per arm; R: the channel's index scale.  On return b holds the next epoch's block geometry; the return value is the
+// channel status (0 = keep going).
 struct DevLoopPre {
   double rem_code_new, rem_carr_new;
 };
 
-__device__ inline DevLoopPre devloop_pre(const DevLoopArgs* __restrict__ dl, const DevLoopChan& st, const gc_block& b, double R) {
+__host__ __device__ inline DevLoopPre devloop_pre(const DevLoopArgs* __restrict__ dl, const DevLoopChan& st, const gc_block& b, double R) {
   const gc_track_params& p = dl->prm;
   const double kPi = 3.141592653589793;
   const int n = b.blksize;
@@ -126,7 +238,7 @@ __device__ inline DevLoopPre devloop_pre(const DevLoopArgs* __restrict__ dl, con
 }
 
 template <int MAXARMS, class Rec>
-__device__ inline int devloop_post(const DevLoopArgs* __restrict__ dl, DevLoopChan& st, gc_block& b, int e, const double (&sums)[6 * MAXARMS],
+__host__ __device__ inline int devloop_post(const DevLoopArgs* __restrict__ dl, DevLoopChan& st, gc_block& b, int e, const double (&sums)[6 * MAXARMS],
                                    int arms, double R, const DevLoopPre& pre, Rec&& rec, bool do_cno = true, long long cno_slot = -1) {
   // rec(field, value) takes the epoch's record: straight to device memory (lane kernel) or into registers, to be stored by
   // devloop_commit AFTER the next descriptor is on its way (fast kernel)
@@ -154,16 +266,7 @@ __device__ inline int devloop_post(const DevLoopArgs* __restrict__ dl, DevLoopCh
     st.cno_ready = 0;
     if (kk == K - 1 && K > 1) {
       const double m = st.cno_s1 / K, zm = st.cno_z0 + m, zv = (st.cno_s2 - st.cno_s1 * m) / (K - 1);
-      const double d = zm * zm - zv;
-      double ratio;  // |Pav / (2*Nv)|
-      if (d >= 0.0) {
-        const double pav = sqrt(d);
-        ratio = fabs(pav / (zm - pav));
-      } else {  // Pav imaginary: |i*s / (Zm - i*s)|
-        const double s2 = -d;
-        ratio = sqrt(s2 / (zm * zm + s2));
-      }
-      st.cno_value = 10.0 * log10(ratio / p.cno_acc_time);
+      st.cno_value = 10.0 * log10(cno_ratio(zm, zv) / p.cno_acc_time);
       st.cno_n = (e + 1) / K;
       st.cno_ready = 1;
       if (cno_slot >= 0 && st.cno_n >= 1 && st.cno_n <= dl->cno_nk) {
@@ -266,15 +369,8 @@ __device__ inline int devloop_post(const DevLoopArgs* __restrict__ dl, DevLoopCh
   rec(GC_TRK_Q_L, q_l);
   // next block geometry (:219-222) or the end
   const long long pos_new = st.pos + n;
-  const double step_new = code_freq_new / p.sampling_freq;
-  const int n_new = (int)ceil((p.code_length - rem_code_new) / step_new);
-  int status = 0;
-  if (e + 1 >= st.epoch_budget)
-    status = 1;
-  else if (!(step_new > 0.0) || !(step_new < 1e6) || !(carr_freq_new == carr_freq_new))
-    status = 4;  // non-finite or non-positive code step (all-zero sums give atan(0/0) = NaN): no block can be cut from it
-  else if (pos_new < 0 || (unsigned long long)(pos_new + n_new) > dl->if_nsamples)
-    status = dl->pause ? 5 : 2;  // paused: the state below is the one the next window's call starts from
+  const DevLoopCut cut = devloop_cut(dl, pos_new, rem_code_new, code_freq_new, carr_freq_new, e + 1, st.epoch_budget);
+  const int status = cut.status;
   st.pos = pos_new;
   st.rem_code = rem_code_new;
   st.rem_carr = rem_carr_new;
@@ -295,13 +391,32 @@ __device__ inline int devloop_post(const DevLoopArgs* __restrict__ dl, DevLoopCh
     }
     b.table_offset[1] = (int)p.code_length * (st.table_phase - 1);
   }
-  b.blksize = n_new;
-  b.first_sample = pos_new;
-  b.rem_code_phase = rem_code_new;
-  b.code_phase_step = step_new;
-  b.carr_freq = carr_freq_new;
-  b.rem_carr_phase = rem_carr_new;
+  devloop_put(b, cut, pos_new, rem_code_new, carr_freq_new, rem_carr_new);
   return status;
+}
+
+// ---- device only: the teams' messages and the closer's stores -------------------------------------------------------
+#if defined(__HIPCC__)
+// Message scope (g_msg_scope, set per launch from DevLoopArgs::reserved): 0 = system (sc0 sc1: past every cache),
+// 1 = workgroup (sc0: past the CU's L1 only — the team's L2 is the meeting point; valid when the whole team runs on ONE
+// XCD, which the launch arranges and the kernel verifies through HW_REG_XCC_ID before switching to it), 2 = agent (sc1).
+__device__ __forceinline__ msg_t msg_load(const msg_t* p, int scope = 0) {
+  msg_t v;
+  if (scope == 1)
+    asm volatile("global_load_dwordx4 %0, %1, off sc0\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
+  else if (scope == 2)
+    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
+  else
+    asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+__device__ __forceinline__ void msg_store(msg_t* p, msg_t v, int scope = 0) {
+  if (scope == 1)
+    asm volatile("global_store_dwordx4 %0, %1, off sc0" : : "v"(p), "v"(v) : "memory");
+  else if (scope == 2)
+    asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
+  else
+    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
 }
 
 // The epoch's record and the loop state to device memory (lane 0), off the critical path.
@@ -338,17 +453,6 @@ __device__ inline void devloop_commit(const DevLoopArgs* __restrict__ dl, DevLoo
   if (dl->cno && st.cno_ready && st.cno_n >= 1 && st.cno_n <= dl->cno_nk) dl->cno[slot * dl->cno_nk + st.cno_n - 1] = st.cno_value;
 }
 
-// All parts back to back on the state held in device memory (lane kernel's closer): state read and written in place, records
-// stored as they are formed.
-template <int MAXARMS>
-__device__ inline int devloop_close(const DevLoopArgs* __restrict__ dl, DevLoopChan* ch, gc_block& b, long long slot, int e,
-                                    const double (&sums)[6 * MAXARMS], int arms, double R, int lane) {
-  double* o = dl->records + (size_t)slot * GC_TRK_NFIELDS * dl->n_epochs;
-  const DevLoopPre pre = devloop_pre(dl, *ch, b, R);
-  return devloop_post<MAXARMS>(dl, *ch, b, e, sums, arms, R, pre, [&](int f, double v) {
-    if (lane == 0) o[(size_t)f * dl->n_epochs + e] = v;
-  });
-}
 #endif
 
 }  // namespace gcorr

@@ -243,7 +243,7 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
 int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, double* out,
                            int32_t* epochs_done, GcTrackResume* r, const int32_t* budget, bool whole_call);
 
-// trackResults.CNo.VSMValue of finished records on the host (the host-closed loops; the device loop has its own copy in devloop.h)
+// trackResults.CNo.VSMValue of finished records on the host (the host-closed loops; the device loop estimates in one pass inside devloop_post - both end in gcorr::cno_ratio, devloop.h)
 void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const double* out, const int32_t* epochs_done);
 
 int gc_bytes_per_sample(int dtype, int layout);

@@ -17,28 +17,6 @@
 
 namespace {
 
-struct ChanState {
-  bool active = false;
-  int64_t pos = 0;
-  double code_freq = 0, code_freq_basis = 0, rem_code = 0;
-  double carr_freq = 0, carr_basis = 0, rem_carr = 0;
-  double old_code_nco = 0, old_code_err = 0;
-  double old_carr_nco = 0, old_carr_err = 0;  // 2nd-order PLL
-  double d2_carr_err = 0, d_carr_err = 0;      // 3-state PLL
-  int epochs = 0;
-  bool aborted = false;
-  int table_phase = 0;  // GPS L2C CLCodePhase
-};
-
-// Common/calcLoopCoef.m:41-45
-void calc_loop_coef(double lbw, double zeta, double k, double* tau1, double* tau2) {
-  const double wn = lbw * 8 * zeta / (4 * zeta * zeta + 1);
-  *tau1 = k / (wn * wn);
-  *tau2 = 2.0 * zeta / wn;
-}
-
-const double kPi = 3.141592653589793;  // MATLAB pi
-
 // What gc_correlate checks per descriptor (validate_blocks, gnsscorr.hip), for the blocks a tracking loop will cut from one
 // channel: every ramp stays inside the reference's [c(end) c c(1)] padding (tracking.m:158,252-270) for ANY code step, because
 // (blksize-1)*step + rem < codeLength by construction of blksize (:222): the largest index is ceil((codeLength + spacing)*R*M).
@@ -75,6 +53,41 @@ int validate_track_channel(const gc_context* ctx, const gc_track_params* p, cons
                    in.channel, a, top, avail, p->code_length);
       return GC_E_INVALID;
     }
+  }
+  return GC_OK;
+}
+
+// What gc_track and gc_track_device check before anything runs (`who` names the entry point in the error texts): the arguments, the
+// IF buffer, every channel configured and fit for the blocks its loop will cut.  Sets the launch scope up on the way.
+// per_channel(channel, index): the entry point's own checks of a configured channel, made before validate_track_channel.
+template <class F>
+int track_preamble(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, const double* out, const int32_t* epochs_done,
+                   GcTrackResume* r, const char* who, int* max_arms, F&& per_channel) {
+  if (r) r->paused = false;
+  if (!ctx || !p || nch <= 0 || nch > GC_MAX_CHANNELS || !init || !out || !epochs_done || p->n_epochs <= 0 || (r && !r->state)) {
+    gc_set_error("%s: bad arguments", who);
+    return GC_E_INVALID;
+  }
+  if (!ctx->d_if) {
+    gc_set_error("%s: no IF buffer loaded", who);
+    return GC_E_STATE;
+  }
+  GC_HIP(hipSetDevice(ctx->device));
+  ctx->fs = p->sampling_freq;
+  int rc = gc_sync_channels(ctx);
+  if (rc) return rc;
+  gc_scope_reset(ctx);
+  *max_arms = 1;
+  for (int c = 0; c < nch; ++c) {
+    const int ci = init[c].channel;
+    if (ci < 0 || ci >= GC_MAX_CHANNELS || !ctx->ch[ci].configured) {
+      gc_set_error("%s: channel %d not configured", who, ci);
+      return GC_E_STATE;
+    }
+    if ((rc = per_channel(ctx->ch[ci], ci))) return rc;
+    if ((rc = validate_track_channel(ctx, p, init[c], who))) return rc;
+    *max_arms = std::max(*max_arms, ctx->ch[ci].arms);
+    gc_scope_add(ctx, ci);
   }
   return GC_OK;
 }
@@ -117,15 +130,7 @@ static void fill_cno_pld(gc_context* ctx, const gc_track_params* p, int nch, con
       sq += Q[e];
     }
     zv /= (K - 1);
-    const double d = zm * zm - zv;
-    double ratio;  // |Pav / (2*Nv)|, Nv = (Zm - Pav)/2
-    if (d >= 0.0) {
-      const double pav = std::sqrt(d);
-      ratio = std::fabs(pav / (zm - pav));
-    } else {
-      ratio = std::sqrt(-d / (zm * zm - d));
-    }
-    lin = ratio / T;
+    lin = gcorr::cno_ratio(zm, zv) / T;
     pld = (wiped * wiped - sq * sq) / (wiped * wiped + sq * sq);
   };
   for (int c = 0; c < nch; ++c) {
@@ -183,15 +188,7 @@ void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const 
           zv += dz * dz;
         }
         zv /= (K - 1);
-        const double d = zm * zm - zv;
-        double ratio;
-        if (d >= 0.0) {
-          const double pav = std::sqrt(d);
-          ratio = std::fabs(pav / (zm - pav));
-        } else {
-          ratio = std::sqrt(-d / (zm * zm - d));
-        }
-        v = 10.0 * std::log10(ratio / p->cno_acc_time);
+        v = 10.0 * std::log10(gcorr::cno_ratio(zm, zv) / p->cno_acc_time);
       }
       ctx->cno_out[(size_t)c * nk + k] = v;
     }
@@ -204,46 +201,25 @@ void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const 
 // this window - more of the record follows - instead of ending that channel (tracking.m:241-245 is the END of the file).
 int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, double* out,
                     int32_t* epochs_done, GcTrackResume* r) {
-  if (r) r->paused = false;
-  if (!ctx || !p || nch <= 0 || nch > GC_MAX_CHANNELS || !init || !out || !epochs_done || p->n_epochs <= 0 || (r && !r->state)) {
-    gc_set_error("gc_track: bad arguments");
-    return GC_E_INVALID;
-  }
-  if (!ctx->d_if) {
-    gc_set_error("gc_track: no IF buffer loaded");
-    return GC_E_STATE;
-  }
-  GC_HIP(hipSetDevice(ctx->device));
-  ctx->fs = p->sampling_freq;
-  // channels that share the device during this call (gc_track_multi): teams are sized for all of them
-  const int nch_dev = ctx->concurrent_jobs ? std::max(nch, ctx->concurrent_channels) : nch;
-  int rc = gc_sync_channels(ctx);
-  if (rc) return rc;
-
   int max_arms = 1;
   bool any_mixed = false, all_mixed_derived = true, any_three_plain = false;
-  gc_scope_reset(ctx);
-  for (int c = 0; c < nch; ++c) {
-    const int ci = init[c].channel;
-    if (ci < 0 || ci >= GC_MAX_CHANNELS || !ctx->ch[ci].configured) {
-      gc_set_error("gc_track: channel %d not configured", ci);
-      return GC_E_STATE;
-    }
-    for (int a = 0; a < ctx->ch[ci].arms; ++a)
-      if (!ctx->ch[ci].d_tab[a]) {
+  int rc = track_preamble(ctx, p, nch, init, out, epochs_done, r, "gc_track", &max_arms, [&](const HostChannel& hcn, int ci) -> int {
+    for (int a = 0; a < hcn.arms; ++a)
+      if (!hcn.d_tab[a]) {
         gc_set_error("gc_track: channel %d arm %d has no code table", ci, a);
         return GC_E_STATE;
       }
-    if ((rc = validate_track_channel(ctx, p, init[c], "gc_track"))) return rc;
-    max_arms = std::max(max_arms, ctx->ch[ci].arms);
-    if (ctx->ch[ci].arms == 3 && !gc_channel_is_derived(ctx->ch[ci])) any_three_plain = true;
-    gc_scope_add(ctx, ci);
-    for (int a = 1; a < ctx->ch[ci].arms; ++a)
-      if (ctx->ch[ci].mult[a] != ctx->ch[ci].mult[0]) {  // B1C wide-band / E1 CBOC: exact per-sample kernel, or the lane
-        any_mixed = true;                                  // kernel's derived-arm instantiation when every such channel allows it
-        if (!gc_channel_is_derived(ctx->ch[ci])) all_mixed_derived = false;
+    if (hcn.arms == 3 && !gc_channel_is_derived(hcn)) any_three_plain = true;
+    for (int a = 1; a < hcn.arms; ++a)
+      if (hcn.mult[a] != hcn.mult[0]) {  // B1C wide-band / E1 CBOC: exact per-sample kernel, or the lane
+        any_mixed = true;                // kernel's derived-arm instantiation when every such channel allows it
+        if (!gc_channel_is_derived(hcn)) all_mixed_derived = false;
       }
-  }
+    return GC_OK;
+  });
+  if (rc) return rc;
+  // channels that share the device during this call (gc_track_multi): teams are sized for all of them
+  const int nch_dev = ctx->concurrent_jobs ? std::max(nch, ctx->concurrent_channels) : nch;
   if ((p->pilot_combine == 4 || p->pilot_combine == 5) && max_arms < 3) {
     gc_set_error("gc_track: pilot_combine 4 / 5 need three arms {data, pilot BOC(1,1), pilot BOC(6,1)}");
     return GC_E_INVALID;
@@ -477,201 +453,47 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
     break;
   }
 
-  double tau1code, tau2code, tau1carr, tau2carr;
-  calc_loop_coef(p->dll_noise_bw, p->dll_damping, 1.0, &tau1code, &tau2code);   // tracking.m:100-102
-  calc_loop_coef(p->pll_noise_bw, p->pll_damping, 0.25, &tau1carr, &tau2carr);  // tracking.m:109-110
-  const double pdi = p->int_time;
-
-  std::vector<ChanState> st((size_t)nch);
-  for (int c = 0; c < nch; ++c) {
-    ChanState& s = st[c];
-    s.active = true;
-    // tracking.m:150-152; positions count from the IF buffer's first sample, which is record sample r->origin (gc_track_resume on a
-    // window: a run that starts in a window other than the record's first one must not read from that window's start)
-    s.pos = p->skip_samples + init[c].code_phase - 1 - (r ? r->origin : 0);
-    s.table_phase = init[c].table_phase;
-    s.code_freq = s.code_freq_basis = init[c].code_freq;  // :163 / GPS_L5C :165
-    s.carr_freq = s.carr_basis = init[c].acquired_freq;   // :167-168
-    if (r && r->resume) {  // continue where the previous window stopped
-      const gc_channel_state& g = r->state[c];
-      s.active = g.status == 0;
-      s.aborted = g.status == 2;
-      s.pos = g.next_sample - r->origin;
-      s.code_freq = g.code_freq;
-      s.rem_code = g.rem_code_phase;
-      s.carr_freq = g.carr_freq;
-      s.rem_carr = g.rem_carr_phase;
-      s.old_code_nco = g.old_code_nco;
-      s.old_code_err = g.old_code_error;
-      s.old_carr_nco = g.old_carr_nco;
-      s.old_carr_err = g.old_carr_error;
-      s.d_carr_err = g.d_carr_error;
-      s.d2_carr_err = g.d2_carr_error;
-      s.table_phase = g.table_phase;
-    }
-  }
+  // The loop is closed by devloop.h's routine, the one the device loops run: its inputs go into `pa` (a persistent kernel took its
+  // copy above), its state is one DevLoopChan per channel.  Positions count from the IF buffer's first sample, which is record
+  // sample r->origin (gc_track_resume on a window: a run that starts in a window other than the record's first one must not read
+  // from that window's start).
   const int64_t origin = r ? r->origin : 0;
+  gcorr::devloop_set_loop(pa, *p, ctx->if_nsamples, origin, r && r->pause_at_end);
+  std::vector<gcorr::DevLoopChan> st((size_t)nch);
+  std::memset(st.data(), 0, sizeof(gcorr::DevLoopChan) * (size_t)nch);
+  // A channel whose cutter found no block (2 the record holds no whole block any more, 4 its NCO left the finite numbers; MATLAB
+  // then fails in fread(fid, NaN)) ends there; its team of a persistent kernel is told to stop instead of waiting for epoch e.
+  auto tell_team = [&](int c, int e) {
+    if (persist && (st[c].status == 2 || st[c].status == 4)) write_desc(c, e, nullptr, 2ull);
+  };
+  for (int c = 0; c < nch; ++c) {
+    gcorr::DevLoopChan& s = st[c];
+    gcorr::devloop_state_in(s, *p, init[c], (r && r->resume) ? &r->state[c] : nullptr, origin);
+    s.epoch_budget = n_epochs;
+    if (s.status != 0) continue;  // ended in an earlier window
+    gcorr::devloop_first(&pa, s);
+    tell_team(c, 0);
+  }
 
   std::vector<int> slot((size_t)nch);
-  std::atomic<bool> any_range{false}, any_diverged{false};  // set by whichever host thread serves the channel
   double t_launch = 0.0, t_wait = 0.0;  // GC_TRACK_TIMING: host time in the launch call / until the records arrived
   const auto t_loop0 = std::chrono::steady_clock::now();
 
-  // tracking.m:219-245 for channel c at epoch e: block size and position -> descriptor.  false: the channel ends here (its NCO
-  // left the finite numbers, or the record holds no whole block any more); a persistent team is told to stop.
-  auto prepare = [&](int c, int e, gc_block& b) -> bool {
-    ChanState& s = st[c];
-    const double step = s.code_freq / p->sampling_freq;                      // :219
-    if (!(step > 0.0) || !(step < 1e6) || !std::isfinite(s.carr_freq)) {
-      // all-zero sums make atan(0/0) = NaN of the carrier and code NCOs; MATLAB then fails in fread(fid, NaN): stop the channel
-      s.active = false;
-      s.aborted = true;
-      any_diverged = true;
-      if (persist) write_desc(c, e, nullptr, 2ull);
-      return false;
-    }
-    const int n = (int)std::ceil((p->code_length - s.rem_code) / step);     // :222
-    if (s.pos < 0 || (uint64_t)(s.pos + n) > ctx->if_nsamples) {            // :241-245
-      s.active = false;
-      s.aborted = true;
-      any_range = true;
-      if (persist) write_desc(c, e, nullptr, 2ull);  // this channel's team stops
-      return false;
-    }
-    std::memset(&b, 0, sizeof b);
-    b.channel = init[c].channel;
-    b.blksize = n;
-    b.first_sample = s.pos;
-    b.rem_code_phase = s.rem_code;
-    if (p->table_phase_count > 0 && s.table_phase > 0)  // GPS_L2C tracking.m:261: index + codeLength*(CLCodePhase-1)
-      b.table_offset[1] = (int32_t)p->code_length * (s.table_phase - 1);
-    b.code_phase_step = step;
-    b.el_spacing = p->el_spacing;
-    b.carr_freq = s.carr_freq;
-    b.rem_carr_phase = s.rem_carr;
-    return true;
-  };
-  // tracking.m:249-348 for channel c at epoch e: the recorded state, the discriminators and loop filters, the next block's state
-  auto close_epoch = [&](int c, int e, const gc_block& b, const double (&sums)[GC_OUT_STRIDE]) {
-      ChanState& s = st[c];
-      const double R = ctx->ch[b.channel].index_scale;
-      const double i_e = sums[0], q_e = sums[1], i_p = sums[2], q_p = sums[3], i_l = sums[4], q_l = sums[5];
-      double* o = out + (size_t)c * GC_TRK_NFIELDS * n_epochs;
-      auto rec = [&](int f, double v) { o[(size_t)f * n_epochs + e] = v; };
-      rec(GC_TRK_ABSOLUTE_SAMPLE, (double)(s.pos + origin));  // :212-216
-      rec(GC_TRK_REM_CODE_PHASE, s.rem_code);      // :249
-      rec(GC_TRK_REM_CARR_PHASE, s.rem_carr);      // :277
-      const int n = b.blksize;
-      const double step = b.code_phase_step;
-      // remCodePhase update, :273 (R = 1) / GAL_E1C tracking.m:268 (R = 2).  tcode(blksize) is the
-      // colon end point ((blksize-1)*codePhaseStep + remCodePhase) * R.
-      const double t_last = ((n - 1) * step + s.rem_code) * R;
-      const double rem_code_new = (R != 1.0) ? (t_last / R + step) - p->code_length : (t_last + step) - p->code_length;
-      // remCarrPhase update, :280-283
-      const double time_n = (double)n / p->sampling_freq;
-      const double trig_n = ((s.carr_freq * 2.0 * kPi) * time_n) + s.rem_carr;
-      const double rem_carr_new = std::fmod(trig_n, 2 * kPi);
-      s.pos += n;
-      s.rem_code = rem_code_new;
-      s.rem_carr = rem_carr_new;
-
-      // ---- PLL discriminator (:305) and pilot combining ---------------------------------
-      double carr_err = std::atan(q_p / i_p) / (2.0 * kPi);
-      double code_err = (std::sqrt(i_e * i_e + q_e * q_e) - std::sqrt(i_l * i_l + q_l * q_l)) /
-                        (std::sqrt(i_e * i_e + q_e * q_e) + std::sqrt(i_l * i_l + q_l * q_l));  // :322-323
-      double pilot6[6] = {sums[6], sums[7], sums[8], sums[9], sums[10], sums[11]};  // arm 1 as correlated
-      if (p->pilot_combine != 0) {
-        if (p->pilot_combine == 4) {
-          // BDS B1C wide-band: arms {data, pilot BOC(1,1), pilot BOC(6,1)} -> one pilot (WB_tracking.m:364-369)
-          const double a61 = -std::sqrt(4.0 / 33.0), a11 = std::sqrt(29.0 / 33.0);
-          for (int x = 0; x < 3; ++x) {
-            const double i11 = sums[6 + 2 * x], q11 = sums[7 + 2 * x], i61 = sums[12 + 2 * x], q61 = sums[13 + 2 * x];
-            pilot6[2 * x] = a61 * i61 + a11 * q11;
-            pilot6[2 * x + 1] = a61 * q61 - a11 * i11;
-          }
-        } else if (p->pilot_combine == 5) {
-          // Galileo E1-C CBOC(6,1,1/11): pilot subcarrier sqrt(10/11) sc_BOC(1,1) - sqrt(1/11) sc_BOC(6,1), both in phase
-          // (Galileo OS SIS ICD 2.3.3; BASELINE config 3 - the reference itself tracks E1 with BOC(1,1) only)
-          const double a11 = std::sqrt(10.0 / 11.0), a61 = -std::sqrt(1.0 / 11.0);
-          for (int x = 0; x < 3; ++x) {
-            const double i11 = sums[6 + 2 * x], q11 = sums[7 + 2 * x], i61 = sums[12 + 2 * x], q61 = sums[13 + 2 * x];
-            pilot6[2 * x] = a11 * i11 + a61 * i61;
-            pilot6[2 * x + 1] = a11 * q11 + a61 * q61;
-          }
-        }
-        const double pi_e = pilot6[0], pq_e = pilot6[1], pi_p = pilot6[2], pq_p = pilot6[3], pi_l = pilot6[4], pq_l = pilot6[5];
-        double carr_err_q;
-        if (p->pilot_combine == 1) {
-          // QI = (I_PQ + 1i*Q_PQ) * exp(-1i*pi/2), GPS_L5C tracking.m:340
-          const double cr = std::cos(kPi / 2), ci = -std::sin(kPi / 2);
-          const double re = pi_p * cr - pq_p * ci;
-          const double im = pi_p * ci + pq_p * cr;
-          carr_err_q = std::atan(im / re) / (2.0 * kPi);
-        } else if (p->pilot_combine == 3) {
-          carr_err_q = std::atan(-pi_p / pq_p) / (2.0 * kPi);  // BDS/B1C NB_tracking.m:341
-        } else {
-          carr_err_q = std::atan(pq_p / pi_p) / (2.0 * kPi);  // GAL_E1C tracking.m:309; WB_tracking.m:381
-        }
-        double code_err_q = (std::sqrt(pi_e * pi_e + pq_e * pq_e) - std::sqrt(pi_l * pi_l + pq_l * pq_l)) /
-                            (std::sqrt(pi_e * pi_e + pq_e * pq_e) + std::sqrt(pi_l * pi_l + pq_l * pq_l));
-        const bool pll_w = p->pll_weight[0] != 0.0 || p->pll_weight[1] != 0.0;
-        const bool dll_w = p->dll_weight[0] != 0.0 || p->dll_weight[1] != 0.0;
-        if (p->dll_scale != 0.0) {  // NB_tracking.m:346-348
-          code_err = code_err * p->dll_scale;
-          code_err_q = code_err_q * p->dll_scale;
-        }
-        if (pll_w)  // (carrError*11 + p11_carrError*29)/40, NB_tracking.m:342; (carrError*1 + p_carrError*3)/4, WB :382
-          carr_err = (carr_err * p->pll_weight[0] + carr_err_q * p->pll_weight[1]) / (p->pll_weight[0] + p->pll_weight[1]);
-        else
-          carr_err = (carr_err + carr_err_q) / 2;
-        if (dll_w && p->pilot_combine == 4)  // codeError*factor + p_codeError*(1-factor), WB_tracking.m:403
-          code_err = code_err * p->dll_weight[0] + code_err_q * p->dll_weight[1];
-        else if (dll_w)  // (codeError*11 + p11_codeError*29)/40, NB_tracking.m:349
-          code_err = (code_err * p->dll_weight[0] + code_err_q * p->dll_weight[1]) / (p->dll_weight[0] + p->dll_weight[1]);
-        else
-          code_err = (code_err + code_err_q) / 2;
-      }
-      double carr_nco;
-      if (p->pll_kind == GC_PLL_2ND_ORDER) {
-        carr_nco = s.old_carr_nco + (tau2carr / tau1carr) * (carr_err - s.old_carr_err) + carr_err * (pdi / tau1carr);  // :308-309
-        s.old_carr_nco = carr_nco;
-        s.old_carr_err = carr_err;
-      } else {
-        s.d2_carr_err = s.d2_carr_err + carr_err * p->pf3;  // GPS_L5C tracking.m:351-353
-        s.d_carr_err = s.d2_carr_err + carr_err * p->pf2 + s.d_carr_err;
-        carr_nco = s.d_carr_err + carr_err * p->pf1;
-      }
-      rec(GC_TRK_CARR_FREQ, s.carr_freq);  // :314
-      s.carr_freq = s.carr_basis + carr_nco;  // :317
-      // ---- DLL (:326-335) -----------------------------------------------------------------
-      const double code_nco = s.old_code_nco + (tau2code / tau1code) * (code_err - s.old_code_err) + code_err * (pdi / tau1code);
-      s.old_code_nco = code_nco;
-      s.old_code_err = code_err;
-      rec(GC_TRK_CODE_FREQ, s.code_freq);  // :332
-      s.code_freq = s.code_freq_basis - code_nco;  // :335
-      rec(GC_TRK_DLL_DISCR, code_err);
-      rec(GC_TRK_DLL_DISCR_FILT, code_nco);
-      rec(GC_TRK_PLL_DISCR, carr_err);
-      rec(GC_TRK_PLL_DISCR_FILT, carr_nco);
-      rec(GC_TRK_I_E, i_e);
-      rec(GC_TRK_Q_E, q_e);
-      rec(GC_TRK_I_P, i_p);
-      rec(GC_TRK_Q_P, q_p);
-      rec(GC_TRK_I_L, i_l);
-      rec(GC_TRK_Q_L, q_l);
-      if (ctx->ch[b.channel].arms >= 2) {
-        rec(GC_TRK_PILOT_I_E, pilot6[0]);
-        rec(GC_TRK_PILOT_Q_E, pilot6[1]);
-        rec(GC_TRK_PILOT_I_P, pilot6[2]);
-        rec(GC_TRK_PILOT_Q_P, pilot6[3]);
-        rec(GC_TRK_PILOT_I_L, pilot6[4]);
-        rec(GC_TRK_PILOT_Q_L, pilot6[5]);
-      }
-      if (p->table_phase_count > 0 && s.table_phase > 0 && p->pilot_combine != 0) {  // GPS_L2C tracking.m:357-360
-        s.table_phase += 1;
-        if (s.table_phase >= p->table_phase_count + 1) s.table_phase = 1;
-      }
-      s.epochs = e + 1;
+  // tracking.m:249-348 for channel c at epoch e: the records, the discriminators and loop filters, the next block in st[c].blk.
+  // Returns the channel's status: 0 = st[c].blk is the block of epoch e + 1.
+  auto advance = [&](int c, int e, const double (&sums)[GC_OUT_STRIDE]) -> int {
+    gcorr::DevLoopChan& s = st[c];
+    const HostChannel& hcn = ctx->ch[s.blk.channel];
+    double* o = out + (size_t)c * GC_TRK_NFIELDS * n_epochs;
+    // Arms: the device loops combine the pilot of a channel only when that channel HAS the arms the mode needs (gc_track_device tracks a
+    // one-arm channel next to two-arm ones as data-only); this loop has always combined whenever pilot_combine is set - sums of arms
+    // a channel lacks are zero, its discriminators NaN, the call ends with GC_E_INVALID.  Passing the arm count the mode needs keeps that (devloop_post then also records the
+    // six Pilot_* fields of that one epoch: zeros, which is what the zero-filled `out` held there).
+    const int arms = p->pilot_combine >= 4 ? 3 : p->pilot_combine != 0 ? std::max(hcn.arms, 2) : hcn.arms;
+    const gcorr::DevLoopPre pre = gcorr::devloop_pre(&pa, s, s.blk, hcn.index_scale);
+    gcorr::devloop_post<GC_MAX_ARMS>(&pa, s, s.blk, e, sums, arms, hcn.index_scale, pre, [&](int f, double v) { o[(size_t)f * n_epochs + e] = v; });
+    tell_team(c, e + 1);
+    return s.status;
   };
 
   // ---- persistent kernel, every channel at its own pace ---------------------------------------------------------------
@@ -684,8 +506,7 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
   const bool async = persist && poll && !(r && r->pause_at_end) && GC_TUNE_ENV("GC_TRACK_LOCKSTEP") == nullptr;
   if (async) {
     const int arms6 = max_arms * 6;
-    struct alignas(64) Slot {  // a channel's loop state on cache lines of its own: neighbouring channels may belong to other threads
-      gc_block cur;
+    struct alignas(64) Slot {  // a channel's turn on a cache line of its own: neighbouring channels may belong to other threads
       int ep = 0;
       bool waiting = false;
       std::chrono::steady_clock::time_point sent;
@@ -707,9 +528,8 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
       int outstanding = 0;
       const auto now0 = std::chrono::steady_clock::now();
       for (int c = c0; c < c1; ++c) {
-        if (!st[c].active) continue;
-        if (!prepare(c, 0, sl[c].cur)) continue;
-        write_desc(c, 0, &sl[c].cur, 0ull);
+        if (st[c].status != 0) continue;
+        write_desc(c, 0, &st[c].blk, 0ull);
         sl[c].waiting = true;
         sl[c].sent = now0;
         ++outstanding;
@@ -732,14 +552,14 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
           std::atomic_thread_fence(std::memory_order_acquire);
           double sums[GC_OUT_STRIDE];
           for (int v = 0; v < GC_OUT_STRIDE; ++v) sums[v] = v < arms6 ? grp[v].value : 0.0;
-          close_epoch(c, sl[c].ep, sl[c].cur, sums);
+          const int status = advance(c, sl[c].ep, sums);
           progress = true;
           ++sl[c].ep;
-          if (sl[c].ep < n_epochs && prepare(c, sl[c].ep, sl[c].cur)) {
-            write_desc(c, sl[c].ep, &sl[c].cur, 0ull);
+          if (status == 0) {
+            write_desc(c, sl[c].ep, &st[c].blk, 0ull);
             sl[c].sent = stamp;
           } else {
-            sl[c].waiting = false;  // all epochs done (the team leaves by itself) or the channel ended (prepare told its team)
+            sl[c].waiting = false;  // all epochs done (the team leaves by itself) or the channel ended (its team has been told)
             --outstanding;
           }
         }
@@ -774,25 +594,20 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
   }
 
   for (int e = 0; e < n_epochs && !async; ++e) {
-    if (r && r->pause_at_end) {
-      bool fits = true;
-      for (int c = 0; c < nch && fits; ++c) {
-        const ChanState& s = st[c];
-        if (!s.active) continue;
-        const double step = s.code_freq / p->sampling_freq;
-        if (!(step > 0.0) || !(step < 1e6)) continue;  // handled below (diverged NCO)
-        const int n = (int)std::ceil((p->code_length - s.rem_code) / step);
-        fits = s.pos >= 0 && (uint64_t)(s.pos + n) <= ctx->if_nsamples;
-      }
-      if (!fits) {
-        r->paused = true;
+    if (r && r->pause_at_end) {  // some channel's block of this epoch lies beyond the window: all of them stop here
+      for (int c = 0; c < nch; ++c) r->paused = r->paused || st[c].status == 5;
+      if (r->paused) {
+        // a channel that diverged in the epoch before has not ended in THIS window: the next window's call finds that out again, first thing
+        // (tell_team has sent its persistent team the stop descriptor already: harmless, persist_stop follows this break)
+        for (int c = 0; c < nch; ++c)
+          if (st[c].status == 4 && st[c].epochs_done == e) st[c].status = 0;
         break;
       }
     }
     int nb = 0;
     for (int c = 0; c < nch; ++c) {
-      if (!st[c].active) continue;
-      if (!prepare(c, e, blocks[nb])) continue;
+      if (st[c].status != 0) continue;
+      blocks[nb] = st[c].blk;
       slot[nb] = c;
       ++nb;
     }
@@ -871,47 +686,31 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
                         : partial[((size_t)k * splits + sp) * GC_OUT_STRIDE + v];
         sums[v] = acc;
       }
-      close_epoch(c, e, blocks[k], sums);
+      advance(c, e, sums);
     }
   }
 
   // The reference processes channels one after the other and returns from the whole function at
   // the first short read (tracking.m:241-245): channels after the first aborted one are never run.
   int first_aborted = nch;
-  for (int c = 0; c < nch; ++c)
-    if (st[c].aborted) {
-      first_aborted = c;
-      break;
-    }
+  bool any_range = false, any_diverged = false;
+  for (int c = 0; c < nch; ++c) {
+    if ((st[c].status == 2 || st[c].status == 4) && first_aborted == nch) first_aborted = c;
+    any_diverged |= st[c].status == 4;
+    // a channel that came in ended (resumed state) is not this call's short read
+    any_range |= st[c].status == 2 && !(r && r->resume && r->state[c].status != 0);
+  }
   for (int c = 0; c < nch; ++c) {
     if (c > first_aborted) {
       double* o = out + (size_t)c * GC_TRK_NFIELDS * n_epochs;
       std::fill(o, o + (size_t)GC_TRK_NFIELDS * n_epochs, 0.0);
       epochs_done[c] = 0;
     } else {
-      epochs_done[c] = st[c].epochs;
+      epochs_done[c] = st[c].epochs_done;
     }
   }
-  if (r) {
-    for (int c = 0; c < nch; ++c) {
-      const ChanState& s = st[c];
-      gc_channel_state& g = r->state[c];
-      g.next_sample = s.pos + origin;
-      g.code_freq = s.code_freq;
-      g.rem_code_phase = s.rem_code;
-      g.carr_freq = s.carr_freq;
-      g.rem_carr_phase = s.rem_carr;
-      g.old_code_nco = s.old_code_nco;
-      g.old_code_error = s.old_code_err;
-      g.old_carr_nco = s.old_carr_nco;
-      g.old_carr_error = s.old_carr_err;
-      g.d_carr_error = s.d_carr_err;
-      g.d2_carr_error = s.d2_carr_err;
-      g.table_phase = s.table_phase;
-      g.status = s.aborted ? 2 : 0;
-      g.reserved = 0;
-    }
-  }
+  if (r)  // the loop state the next window's call starts from, in record coordinates
+    for (int c = 0; c < nch; ++c) gcorr::devloop_state_out(r->state[c], st[c], origin);
   const bool persist_was = persist;
   if (persist) {  // teams that were not told to stop leave after n_epochs by themselves; the others were stopped above
     persist_stop();
@@ -950,32 +749,19 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
 // gc_track_file_device, which assembles a call from many windows, does that once at its end.
 int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, double* out,
                            int32_t* epochs_done, GcTrackResume* r, const int32_t* budget, bool whole_call) {
-  if (r) r->paused = false;
-  if (!ctx || !p || nch <= 0 || nch > GC_MAX_CHANNELS || !init || !out || !epochs_done || p->n_epochs <= 0 || (r && (!r->state || r->origin < 0))) {
+  if (r && r->origin < 0) {
+    r->paused = false;
     gc_set_error("gc_track_device: bad arguments");
     return GC_E_INVALID;
   }
-  if (!ctx->d_if) {
-    gc_set_error("gc_track_device: no IF buffer loaded");
-    return GC_E_STATE;
-  }
-  GC_HIP(hipSetDevice(ctx->device));
-  ctx->fs = p->sampling_freq;
-  // channels that share the device during this call (gc_track_multi): teams are sized for all of them
-  const int nch_dev = ctx->concurrent_jobs ? std::max(nch, ctx->concurrent_channels) : nch;
-  int rc = gc_sync_channels(ctx);
-  if (rc) return rc;
-  gc_scope_reset(ctx);
-  const bool f64 = ctx->precision == GC_PREC_F64;  // corr_f64.hip's device loop: every configuration gc_track takes
+  const bool f64 = ctx && ctx->precision == GC_PREC_F64;  // corr_f64.hip's device loop: every configuration gc_track takes
   int max_arms = 1;
   bool single_r1 = true, all_derived = true;
-  for (int c = 0; c < nch; ++c) {
-    const int ci = init[c].channel;
-    if (ci < 0 || ci >= GC_MAX_CHANNELS || !ctx->ch[ci].configured || !ctx->ch[ci].d_tab[0]) {
+  int rc = track_preamble(ctx, p, nch, init, out, epochs_done, r, "gc_track_device", &max_arms, [&](const HostChannel& hcn, int ci) -> int {
+    if (!hcn.d_tab[0]) {
       gc_set_error("gc_track_device: channel %d not configured", ci);
       return GC_E_STATE;
     }
-    const HostChannel& hcn = ctx->ch[ci];
     const bool hder = gc_channel_is_derived(hcn);  // three arms, the third derived from the second inside the lane kernel
     all_derived = all_derived && hder;
     for (int a = 0; a < hcn.arms; ++a)
@@ -983,11 +769,12 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
         gc_set_error("gc_track_device: ramp multipliers other than a derived third arm are not covered (use gc_track)");
         return GC_E_UNSUPPORTED;
       }
-    if ((rc = validate_track_channel(ctx, p, init[c], "gc_track_device"))) return rc;
-    max_arms = std::max(max_arms, hcn.arms);
     single_r1 = single_r1 && hcn.arms == 1 && hcn.index_scale == 1.0;
-    gc_scope_add(ctx, ci);
-  }
+    return GC_OK;
+  });
+  if (rc) return rc;
+  // channels that share the device during this call (gc_track_multi): teams are sized for all of them
+  const int nch_dev = ctx->concurrent_jobs ? std::max(nch, ctx->concurrent_channels) : nch;
   // three arms, the third derived from the second: Galileo E1-C CBOC (fold 5), BDS B1C wide-band (fold 4)
   const bool cboc = max_arms == 3 && all_derived && (p->pilot_combine == 5 || p->pilot_combine == 4);
   const bool i8c = ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL;  // int8 I/Q or Q/I record
@@ -1007,13 +794,16 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
   int lowrate = 2;
   bool share = true;
   const int64_t origin = r ? r->origin : 0;
+  gcorr::DevLoopArgs ha;
+  std::memset(&ha, 0, sizeof ha);
+  gcorr::devloop_set_loop(ha, *p, ctx->if_nsamples, origin, r && r->pause_at_end);
   for (int c = 0; c < nch; ++c) {
     gcorr::DevLoopChan& s = hc[c];
-    s.pos = p->skip_samples + init[c].code_phase - 1 - origin;
-    s.code_freq = s.code_freq_basis = init[c].code_freq;
-    s.carr_freq = s.carr_basis = init[c].acquired_freq;
-    s.table_phase = init[c].table_phase;
+    gcorr::devloop_state_in(s, *p, init[c], (r && r->resume) ? &r->state[c] : nullptr, origin);
     s.epoch_budget = budget ? std::max(0, std::min(budget[c], n_epochs)) : n_epochs;
+    // the first block, cut as devloop_post cuts every later one; not even one block: tracking.m:241-245
+    if (s.status == 0) gcorr::devloop_first(&ha, s);
+    if (s.status == 0 && s.epoch_budget <= 0) s.status = 1;
     // what selects the kernel and sizes the teams - hence the order of the float additions - comes from the channel's NOMINAL first
     // block (remainder 0, the acquired code frequency), which a resident call's first block is: every window of a record takes the
     // same kernel with the same teams as the whole record would
@@ -1024,42 +814,6 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
     nominal.blksize = (int)std::ceil(p->code_length / nominal.code_phase_step);
     nominal.el_spacing = p->el_spacing;
     if (c == 0) nominal_blksize = nominal.blksize;
-    if (r && r->resume) {  // continue where the previous window stopped (gc_track_window's counterpart)
-      const gc_channel_state& g = r->state[c];
-      if (g.status != 0) s.status = 2;  // ended before: does not run
-      s.pos = g.next_sample - origin;
-      s.code_freq = g.code_freq;
-      s.rem_code = g.rem_code_phase;
-      s.carr_freq = g.carr_freq;
-      s.rem_carr = g.rem_carr_phase;
-      s.old_code_nco = g.old_code_nco;
-      s.old_code_err = g.old_code_error;
-      s.old_carr_nco = g.old_carr_nco;
-      s.old_carr_err = g.old_carr_error;
-      s.d_carr_err = g.d_carr_error;
-      s.d2_carr_err = g.d2_carr_error;
-      s.table_phase = g.table_phase;
-    }
-    // the first block: the statements devloop_post ends every epoch with (tracking.m:219-222, GPS_L2C tracking.m:261)
-    const double step = s.code_freq / p->sampling_freq;
-    const bool finite = step > 0.0 && step < 1e6 && s.carr_freq == s.carr_freq;
-    const int n = finite ? (int)std::ceil((p->code_length - s.rem_code) / step) : 0;
-    gc_block& b = s.blk;
-    b.channel = init[c].channel;
-    if (p->table_phase_count > 0 && s.table_phase > 0)  // GPS_L2C tracking.m:261: index + codeLength*(CLCodePhase-1)
-      b.table_offset[1] = (int32_t)p->code_length * (s.table_phase - 1);
-    b.blksize = n;
-    b.first_sample = s.pos;
-    b.rem_code_phase = s.rem_code;
-    b.code_phase_step = step;
-    b.el_spacing = p->el_spacing;
-    b.carr_freq = s.carr_freq;
-    b.rem_carr_phase = s.rem_carr;
-    if (s.status == 0) {
-      if (!finite) s.status = 4;
-      else if (s.pos < 0 || (uint64_t)(s.pos + n) > ctx->if_nsamples) s.status = (r && r->pause_at_end) ? 5 : 2;  // not even one block: tracking.m:241-245
-      else if (s.epoch_budget <= 0) s.status = 1;
-    }
     gc_block probe = nominal;
     probe.code_phase_step = nominal.code_phase_step * 1.001;  // head-room for the code NCO
     lowrate = std::min(lowrate, gc_block_lowrate_level(ctx, probe));
@@ -1098,20 +852,8 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
   // kernel's 21 ms beside it), spread over the device they overlap completely and lose nothing alone (88.7 vs 89.7 ms).
   const bool xcd_local = GC_TUNE_ENV("GC_DEVLOOP_SPREAD") == nullptr && !ctx->concurrent_jobs;
 
-  gcorr::DevLoopArgs ha;
-  std::memset(&ha, 0, sizeof ha);
-  ha.prm = *p;
-  calc_loop_coef(p->dll_noise_bw, p->dll_damping, 1.0, &ha.tau1code, &ha.tau2code);
-  calc_loop_coef(p->pll_noise_bw, p->pll_damping, 0.25, &ha.tau1carr, &ha.tau2carr);
-  ha.k1code = ha.tau2code / ha.tau1code;
-  ha.k2code = p->int_time / ha.tau1code;
-  ha.k1carr = ha.tau2carr / ha.tau1carr;
-  ha.k2carr = p->int_time / ha.tau1carr;
-  ha.if_nsamples = ctx->if_nsamples;
   ha.n_epochs = n_epochs;
   ha.splits = splits;
-  ha.pause = (r && r->pause_at_end) ? 1 : 0;
-  ha.origin = origin;
   ha.code_index_scale_is_one = 1;
   if (const char* e = GC_TUNE_ENV("GC_DEVLOOP_SCOPE")) ha.reserved = std::atoi(e);  // message scope (devloop.h): 0 system (default), 2 agent
   ha.timing = GC_TUNE_ENV("GC_DEVLOOP_TIMING") ? std::atoi(GC_TUNE_ENV("GC_DEVLOOP_TIMING")) : 0;  // 1: host + in-kernel phase clocks, 2: host only
@@ -1241,26 +983,8 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
       epochs_done[c] = hc[c].epochs_done;
     }
   }
-  if (r) {  // the loop state the next window's call starts from, in record coordinates
-    for (int c = 0; c < nch; ++c) {
-      const gcorr::DevLoopChan& s = hc[c];
-      gc_channel_state& g = r->state[c];
-      g.next_sample = s.pos + origin;
-      g.code_freq = s.code_freq;
-      g.rem_code_phase = s.rem_code;
-      g.carr_freq = s.carr_freq;
-      g.rem_carr_phase = s.rem_carr;
-      g.old_code_nco = s.old_code_nco;
-      g.old_code_error = s.old_code_err;
-      g.old_carr_nco = s.old_carr_nco;
-      g.old_carr_error = s.old_carr_err;
-      g.d_carr_error = s.d_carr_err;
-      g.d2_carr_error = s.d2_carr_err;
-      g.table_phase = s.table_phase;
-      g.status = (s.status == 2 || s.status == 4) ? 2 : 0;  // running or paused | ended
-      g.reserved = 0;
-    }
-  }
+  if (r)  // the loop state the next window's call starts from, in record coordinates
+    for (int c = 0; c < nch; ++c) gcorr::devloop_state_out(r->state[c], hc[c], origin);
   if (!r && p->cno_mode != GC_CNO_VSM) gc_fill_cno_host(ctx, p, nch, out, epochs_done);  // Calc_CNo_PLD: from the records, as everywhere
   if (diverged) {
     gc_set_error("gc_track_device: a channel's code / carrier NCO became non-finite (all-zero correlator sums?); its records end there");
