@@ -25,7 +25,7 @@
 // of both kinds (no test at all), bit 1 = free of six-fold near-edges (the per-sample integer test is skipped).
 #include <cstdlib>
 
-#include "corr_common.h"
+#include "launch_plan.h"
 
 using namespace gcorr;
 
@@ -471,40 +471,17 @@ void launch_cboc_waves(gc_context* ctx, const KArgs& a, dim3 grid, size_t smem) 
 
 }  // namespace
 
-// Wavefronts per workgroup: the most of {4, 3, 2, 1} whose LDS (two interleaved int8 tables + 32 KB of running sums per wave)
-// fits a CU; 0 = not even one (GC_CBOC_WAVES overrides)
-int gc_cboc_waves(const gc_context* ctx) {
-  const int tb = gc_multi_table_bytes(ctx->max_stage_len, 2);
-  int forced = 0;
-  if (const char* e = GC_TUNE_ENV("GC_CBOC_WAVES")) forced = std::atoi(e);
-  for (int w : {16, 12, 8, 6, 4, 2, 1}) {
-    if (tb + w * kWaveLds > kMaxLds) continue;
-    if (forced == 0 || forced == w) return w;
-  }
-  return 0;
-}
-
-bool gc_cboc_takes(const gc_context* ctx, long long nblocks, int period) {
-  if (!(ctx->scope_kt6 >= 1 && period > 0 && ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL)) return false;
-  const long long waves = gc_cboc_waves(ctx);
-  if (waves <= 0) return false;
-  // A wave takes one epoch and a workgroup fills a CU, so the launch runs in rounds of waves x CUs epochs and a part-filled last round
-  // costs a whole one; a single round is as long as its slowest wave (a channel's first block sits on exact chip edges and takes the
-  // float64 path chunk after chunk: ~0.2 ms more).  Measured on config 3's shape (eight channels, 1 - 10 s: lane kernel 97 ns per block;
-  // the hybrid 0.47 ms for one round, 0.255 ms per round from two on): ahead from two rounds at least two thirds full on (3 s: 0.52
-  // against 0.57 ms), up to 58 % behind below (1.5 s = 0.72 rounds: 0.47 / 0.30; 2.1 s = 1.02 rounds: 0.51 / 0.41).
-  const long long cus = ctx->compute_units;
-  const long long wgs = ((nblocks / period + waves - 1) / waves) * period;
-  const long long rounds = (wgs + cus - 1) / cus;
-  return rounds >= 2 && 3 * nblocks >= 2 * rounds * cus * waves;
-}
+static_assert(kMaxLds == kPlanMaxLds && kGLO + kGHI == kPlanTabGuard && kWaveLds == kPlanWaveSums,
+              "gc_multi_table_bytes / gc_cboc_waves (launch_plan.h) size this kernel's LDS");
 
 // Periodic replay lists of int8 I/Q (Q/I) records whose channels are three-arm channels with a derived six-fold arm
 // (gc_channel_is_derived), base ramp with at most two table transitions per 16-sample chunk; a.bpw = a multiple of `waves`,
 // a.stride = the list's period, a.splits == 1.
-int gc_launch_correlator_cboc(gc_context* ctx, const KArgs& a_in, unsigned int grid, int waves) {
+int gc_launch_correlator_cboc(gc_context* ctx, const KArgs& a_in, const LaunchScope& s, const LaunchPlan& plan) {
   KArgs a = a_in;
-  a.red_off = gc_multi_table_bytes(ctx->max_stage_len, 2);
+  const unsigned int grid = plan.grid;
+  const int waves = plan.waves;
+  a.red_off = gc_multi_table_bytes(s.stage_len, 2);
   const size_t smem = (size_t)a.red_off + (size_t)waves * kWaveLds;
   if (waves == 16) launch_cboc_waves<16>(ctx, a, dim3(grid), smem);
   else if (waves == 8) launch_cboc_waves<8>(ctx, a, dim3(grid), smem);

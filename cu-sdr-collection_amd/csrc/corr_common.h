@@ -372,23 +372,15 @@ __device__ __forceinline__ gc_block load_block(const KArgs& p, long long lb) {
 
 }  // namespace gcorr
 
+// The launchers: kernel arguments filled from the plan, LDS layout from the scope's table sizes, the instantiation from the
+// record format (launch_plan.h: LaunchScope, LaunchPlan).
 // corr_lane.hip
-int gc_launch_devloop_lane(gc_context* ctx, const gcorr::KArgs& a, unsigned int grid, int max_arms, bool share_el, int waves);
-int gc_launch_correlator_lane(gc_context* ctx, const gcorr::KArgs& a, const gcorr::InlineBlocks& ib, unsigned int grid,
-                              int max_arms, bool share_el);
+int gc_launch_devloop_lane(gc_context* ctx, const gcorr::KArgs& a, const LaunchScope& s, unsigned int grid, bool share_el, int waves);
+int gc_launch_correlator_lane(gc_context* ctx, const gcorr::KArgs& a, const gcorr::InlineBlocks& ib, const LaunchScope& s, const LaunchPlan& plan);
 // corr_multi.hip
-int gc_multi_waves(const gc_context* ctx, int max_arms, long long nblocks, int period, int kt, bool share_el);
-int gc_launch_correlator_multi(gc_context* ctx, const gcorr::KArgs& a, unsigned int grid, int max_arms, int kt, bool share_el, int waves);
+int gc_launch_correlator_multi(gc_context* ctx, const gcorr::KArgs& a, const LaunchScope& s, const LaunchPlan& plan);
 // corr_cboc.hip
-int gc_cboc_waves(const gc_context* ctx);
-// the hybrid kernel takes a periodic replay list of `nblocks` blocks (channel pattern period `period`) of the scope just validated:
-// every channel a three-arm channel with a derived six-fold arm, base ramp with <= 2 transitions per 16-sample chunk (scope_kt6), int8
-// I/Q or Q/I record, tables + 8 KB of running sums per wave fit a CU, and the launch at least two rounds (of waves x CUs epochs), at
-// least two thirds full
-bool gc_cboc_takes(const gc_context* ctx, long long nblocks, int period);
-int gc_launch_correlator_cboc(gc_context* ctx, const gcorr::KArgs& a, unsigned int grid, int waves);
+int gc_launch_correlator_cboc(gc_context* ctx, const gcorr::KArgs& a, const LaunchScope& s, const LaunchPlan& plan);
 // corr_fast.hip
-bool gc_fast_prefers_wide();  // compiled with the prefix-sum variant
-int gc_launch_devloop(gc_context* ctx, const gcorr::KArgs& a, unsigned int grid, bool spl16, bool share_el);
-int gc_launch_correlator_fast(gc_context* ctx, const gcorr::KArgs& a, const gcorr::InlineBlocks& ib, unsigned int grid,
-                              int max_arms, bool spl16);
+int gc_launch_devloop(gc_context* ctx, const gcorr::KArgs& a, const LaunchScope& s, unsigned int grid, bool spl16, bool share_el);
+int gc_launch_correlator_fast(gc_context* ctx, const gcorr::KArgs& a, const gcorr::InlineBlocks& ib, const LaunchScope& s, const LaunchPlan& plan);

@@ -760,22 +760,22 @@ int launch_devloop_mode(gc_context* ctx, KArgs& a, const InlineBlocks& ib, dim3 
 }  // namespace
 
 // Persistent single-arm tracker (any record format) with device-side loop closure: grid = channels x splits one-wave workgroups.
-int gc_launch_devloop(gc_context* ctx, const KArgs& a_in, unsigned int grid, bool spl16, bool share_el) {
+int gc_launch_devloop(gc_context* ctx, const KArgs& a_in, const LaunchScope& s, unsigned int grid, bool spl16, bool share_el) {
   KArgs a = a_in;
   InlineBlocks ib;
   std::memset(&ib, 0, sizeof ib);
-  a.red_off = 8 * ctx->max_lds_bytes;
+  a.red_off = 8 * s.lds_bytes;
   const size_t smem = (size_t)a.red_off + 8 * 3 * 64 + (size_t)16 * kFW * sizeof(float2);  // + the closer's reduction scratch + prefix sums
   return launch_devloop_mode(ctx, a, ib, dim3(grid), smem, share_el, spl16 && ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL);
 }
 
-bool gc_fast_prefers_wide() { return true; }
-
-// spl16: every block satisfies 15*step*R*M < 1 and the samples are int8 I/Q
-int gc_launch_correlator_fast(gc_context* ctx, const KArgs& a, const InlineBlocks& ib, unsigned int grid, int max_arms,
-                              bool spl16) {
-  // float2 tables: 8 bytes per staged entry (lds_off counts entries here)
-  const bool wide = spl16 && ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL;  // 16-sample chunks
+// plan.chunk == 16: every block satisfies 15*step*R*M < 1 and the samples are int8 I/Q
+int gc_launch_correlator_fast(gc_context* ctx, const KArgs& a_in, const InlineBlocks& ib, const LaunchScope& s, const LaunchPlan& plan) {
+  KArgs a = a_in;
+  a.red_off = (a.wide == 2 ? 4 : a.wide ? 2 : 8) * s.lds_bytes;  // float2 {c, dc} tables: 8 bytes per staged entry (int8 pairs: 2, plain floats: 4)
+  const unsigned int grid = plan.grid;
+  const int max_arms = s.max_arms;
+  const bool wide = plan.chunk == 16;
   // + per wave the running prefix sums of one lane-chunk ([SPL][64] float2) of the prefix-sum variant
   size_t smem = (size_t)a.red_off + 64 + (size_t)(a.wide ? 4 : 1) * (wide ? 16 : 8) * kFW * sizeof(float2);
   if (const char* e = GC_TUNE_ENV("GC_FAST_EXTRA_LDS")) smem += (size_t)std::atoi(e);  // tuning: occupancy experiments

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(DEVLOOP ? 8 * 64 : kLW * 64)  // device loop: at mo
     const void* pre = kF16 ? (const void*)chn0->tabh : (const void*)chn0->tabf;
     // pre-interleaved copy usable as is: the same pitch AND the same layout - a derived channel's f32 image is {arm 0, arm 1,
     // arm 1 * (-1)^entry, 0}, which has the pitch of a genuine three-arm image {arm 0, arm 1, arm 2, 0}: the host routes such
-    // channels to the DER instantiation (validate_blocks), this check makes a mix-up impossible instead of silent
+    // channels to the DER instantiation (gc_scope_from_blocks), this check makes a mix-up impossible instead of silent
     bool plain = pre != nullptr && (kF16 ? chn0->tabh_ap : chn0->tabf_ap) == AP && (kF16 || (chn0->derived != 0) == DER);
 #pragma unroll
     for (int a = 0; a < LA; ++a) {
@@ -992,16 +992,17 @@ int gc_lane_part_derived(gc_context* ctx, KArgs& a, const InlineBlocks& ib, unsi
 #if GC_LANE_HAS(0)
 // Persistent tracker with device-side loop closure on the lane kernel: grid = channel slots x a.splits member workgroups.
 // f32 tables only (<= 96 KiB), int8 I/Q or Q/I records, one or two arms.
-int gc_launch_devloop_lane(gc_context* ctx, const KArgs& a_in, unsigned int grid, int max_arms, bool share_el, int waves) {
+int gc_launch_devloop_lane(gc_context* ctx, const KArgs& a_in, const LaunchScope& s, unsigned int grid, bool share_el, int waves) {
   KArgs a = a_in;
+  const int max_arms = s.max_arms;
   InlineBlocks ib;
   std::memset(&ib, 0, sizeof ib);
   const bool der = a.derived != 0 && max_arms == 3;  // third arm derived from the second: two tables in LDS (host-fed runs only)
   const int ap = gc_arm_pitch(der ? 2 : max_arms);
   // a derived arm's f32 image has four values per entry (the third: arm 1 times (-1)^entry, DevChannel::tabf_ap) and may take
   // most of the LDS - a persistent member is alone on its CU anyway; every other f32 table stays below 96 KiB
-  const size_t f32_bytes = (((size_t)ctx->max_stage_len + 2 * kGuard) * ((der && GC_LANE_PN != 0) ? 4 : ap) * 4 + 15) / 16 * 16;
-  const size_t f16_bytes = (((size_t)ctx->max_stage_len + 2 * kGuard) * ap * 2 + 15) / 16 * 16;
+  const size_t f32_bytes = (((size_t)s.stage_len + 2 * kGuard) * ((der && GC_LANE_PN != 0) ? 4 : ap) * 4 + 15) / 16 * 16;
+  const size_t f16_bytes = (((size_t)s.stage_len + 2 * kGuard) * ap * 2 + 15) / 16 * 16;
   const bool half_tables = f32_bytes > (der ? 136u : 96u) * 1024;  // BDS B1C: two 20 462-entry arms = 164 KB as f32, 82 KB as f16
   const size_t tab_bytes = half_tables ? f16_bytes : f32_bytes;
   const bool i8c = ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL;  // int8 I/Q or Q/I
@@ -1019,12 +1020,14 @@ int gc_launch_devloop_lane(gc_context* ctx, const KArgs& a_in, unsigned int grid
   return gc_lane_part_devloop2(ctx, a, ib, grid, smem, share_el, waves, half_tables);
 }
 
-// share_el: every block of the launch has 2*el_spacing*R*M an exact positive integer
-int gc_launch_correlator_lane(gc_context* ctx, const KArgs& a_in, const InlineBlocks& ib, unsigned int grid, int max_arms,
-                              bool share_el) {
+// s.share_lane: every block of the launch has 2*el_spacing*R*M == 1
+int gc_launch_correlator_lane(gc_context* ctx, const KArgs& a_in, const InlineBlocks& ib, const LaunchScope& s, const LaunchPlan& plan) {
   KArgs a = a_in;
+  const unsigned int grid = plan.grid;
+  const int max_arms = s.max_arms;
+  const bool share_el = s.share_lane;
   const int ap = gc_arm_pitch(a.derived ? 2 : max_arms);  // a derived third arm has no table of its own ...
-  const size_t entries = (size_t)ctx->max_stage_len + 2 * kGuard;
+  const size_t entries = (size_t)s.stage_len + 2 * kGuard;
   // ... but its f32 image carries a third column, arm 1 times (-1)^entry: four values per entry (DevChannel::tabf_ap), up to 136 KiB
   const size_t f32_bytes = (entries * ((a.derived && GC_LANE_PN != 0) ? 4 : ap) * 4 + 15) / 16 * 16;
   const size_t f16_bytes = (entries * ap * 2 + 15) / 16 * 16;

@@ -23,7 +23,7 @@
 //     corr_fast.hip; blocks the host proved tie-free (gc_mark_tie_free) skip the test.
 #include <cstdlib>
 
-#include "corr_common.h"
+#include "launch_plan.h"
 
 using namespace gcorr;
 
@@ -463,33 +463,17 @@ void launch_multi_waves(gc_context* ctx, const KArgs& a, dim3 grid, size_t smem,
 
 }  // namespace
 
-// LDS bytes of the interleaved int8 tables of a launch whose longest table has `max_entries` entries
-int gc_multi_table_bytes(int max_entries, int arms) { return ((max_entries + kGLO + kGHI) * (arms <= 1 ? 1 : 2) + 15) / 16 * 16; }
-
-// Wavefronts per workgroup for a launch: the most of {16, 12, 8, 4} whose LDS (tables + 8 KB of running sums per wave) fits the CU
-// and that still leaves the list >= 2 workgroups per CU (GC_MULTI_WAVES overrides); 0 = the tables do not fit at all.
-int gc_multi_waves(const gc_context* ctx, int max_arms, long long nblocks, int period, int kt, bool share_el) {
-  const int tb = gc_multi_table_bytes(ctx->max_stage_len, max_arms);
-  int forced = 0;
-  if (const char* e = GC_TUNE_ENV("GC_MULTI_WAVES")) forced = std::atoi(e);
-  if (ctx->if_dtype == GC_I16) return tb + 4 * kMSPL * 2 * kMW * (int)sizeof(float) <= kMaxLds ? 4 : 0;  // the int16 instantiations: 4 waves
-  // two transitions per chunk (short tables: Galileo E1, BDS B1I): three four-wave workgroups per CU measured 3 % ahead of one
-  // sixteen-wave workgroup (e1x8: 1.40 against 1.44 ms); four transitions (GPS L5 at 50 Msps): the other way round (3.95 / 4.10 ms)
-  if (forced == 0 && kt <= 2 && 3 * (tb + 4 * kMSPL * 2 * kMW * (int)sizeof(float)) <= kMaxLds) return 4;
-  for (int w : {16, 12, 8, 4}) {
-    if (tb + w * kMSPL * 2 * kMW * (int)sizeof(float) > kMaxLds) continue;
-    if (w == 16 && max_arms == 2 && kt == 4 && !share_el) continue;  // three ramps x four transitions x two arms: 135 VGPRs, over the 128 a 1024-thread workgroup gets
-    if (forced == w) return w;
-    if (forced == 0 && (w == 4 || nblocks / ((long long)w * std::max(1, period)) * period >= 2LL * ctx->compute_units)) return w;
-  }
-  return 0;
-}
+static_assert(kMaxLds == kPlanMaxLds && kGLO + kGHI == kPlanTabGuard && kMSPL * 2 * kMW * (int)sizeof(float) == kPlanWaveSums,
+              "gc_multi_table_bytes / gc_multi_waves (launch_plan.h) size this kernel's LDS");
 
 // Periodic replay lists of int8 I/Q (Q/I) records, one or two arms with one ramp multiplier, at most `kt` (2 or 4) table
 // transitions per 16-sample chunk; a.bpw = a multiple of `waves` (gc_multi_waves), a.stride = the list's period, a.splits == 1.
-int gc_launch_correlator_multi(gc_context* ctx, const KArgs& a_in, unsigned int grid, int max_arms, int kt, bool share_el, int waves) {
+int gc_launch_correlator_multi(gc_context* ctx, const KArgs& a_in, const LaunchScope& s, const LaunchPlan& plan) {
   KArgs a = a_in;
-  a.red_off = gc_multi_table_bytes(ctx->max_stage_len, max_arms);
+  const unsigned int grid = plan.grid;
+  const int max_arms = s.max_arms, kt = s.kt, waves = plan.waves;
+  const bool share_el = s.share_lane;
+  a.red_off = gc_multi_table_bytes(s.stage_len, max_arms);
   const size_t smem = (size_t)a.red_off + (size_t)waves * kMSPL * 2 * kMW * sizeof(float);
   if (waves == 16) launch_multi_waves<16>(ctx, a, dim3(grid), smem, max_arms, kt, share_el);
   else if (waves == 12) launch_multi_waves<12>(ctx, a, dim3(grid), smem, max_arms, kt, share_el);

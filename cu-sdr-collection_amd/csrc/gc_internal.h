@@ -107,6 +107,42 @@ inline void gc_buf_free(GcBuf& b) {
   b.cap = 0;
 }
 
+// What a correlator launch needs to know about the channels and blocks it covers.  A value: built from a descriptor list
+// (gc_scope_from_blocks: gc_correlate, gc_replay_prepare) or from a channel set (gc_scope_add_channel + gc_scope_set_epoch: the
+// tracking loops), handed to the planner and the launchers, kept by nobody but the replay list it describes (launch_plan.h).
+struct LaunchScope {
+  int lds_bytes = 0;        // staged int8 bytes of the largest channel (the fast kernels scale them by 8, 2 or 4)
+  int stage_len = 0;        // longest staged table (entries): lane, multi-transition and hybrid kernels
+  int max_arms = 1;         // largest arm count a channel is configured with: the arms the kernel is instantiated for
+  // lowrate level, resolved to the kernel class the launch qualifies for: -1 = exact per-sample kernel (mixed ramp multipliers),
+  // 0 = lane kernel, 1 / 2 = fast kernel with 8- / 16-sample lane-chunks (at most one table transition per chunk and tap)
+  int fast = 0;
+  bool share_el = false;    // every block has el_spacing*R*M == 1/2 on a one-arm channel (gc_block_shares_el)
+  bool share_lane = false;  // every block has 2*el_spacing*R*M == 1 (gc_block_shares_el_lane)
+  // multi-transition kernel (corr_multi.hip): 0 = some block or channel does not qualify, else the largest number of table
+  // transitions a 16-sample chunk of any block can see (2 or 4) - int8 tables of one ramp multiplier, no windows
+  int kt = 0;
+  // hybrid kernel (corr_cboc.hip): every channel has a derived six-fold arm and every block's base ramp sees at most this many
+  // (1 or 2) table transitions per 16-sample chunk; 0 = does not qualify
+  int kt6 = 0;
+  bool derived = false;     // the lane kernel's derived-arm instantiation (gc_derived_arm_launch)
+  int min_blksize = 0;      // shortest block
+  int period = 0;           // channel pattern period of a replay list (0 = not periodic, or not a replay list)
+};
+
+// What the planner decided for one launch (gc_plan_launch, launch_plan.h): the kernel and its geometry.
+struct LaunchPlan {
+  int kernel = -2;  // gc_debug_last_kernel: -1 exact per-sample, 0 lane, 1 fast, 2 WIDE, 3 float-table WIDE, 4 multi-transition, 5 hybrid, 6 float64
+  int fast = 0;     // LaunchScope::fast after the planner's demotions
+  int chunk = 8;    // samples per lane-chunk of the fast kernel
+  int bpw = 1, stride = 1, wide = 0;  // KArgs::bpw / stride / wide
+  bool share_el = false, derived = false;
+  int waves = 0;    // wavefronts per workgroup where the kernel has the choice (multi-transition, hybrid)
+  unsigned int grid = 0;
+  int xcd_swizzle = 0;
+  long long total_wg = 0;
+};
+
 struct gc_context {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -127,22 +163,6 @@ struct gc_context {
   HostChannel ch[GC_MAX_CHANNELS];
   DevChannel* d_channels = nullptr;  // GC_MAX_CHANNELS entries
   bool channels_dirty = true;
-  // scope of the launch being prepared (gc_scope_reset / gc_scope_add): LDS needs of the channels it references
-  int max_lds_bytes = 0;  // int8 bytes of the largest channel (fast kernels scale it by 8 or 2)
-  int max_stage_len = 0;  // longest staged table (entries), generic kernel
-  int max_arms_configured = 0;
-  int replay_scope[3] = {0, 0, 0};
-  bool scope_share_lane = false;  // every block of the scope has 2*el_spacing*R*M an exact positive integer
-  bool replay_share_lane = false;
-  // multi-transition kernel (corr_multi.hip): 0 = some block or channel of the scope does not qualify, else the largest number of
-  // table transitions a 16-sample chunk of any block can see (2 or 4) - int8 tables of one ramp multiplier, no windows
-  int scope_kt = 0;
-  int replay_kt = 0;
-  // hybrid kernel (corr_cboc.hip): every channel of the scope has a derived six-fold arm and every block's base ramp sees at most
-  // this many (1 or 2) table transitions per 16-sample chunk; 0 = does not qualify
-  int scope_kt6 = 0;
-  int replay_kt6 = 0;
-  int replay_min_blksize = 0;
 
   // scratch for gc_correlate / gc_track
   gc_block* d_blocks = nullptr;
@@ -161,13 +181,8 @@ struct gc_context {
   gc_block* d_replay_blocks = nullptr;
   double* d_replay_out = nullptr;
   int64_t replay_nblocks = 0;
-  int replay_max_arms = 1;
-  int replay_fast = 0;
-  bool replay_derived = false;
-  int replay_period = 0;
-  bool replay_share_el = false;  // channel pattern period of the replay list (0 = not periodic)
+  LaunchScope replay_scope;  // of the prepared list (gc_replay_prepare); gc_replay_launch plans from it, whatever ran in between
   bool force_generic = false;
-  bool launch_derived = false;  // the launch being prepared runs the lane kernel's derived-arm instantiation
   int last_kernel = -2;  // gc_debug_last_kernel
   int last_track_mode = -1;  // gc_debug_last_track_mode: 0 launch per epoch, 1 persistent host-fed kernel, 2 device loop
   int precision = GC_PREC_F32;  // gc_set_precision: GC_PREC_F64 routes gc_correlate and the tracking loops to corr_f64.hip
@@ -249,26 +264,9 @@ void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const 
 int gc_bytes_per_sample(int dtype, int layout);
 void gc_acq_free(gc_context* ctx);  // acq_coarse.hip
 int gc_sync_channels(gc_context* ctx);
-void gc_scope_reset(gc_context* ctx);
-void gc_scope_add(gc_context* ctx, int channel);
-// Launches the correlator for `nblocks` descriptors already on the device.
-int gc_launch_correlator(gc_context* ctx, const gc_block* d_blocks, int64_t nblocks, int splits,
-                         double* d_out, double* d_partial, int max_arms, int fast, int period = 0,
-                         unsigned int notify_tag = 0, bool share_el = false);
-// el_spacing * R * M == 1/2 exactly: early and late ramps differ by one whole table entry
-bool gc_block_shares_el(const gc_context* ctx, const gc_block& b);
-// 2 * el_spacing * R * M == 1 exactly: early, prompt and late taps read table entries k and k + 1 of ONE ramp (lane kernel, HALF)
-bool gc_block_shares_el_lane(const gc_context* ctx, const gc_block& b);
-// Kernel class a block qualifies for: 0 = generic only, 1 = fast kernel with 8-sample lane-chunks,
-// 2 = fast kernel with 16-sample lane-chunks (at most one table transition per chunk and tap).
-int gc_block_lowrate_level(const gc_context* ctx, const gc_block& b);
-bool gc_fast_lds_ok(const gc_context* ctx);
-int gc_lane_splits(const gc_context* ctx, int64_t nblocks, int min_blksize, int cap);
+// Launches the correlator for `nblocks` descriptors of scope `s` already on the device: plans (launch_plan.h), fills the
+// kernel arguments from the plan, dispatches on its kernel, combines the partial sums where splits > 1.
+int gc_launch_correlator(gc_context* ctx, const LaunchScope& s, const gc_block* d_blocks, int64_t nblocks, int splits,
+                         double* d_out, double* d_partial, unsigned int notify_tag = 0);
 int64_t gc_first_sample_near_edge(double a, double step, int64_t n, double eps);
 void gc_mark_tie_free(const gc_context* ctx, gc_block* b, int64_t n, double eps_unit_steps);
-// 0 = float2 tables / single-wave workgroups, 1 = WIDE (int8 pairs, four waves), -1 = tables too large for the fast kernel
-int gc_fast_table_mode(const gc_context* ctx);
-// corr_multi.hip
-int gc_multi_table_bytes(int max_entries, int arms);
-int gc_block_multi_kt(const gc_context* ctx, const gc_block& b);  // 1, 2, 4 transitions per 16-sample chunk at most; 0 = more
-bool gc_channel_is_derived(const HostChannel& c);  // cached in HostChannel::derived_state

@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <utility>
 
-#include "corr_common.h"
+#include "launch_plan.h"
 
 static thread_local std::string g_last_error;
 
@@ -476,34 +476,8 @@ int gc_set_code_window(gc_context* ctx, int channel, int arm, int window_entries
 
 }  // extern "C"
 
-// Three arms {a, b, b'} where b' is b with a sign pattern at six times the ramp rate — BOC(6,1) next to BOC(1,1) (BDS B1C
-// wide-band pilot, Galileo E1-C CBOC): entry k6 of b' (padded like every table) is entry p = (k6 + 5) / 6 of b times
-// (-1)^(p + k6).  Then the lane kernel needs no third table (csrc/corr_lane.hip, DER).
-static bool tables_derivable(const int8_t* t1, int nent1, const int8_t* t6, int nent6) {
-  const int n1 = nent1 - 2, n6 = nent6 - 2;
-  if (n1 < 1 || n6 != 6 * n1) return false;
-  for (int k6 = 0; k6 < nent6; ++k6) {
-    const int pidx = (k6 + 5) / 6;
-    if (t6[k6] != t1[pidx] * (((pidx + k6) & 1) ? -1 : 1)) return false;
-  }
-  return true;
-}
 extern "C" int gc_debug_tables_derivable(const int8_t* t1, int n1, const int8_t* t6, int n6) {
-  return (t1 && t6 && tables_derivable(t1, n1, t6, n6)) ? 1 : 0;
-}
-
-static bool channel_is_derived_uncached(const HostChannel& c) {
-  if (GC_TUNE_ENV("GC_NO_DERIVED_ARM")) return false;
-  if (c.arms != 3 || c.mult[0] != c.mult[1] || c.mult[2] != 6.0 * c.mult[1]) return false;
-  for (int a = 0; a < 3; ++a)
-    if (c.window[a] != 0 || (int)c.h_tab[a].size() != c.nent[a]) return false;
-  // the two interleaved arms must fit the lane kernel's LDS budget as f16 at least (f32 up to 96 KiB)
-  if (((size_t)std::max(c.nent[0], c.nent[1]) + 2 * gcorr::kGuard) * 2 * 2 + 2048 > 160 * 1024) return false;
-  return tables_derivable(c.h_tab[1].data(), c.nent[1], c.h_tab[2].data(), c.nent[2]);
-}
-bool gc_channel_is_derived(const HostChannel& c) {
-  if (c.derived_state < 0) c.derived_state = channel_is_derived_uncached(c) ? 1 : 0;
-  return c.derived_state == 1;
+  return (t1 && t6 && gc_tables_derivable(t1, n1, t6, n6)) ? 1 : 0;
 }
 
 int gc_sync_channels(gc_context* ctx) {
@@ -738,183 +712,6 @@ extern "C" long long gc_debug_first_sample_near_edge(double a, double step, long
   return gc_first_sample_near_edge(a, step, n, eps);
 }
 
-int gc_block_lowrate_level(const gc_context* ctx, const gc_block& b) {
-  const HostChannel& c = ctx->ch[b.channel];
-  // at most one table transition per lane-chunk (8 or 16 samples), with a safety margin
-  const double s = b.code_phase_step * c.index_scale * c.mult[0];
-  return (15.0 * s < 0.995) ? 2 : (7.0 * s < 0.995) ? 1 : 0;
-}
-
-int gc_block_multi_kt(const gc_context* ctx, const gc_block& b) {
-  const HostChannel& c = ctx->ch[b.channel];
-  // (16 - 1) samples advance the table index by 15*s entries: at most KT integers are crossed when that stays below KT
-  const double s = 15.0 * b.code_phase_step * c.index_scale * c.mult[0];
-  return s < 0.995 ? 1 : s < 1.995 ? 2 : s < 3.995 ? 4 : 0;
-}
-
-bool gc_block_shares_el_lane(const gc_context* ctx, const gc_block& b) {
-  const HostChannel& c = ctx->ch[b.channel];
-  const double v = 2.0 * b.el_spacing * c.index_scale * c.mult[0];
-  return v == 1.0;  // exactly half a table entry between prompt and early / late: the lane kernel's one-ramp (HALF) variant
-}
-
-bool gc_block_shares_el(const gc_context* ctx, const gc_block& b) {
-  const HostChannel& c = ctx->ch[b.channel];
-  return c.arms == 1 && b.el_spacing * c.index_scale * c.mult[0] == 0.5;
-}
-
-// LDS needs of the launch being prepared ("scope" = the channels its descriptors reference): the kernels
-// size their staging areas for the largest table among THOSE channels, not among everything configured.
-void gc_scope_reset(gc_context* ctx) {
-  ctx->max_lds_bytes = 0;
-  ctx->max_stage_len = 0;
-  ctx->max_arms_configured = 0;
-}
-
-void gc_scope_add(gc_context* ctx, int channel) {
-  const HostChannel& c = ctx->ch[channel];
-  int off = 0, maxn = 0;
-  bool mixed = false;
-  for (int a = 0; a < c.arms; ++a) {
-    const int stage = (c.window[a] > 0) ? std::min(c.window[a], c.nent[a]) : c.nent[a];
-    off += ((stage + 8 + 15) / 16) * 16;  // as DevChannel::lds_off in gc_sync_channels
-    maxn = std::max(maxn, stage);
-    mixed |= c.mult[a] != c.mult[0];
-  }
-  ctx->max_arms_configured = std::max(ctx->max_arms_configured, c.arms);
-  if (mixed && gc_channel_is_derived(c)) {  // third arm derived from the second: only two tables go to LDS
-    ctx->max_stage_len = std::max(ctx->max_stage_len, std::max(c.nent[0], c.nent[1]));
-    return;
-  }
-  if (mixed) return;  // mixed-multiplier channels use the LDS-free exact kernel
-  ctx->max_lds_bytes = std::max(ctx->max_lds_bytes, off);
-  ctx->max_stage_len = std::max(ctx->max_stage_len, maxn);
-}
-
-int gc_fast_table_mode(const gc_context* ctx) {
-  if (8 * ctx->max_lds_bytes + 512 <= 64 * 1024) return 0;   // float2 tables, one wave per workgroup
-  if (2 * ctx->max_lds_bytes + 512 <= 40 * 1024 && ctx->max_arms_configured <= 2) return 1;  // int8 pairs, 4 waves share them
-  return -1;
-}
-
-bool gc_fast_lds_ok(const gc_context* ctx) {
-  const int m = gc_fast_table_mode(ctx);
-  if (m == 0) return true;
-  // WIDE is instantiated for int8 I/Q (Q/I) records and 8-sample chunks only
-  return m == 1 && ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL;
-}
-
-// Validates descriptors on the host; returns the largest arm count among the referenced
-// channels, or a negative status.  *all_lowrate is cleared if any block needs the generic kernel.
-static int validate_blocks(gc_context* ctx, int64_t n, const gc_block* b, int* all_lowrate, bool* all_share = nullptr) {
-  *all_lowrate = 2;
-  if (all_share) *all_share = true;
-  bool any_derived = false, any_plain_mixed = false, any_three_plain = false;
-  ctx->launch_derived = false;
-  if (!ctx->d_if) {
-    gc_set_error("no IF buffer loaded");
-    return GC_E_STATE;
-  }
-  if (!(ctx->fs > 0)) {
-    gc_set_error("sampling frequency not set (gc_set_sampling_freq)");
-    return GC_E_STATE;
-  }
-  int max_arms = 1;
-  bool seen[GC_MAX_CHANNELS] = {false};
-  gc_scope_reset(ctx);
-  ctx->scope_share_lane = true;
-  int kt = 1, kt6 = 1;
-  for (int64_t i = 0; i < n; ++i) {
-    const gc_block& k = b[i];
-    if (k.channel < 0 || k.channel >= GC_MAX_CHANNELS || !ctx->ch[k.channel].configured) {
-      gc_set_error("block %lld: channel %d not configured", (long long)i, k.channel);
-      return GC_E_STATE;
-    }
-    const HostChannel& c = ctx->ch[k.channel];
-    if (!seen[k.channel]) {
-      seen[k.channel] = true;
-      gc_scope_add(ctx, k.channel);
-    }
-    for (int a = 0; a < c.arms; ++a) {
-      if (!c.d_tab[a]) {
-        gc_set_error("block %lld: channel %d arm %d has no code table", (long long)i, k.channel, a);
-        return GC_E_STATE;
-      }
-      if (c.mult[a] != c.mult[0]) {  // mixed multipliers: exact per-sample kernel, unless the odd arm can be derived
-        if (gc_channel_is_derived(c)) any_derived = true;
-        else any_plain_mixed = true;
-      }
-      if (k.table_offset[a] < 0 || k.table_offset[a] + 3 > c.nent[a]) {
-        gc_set_error("block %lld: table offset out of range", (long long)i);
-        return GC_E_INVALID;
-      }
-    }
-    double max_mult = c.mult[0];
-    for (int a = 1; a < c.arms; ++a) max_mult = std::max(max_mult, c.mult[a]);
-    if (k.blksize <= 0 || k.first_sample < 0 || !(k.code_phase_step > 0) ||
-        !(k.el_spacing * c.index_scale * max_mult < 1.0) || !(k.el_spacing >= 0) ||
-        !(k.rem_code_phase > -1.0) || !std::isfinite(k.carr_freq) || !std::isfinite(k.rem_carr_phase)) {
-      gc_set_error("block %lld: invalid descriptor", (long long)i);
-      return GC_E_INVALID;
-    }
-    if ((uint64_t)k.first_sample + (uint64_t)k.blksize > ctx->if_nsamples) {
-      gc_set_error("block %lld: samples [%lld, %lld) exceed the IF buffer (%llu samples)", (long long)i,
-                   (long long)k.first_sample, (long long)(k.first_sample + k.blksize),
-                   (unsigned long long)ctx->if_nsamples);
-      return GC_E_RANGE;  // tracking.m:241-245
-    }
-    // highest and lowest table index the ramps can reach must stay inside the staged window, which starts at the entry
-    // table_offset names: the early ramp's first sample (rem - d) * R * mult > -1, i.e. index ceil(.) >= 0 (MATLAB index >= 1;
-    // tracking.m would stop with an index error on 0)
-    for (int a = 0; a < c.arms; ++a) {
-      const double tmin = (k.rem_code_phase - k.el_spacing) * c.index_scale * c.mult[a];
-      if (!(std::ceil(tmin) >= 0.0)) {
-        gc_set_error("block %lld: early code ramp starts at index %g, below the table entry at table_offset (arm %d)", (long long)i,
-                     std::ceil(tmin), a);
-        return GC_E_INVALID;
-      }
-      const double tmax = ((k.blksize - 1) * k.code_phase_step + k.rem_code_phase + k.el_spacing) *
-                          c.index_scale * c.mult[a];
-      const int stage = (c.window[a] > 0) ? std::min(c.window[a], c.nent[a]) : c.nent[a];
-      const int avail = std::min(stage, c.nent[a] - k.table_offset[a]);
-      if (std::ceil(tmax) > avail - 1) {
-        gc_set_error("block %lld: code ramp reaches index %g beyond table (%d entries)", (long long)i,
-                     std::ceil(tmax), avail);
-        return GC_E_INVALID;
-      }
-    }
-    max_arms = std::max(max_arms, c.arms);
-    if (kt > 0) {  // corr_multi.hip: whole int8 tables of one ramp multiplier, one or two arms
-      bool plain = c.arms <= 2;
-      for (int a = 0; a < c.arms; ++a) plain = plain && c.mult[a] == c.mult[0] && c.window[a] == 0 && k.table_offset[a] == 0;
-      const int need = plain ? gc_block_multi_kt(ctx, k) : 0;
-      kt = need == 0 ? 0 : std::max(kt, need);
-    }
-    if (kt6 > 0) {  // corr_cboc.hip: whole tables, derived third arm, base ramp with at most two transitions per chunk
-      bool der = c.arms == 3 && gc_channel_is_derived(c);
-      for (int a = 0; a < c.arms; ++a) der = der && k.table_offset[a] == 0;
-      const int need = der ? gc_block_multi_kt(ctx, k) : 0;
-      kt6 = (need == 0 || need > 2) ? 0 : std::max(kt6, need);
-    }
-    if (*all_lowrate >= 0) *all_lowrate = std::min(*all_lowrate, gc_block_lowrate_level(ctx, k));
-    if (all_share && !gc_block_shares_el(ctx, k)) *all_share = false;
-    if (ctx->scope_share_lane && !gc_block_shares_el_lane(ctx, k)) ctx->scope_share_lane = false;
-    if (c.arms == 3 && !gc_channel_is_derived(c)) any_three_plain = true;
-  }
-  // mixed ramp multipliers: the exact per-sample kernel (-1), unless every such channel's odd arm can be derived from its
-  // neighbour (BOC(6,1) from BOC(1,1)) and the record is int8 I/Q: then the lane kernel's derived-arm instantiation (0)
-  ctx->scope_kt = (kt >= 2 && ctx->if_layout != GC_REAL && !any_derived && !any_plain_mixed) ? kt : 0;
-  ctx->scope_kt6 = (any_derived && !any_plain_mixed && !any_three_plain && ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL) ? kt6 : 0;
-  if (any_plain_mixed || (any_derived && (any_three_plain || ctx->if_dtype != GC_I8 || ctx->if_layout == GC_REAL))) {
-    *all_lowrate = -1;
-  } else if (any_derived) {
-    *all_lowrate = 0;
-    ctx->launch_derived = true;
-    ctx->scope_share_lane = false;
-  }
-  return max_arms;
-}
-
 static int ensure(void** p, int64_t* cap, int64_t need, size_t elem) {
   if (*cap >= need) return GC_OK;
   if (*p) (void)hipFree(*p);
@@ -929,27 +726,6 @@ static int ensure(void** p, int64_t* cap, int64_t need, size_t elem) {
   return GC_OK;
 }
 
-// Number of workgroups per block for small launches: aim at >= 2 workgroups per CU.
-static int choose_splits(gc_context* ctx, int64_t nblocks, const gc_block* b, int wg_threads, int spl) {
-  if (nblocks * (wg_threads / 64) >= 8 * (int64_t)ctx->compute_units) return 1;
-  int min_chunks = 1 << 30;
-  for (int64_t i = 0; i < nblocks; ++i) min_chunks = std::min(min_chunks, b[i].blksize / spl + 1);
-  // aim at ~8 wavefronts per CU, but keep at least two chunks per thread in every split
-  int s = (int)((8 * (int64_t)ctx->compute_units * 64 / wg_threads + nblocks - 1) / nblocks);
-  s = std::min(s, std::max(1, min_chunks / (2 * wg_threads)));
-  return std::max(1, std::min(s, 64));
-}
-
-// Lane kernel (corr_lane.hip): one wavefront per (block, split) item, 16 items per workgroup sharing a block
-// -> splits is a multiple of 16; aim at 16 wavefronts per CU, keep >= 8 samples per lane in every split.
-int gc_lane_splits(const gc_context* ctx, int64_t nblocks, int min_blksize, int cap) {
-  if (nblocks >= 2 * (int64_t)ctx->compute_units) return 1;  // one block per 16-wave workgroup, combined in LDS
-  int64_t s = (16 * (int64_t)ctx->compute_units + nblocks - 1) / nblocks;
-  s = std::min<int64_t>(s, std::max(1, min_blksize / 512));
-  s = (s + 15) / 16 * 16;
-  return (int)std::max<int64_t>(16, std::min<int64_t>(s, cap / 16 * 16));
-}
-
 extern "C" {
 
 int gc_correlate(gc_context* ctx, int nblocks, const gc_block* blocks, double* out) {
@@ -959,29 +735,20 @@ int gc_correlate(gc_context* ctx, int nblocks, const gc_block* blocks, double* o
   }
   if (nblocks == 0) return GC_OK;
   GC_HIP(hipSetDevice(ctx->device));
-  int lowrate;
-  bool share;
-  const int max_arms = validate_blocks(ctx, nblocks, blocks, &lowrate, &share);
-  if (max_arms < 0) return max_arms;
-  int rc = gc_sync_channels(ctx);
+  LaunchScope scope;  // one-shot lists take no periodic geometry
+  int rc = gc_scope_from_blocks(ctx, nblocks, blocks, false, &scope);
   if (rc) return rc;
-  const int fast = lowrate < 0 ? -1 : (gc_fast_lds_ok(ctx) && !ctx->force_generic) ? lowrate : 0;
-  int splits = choose_splits(ctx, nblocks, blocks, fast > 0 ? 64 : 256, fast == 2 ? 16 : 8);
-  if (fast > 0 && gc_fast_table_mode(ctx) == 1 && splits > 1) splits = std::max(4, (splits / 4) * 4);  // WIDE kernel
-  if (fast == 0) {
-    int min_blk = 1 << 30;
-    for (int i = 0; i < nblocks; ++i) min_blk = std::min(min_blk, blocks[i].blksize);
-    splits = gc_lane_splits(ctx, nblocks, min_blk, 256);
-  }
+  if ((rc = gc_sync_channels(ctx))) return rc;
+  const int splits = gc_correlate_splits(ctx, scope, nblocks);
   if ((rc = ensure((void**)&ctx->d_blocks, &ctx->d_blocks_cap, nblocks, sizeof(gc_block)))) return rc;
   if ((rc = ensure((void**)&ctx->d_out, &ctx->d_out_cap, (int64_t)nblocks * GC_OUT_STRIDE, sizeof(double)))) return rc;
   if (splits > 1 &&
       (rc = ensure((void**)&ctx->d_partial, &ctx->d_partial_cap, (int64_t)nblocks * splits * GC_OUT_STRIDE, sizeof(double))))
     return rc;
   std::vector<gc_block> marked(blocks, blocks + nblocks);
-  gc_mark_tie_free(ctx, marked.data(), nblocks, fast > 0 ? 8e-6 : 0.0);
+  gc_mark_tie_free(ctx, marked.data(), nblocks, scope.fast > 0 ? 8e-6 : 0.0);
   GC_HIP(hipMemcpyAsync(ctx->d_blocks, marked.data(), sizeof(gc_block) * (size_t)nblocks, hipMemcpyHostToDevice, ctx->stream));
-  rc = gc_launch_correlator(ctx, ctx->d_blocks, nblocks, splits, ctx->d_out, ctx->d_partial, max_arms, fast, 0, 0u, share);
+  rc = gc_launch_correlator(ctx, scope, ctx->d_blocks, nblocks, splits, ctx->d_out, ctx->d_partial);
   if (rc) return rc;
   GC_HIP(hipMemcpyAsync(out, ctx->d_out, sizeof(double) * (size_t)nblocks * GC_OUT_STRIDE, hipMemcpyDeviceToHost, ctx->stream));
   GC_HIP(hipStreamSynchronize(ctx->stream));
@@ -998,21 +765,10 @@ int gc_replay_prepare(gc_context* ctx, int64_t nblocks, const gc_block* blocks) 
     return GC_E_UNSUPPORTED;
   }
   GC_HIP(hipSetDevice(ctx->device));
-  int lowrate;
-  bool share;
-  const int max_arms = validate_blocks(ctx, nblocks, blocks, &lowrate, &share);
-  if (max_arms < 0) return max_arms;
-  int rc = gc_sync_channels(ctx);
+  LaunchScope scope;
+  int rc = gc_scope_from_blocks(ctx, nblocks, blocks, true, &scope);
   if (rc) return rc;
-  ctx->replay_share_el = share;
-  ctx->replay_scope[0] = ctx->max_lds_bytes;
-  ctx->replay_scope[1] = ctx->max_stage_len;
-  ctx->replay_scope[2] = ctx->max_arms_configured;
-  ctx->replay_share_lane = ctx->scope_share_lane;
-  ctx->replay_kt = ctx->scope_kt;
-  ctx->replay_kt6 = ctx->scope_kt6;
-  ctx->replay_derived = ctx->launch_derived;
-  ctx->replay_fast = lowrate < 0 ? -1 : (gc_fast_lds_ok(ctx) && !ctx->force_generic) ? lowrate : 0;
+  if ((rc = gc_sync_channels(ctx))) return rc;
   GC_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->d_replay_blocks) (void)hipFree(ctx->d_replay_blocks);
   if (ctx->d_replay_out) (void)hipFree(ctx->d_replay_out);
@@ -1025,34 +781,17 @@ int gc_replay_prepare(gc_context* ctx, int64_t nblocks, const gc_block* blocks) 
     return GC_E_NOMEM;
   }
   ctx->replay_nblocks = nblocks;
-  ctx->replay_max_arms = max_arms;
-  ctx->replay_min_blksize = 1 << 30;
-  for (int64_t i = 0; i < nblocks; ++i) ctx->replay_min_blksize = std::min(ctx->replay_min_blksize, blocks[i].blksize);
-  // channel pattern period: blocks[i].channel == blocks[i % P].channel (epoch-major replay lists)
-  int period = 0;
-  for (int64_t i = 1; i < nblocks && i <= GC_MAX_CHANNELS; ++i)
-    if (blocks[i].channel == blocks[0].channel) {
-      period = (int)i;
-      break;
-    }
-  if (period > 0)
-    for (int64_t i = 0; i < nblocks; ++i)
-      if ((i >= period && blocks[i].channel != blocks[i - period].channel) || blocks[i].table_offset[0] != 0 ||
-          blocks[i].table_offset[1] != 0 || blocks[i].table_offset[2] != 0) {
-        period = 0;
-        break;
-      }
+  ctx->replay_scope = scope;
   {
     std::vector<gc_block> marked(blocks, blocks + nblocks);
     // the band the kernel that may take the list tests in: 8e-6 samples of ramp = twice the 4e-6 of corr_fast.hip and corr_multi.hip
     // (a list of derived-arm channels needs the wide band only where corr_cboc.hip takes it - gc_cboc_takes, the launcher's own
     // predicate: with it on every such list the lane kernel lost its tie-free marks on ~40 % of config 3's blocks, 0.26 -> 0.22)
-    const bool cboc_list = ctx->replay_kt6 > 0 && !GC_TUNE_ENV("GC_NO_CBOC") && gc_cboc_takes(ctx, nblocks, period);
-    gc_mark_tie_free(ctx, marked.data(), nblocks, (ctx->replay_kt > 0 || cboc_list || ctx->replay_fast > 0) ? 8e-6 : 0.0);
+    const bool cboc_list = !GC_TUNE_ENV("GC_NO_CBOC") && gc_cboc_takes(ctx, scope, nblocks);
+    gc_mark_tie_free(ctx, marked.data(), nblocks, (scope.kt > 0 || cboc_list || scope.fast > 0) ? 8e-6 : 0.0);
     GC_HIP(hipMemcpyAsync(ctx->d_replay_blocks, marked.data(), sizeof(gc_block) * (size_t)nblocks, hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
   }
-  ctx->replay_period = period;
   return GC_OK;
 }
 
@@ -1062,34 +801,13 @@ int gc_replay_launch(gc_context* ctx) {
     return GC_E_STATE;
   }
   GC_HIP(hipSetDevice(ctx->device));
-  ctx->max_lds_bytes = ctx->replay_scope[0];
-  ctx->max_stage_len = ctx->replay_scope[1];
-  ctx->max_arms_configured = ctx->replay_scope[2];
-  ctx->scope_share_lane = ctx->replay_share_lane;
-  ctx->scope_kt = ctx->replay_kt;
-  ctx->scope_kt6 = ctx->replay_kt6;
-  ctx->launch_derived = ctx->replay_derived;
-  int splits = 1;
-  if (ctx->replay_fast == 0) {
-    // lane kernel: periodic lists with enough blocks run one block per wavefront (bpw path of the launcher),
-    // everything else is split 16-fold or more
-    const bool periodic = ctx->replay_period > 0 && ctx->replay_nblocks >= 8 * (int64_t)ctx->compute_units;
-    if (!periodic) splits = gc_lane_splits(ctx, ctx->replay_nblocks, ctx->replay_min_blksize, 256);
-    if (splits > 1) {
-      int rc = ensure((void**)&ctx->d_partial, &ctx->d_partial_cap, ctx->replay_nblocks * splits * GC_OUT_STRIDE, sizeof(double));
-      if (rc) return rc;
-    }
-  } else if (ctx->replay_nblocks * (ctx->replay_fast > 0 ? 1 : 4) < 8 * (int64_t)ctx->compute_units) {
-    // small replay sets: split blocks over several workgroups, scratch from d_partial
-    const int wg_waves = ctx->replay_fast > 0 ? 1 : 4;
-    splits = (int)std::min<int64_t>(8, (8 * (int64_t)ctx->compute_units / wg_waves + ctx->replay_nblocks - 1) / ctx->replay_nblocks);
-    if (ctx->replay_fast > 0 && gc_fast_table_mode(ctx) == 1 && splits > 1) splits = std::max(4, (splits / 4) * 4);
+  const LaunchScope& scope = ctx->replay_scope;
+  const int splits = gc_replay_splits(ctx, scope, ctx->replay_nblocks);
+  if (splits > 1) {  // scratch from d_partial
     int rc = ensure((void**)&ctx->d_partial, &ctx->d_partial_cap, ctx->replay_nblocks * splits * GC_OUT_STRIDE, sizeof(double));
     if (rc) return rc;
   }
-  return gc_launch_correlator(ctx, ctx->d_replay_blocks, ctx->replay_nblocks, splits, ctx->d_replay_out,
-                              ctx->d_partial, ctx->replay_max_arms, ctx->replay_fast, ctx->replay_period, 0u,
-                              ctx->replay_share_el);
+  return gc_launch_correlator(ctx, scope, ctx->d_replay_blocks, ctx->replay_nblocks, splits, ctx->d_replay_out, ctx->d_partial);
 }
 
 int gc_replay_fetch(gc_context* ctx, double* out) {

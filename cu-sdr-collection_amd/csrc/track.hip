@@ -12,12 +12,12 @@
 #include <cstdlib>
 #include <thread>
 
-#include "corr_common.h"
 #include "devloop.h"
+#include "launch_plan.h"
 
 namespace {
 
-// What gc_correlate checks per descriptor (validate_blocks, gnsscorr.hip), for the blocks a tracking loop will cut from one
+// What gc_correlate checks per descriptor (gc_scope_from_blocks, launch_plan.h), for the blocks a tracking loop will cut from one
 // channel: every ramp stays inside the reference's [c(end) c c(1)] padding (tracking.m:158,252-270) for ANY code step, because
 // (blksize-1)*step + rem < codeLength by construction of blksize (:222): the largest index is ceil((codeLength + spacing)*R*M).
 int validate_track_channel(const gc_context* ctx, const gc_track_params* p, const gc_channel_init& in, const char* who) {
@@ -58,11 +58,12 @@ int validate_track_channel(const gc_context* ctx, const gc_track_params* p, cons
 }
 
 // What gc_track and gc_track_device check before anything runs (`who` names the entry point in the error texts): the arguments, the
-// IF buffer, every channel configured and fit for the blocks its loop will cut.  Sets the launch scope up on the way.
+// IF buffer, every channel configured and fit for the blocks its loop will cut.  Fills the channel set's launch scope (`scope`, and
+// `mix`: which channels mix ramp multipliers) on the way.
 // per_channel(channel, index): the entry point's own checks of a configured channel, made before validate_track_channel.
 template <class F>
 int track_preamble(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, const double* out, const int32_t* epochs_done,
-                   GcTrackResume* r, const char* who, int* max_arms, F&& per_channel) {
+                   GcTrackResume* r, const char* who, LaunchScope* scope, ChannelMix* mix, F&& per_channel) {
   if (r) r->paused = false;
   if (!ctx || !p || nch <= 0 || nch > GC_MAX_CHANNELS || !init || !out || !epochs_done || p->n_epochs <= 0 || (r && !r->state)) {
     gc_set_error("%s: bad arguments", who);
@@ -76,8 +77,8 @@ int track_preamble(gc_context* ctx, const gc_track_params* p, int nch, const gc_
   ctx->fs = p->sampling_freq;
   int rc = gc_sync_channels(ctx);
   if (rc) return rc;
-  gc_scope_reset(ctx);
-  *max_arms = 1;
+  *scope = LaunchScope();
+  *mix = ChannelMix();
   for (int c = 0; c < nch; ++c) {
     const int ci = init[c].channel;
     if (ci < 0 || ci >= GC_MAX_CHANNELS || !ctx->ch[ci].configured) {
@@ -86,9 +87,10 @@ int track_preamble(gc_context* ctx, const gc_track_params* p, int nch, const gc_
     }
     if ((rc = per_channel(ctx->ch[ci], ci))) return rc;
     if ((rc = validate_track_channel(ctx, p, init[c], who))) return rc;
-    *max_arms = std::max(*max_arms, ctx->ch[ci].arms);
-    gc_scope_add(ctx, ci);
+    gc_scope_add_channel(*scope, ctx->ch[ci]);
+    mix->add(ctx->ch[ci]);
   }
+  gc_scope_set_level(ctx, *scope, *mix, 2);
   return GC_OK;
 }
 
@@ -201,23 +203,21 @@ void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const 
 // this window - more of the record follows - instead of ending that channel (tracking.m:241-245 is the END of the file).
 int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc_channel_init* init, double* out,
                     int32_t* epochs_done, GcTrackResume* r) {
-  int max_arms = 1;
-  bool any_mixed = false, all_mixed_derived = true, any_three_plain = false;
-  int rc = track_preamble(ctx, p, nch, init, out, epochs_done, r, "gc_track", &max_arms, [&](const HostChannel& hcn, int ci) -> int {
+  LaunchScope scope;
+  ChannelMix mix;
+  int rc = track_preamble(ctx, p, nch, init, out, epochs_done, r, "gc_track", &scope, &mix, [&](const HostChannel& hcn, int ci) -> int {
     for (int a = 0; a < hcn.arms; ++a)
       if (!hcn.d_tab[a]) {
         gc_set_error("gc_track: channel %d arm %d has no code table", ci, a);
         return GC_E_STATE;
       }
-    if (hcn.arms == 3 && !gc_channel_is_derived(hcn)) any_three_plain = true;
-    for (int a = 1; a < hcn.arms; ++a)
-      if (hcn.mult[a] != hcn.mult[0]) {  // B1C wide-band / E1 CBOC: exact per-sample kernel, or the lane
-        any_mixed = true;                // kernel's derived-arm instantiation when every such channel allows it
-        if (!gc_channel_is_derived(hcn)) all_mixed_derived = false;
-      }
     return GC_OK;
   });
   if (rc) return rc;
+  const int max_arms = scope.max_arms;
+  // B1C wide-band / E1 CBOC: the exact per-sample kernel, or the lane kernel's derived-arm instantiation when every such channel
+  // allows it (three arms, the third derived, int8 I/Q or Q/I record)
+  const bool any_mixed = mix.any_mixed(), derived = scope.derived;
   // channels that share the device during this call (gc_track_multi): teams are sized for all of them
   const int nch_dev = ctx->concurrent_jobs ? std::max(nch, ctx->concurrent_channels) : nch;
   if ((p->pilot_combine == 4 || p->pilot_combine == 5) && max_arms < 3) {
@@ -233,7 +233,7 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
   const int approx_chunks = (int)(p->code_length / (p->code_freq_basis / p->sampling_freq) / 8.0) + 1;
   // nominal kernel choice (per-epoch blocks are re-checked below): the fast kernel runs one
   // wavefront per workgroup, the generic one four
-  int fast_nominal = (gc_fast_lds_ok(ctx) && !ctx->force_generic) ? 2 : 0;
+  int fast_nominal = (gc_fast_lds_ok(ctx, scope) && !ctx->force_generic) ? 2 : 0;
   for (int c = 0; c < nch && fast_nominal; ++c) {
     gc_block probe;
     std::memset(&probe, 0, sizeof probe);
@@ -241,14 +241,13 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
     probe.code_phase_step = init[c].code_freq * 1.001 / p->sampling_freq;
     fast_nominal = std::min(fast_nominal, gc_block_lowrate_level(ctx, probe));
   }
-  if (any_mixed && all_mixed_derived && !any_three_plain && ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL)
-    fast_nominal = 0;  // derived-arm channels run on the lane kernel
+  if (derived) fast_nominal = 0;  // derived-arm channels run on the lane kernel
   int splits;
   if (fast_nominal) {
     const int chunks_nominal = approx_chunks * 8 / (fast_nominal == 2 ? 16 : 8);
     splits = (8 * ctx->compute_units + nch_dev - 1) / nch_dev;
     splits = std::max(1, std::min(std::min(splits, 32), std::max(1, chunks_nominal / (2 * 64))));
-    if (gc_fast_table_mode(ctx) == 1) splits = std::max(4, std::min(32, (splits / 4) * 4));  // WIDE: 4 waves per workgroup
+    if (gc_fast_table_mode(scope) == 1) splits = gc_wide_splits(splits, 32);  // WIDE: 4 waves per workgroup
   } else {
     splits = gc_lane_splits(ctx, nch, approx_chunks * 8, 32);  // lane kernel: one wave per item, 16 items per workgroup
     if (splits == 1) splits = 16;  // the closed loop always goes through per-item records
@@ -296,10 +295,9 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
   // single-arm R = 1 channels on the transition-mask kernel with one-wave workgroups, any record format (GPS L1 C/A, BDS B1I,
   // GLONASS); everything else keeps launching.
   ctx->last_track_mode = 0;
-  bool persist = poll && !any_mixed && max_arms == 1 && fast_nominal > 0 && gc_fast_table_mode(ctx) == 0 && p->pilot_combine == 0 &&
+  bool persist = poll && !any_mixed && max_arms == 1 && fast_nominal > 0 && gc_fast_table_mode(scope) == 0 && p->pilot_combine == 0 &&
                  p->table_phase_count == 0 && n_epochs > 0 &&
                  !(GC_TUNE_ENV("GC_TRACK_PERSIST") && std::atoi(GC_TUNE_ENV("GC_TRACK_PERSIST")) == 0);
-  const bool i8c_rec = ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL;  // int8 I/Q or Q/I (the derived-arm instantiation's only format)
   for (int c = 0; c < nch && persist; ++c) {
     const HostChannel& hcn = ctx->ch[init[c].channel];
     persist = hcn.arms == 1 && hcn.index_scale == 1.0 && hcn.mult[0] == 1.0 && hcn.window[0] == 0;
@@ -307,8 +305,7 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
   // ... and on the lane kernel's persistent instantiation (corr_lane.hip, host_loop) for one- and two-arm channels of any
   // rate and index scale (GPS L5, BDS B2a / B3I, Galileo E5a / E5b / E1 B+C, BDS B1C narrow-band): member 0's first wave
   // gathers the team's sums, hands them to the host and relays the host's next descriptor
-  const bool derived_nominal = any_mixed && all_mixed_derived && !any_three_plain;  // three arms, the third derived (E1-C CBOC)
-  bool persist_lane = !persist && poll && ((!any_mixed && max_arms <= 2) || (derived_nominal && i8c_rec)) && n_epochs > 0 &&
+  bool persist_lane = !persist && poll && ((!any_mixed && max_arms <= 2) || derived) && n_epochs > 0 &&
                       !(GC_TUNE_ENV("GC_TRACK_PERSIST") && std::atoi(GC_TUNE_ENV("GC_TRACK_PERSIST")) == 0);
   bool share_lane_nominal = true;
   for (int c = 0; c < nch && persist_lane; ++c) {
@@ -421,12 +418,12 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
       a.xcd_swizzle = 0;
       if (persist_lane) {
         a.share_el = 0;
-        a.derived = derived_nominal ? 1 : 0;
-        const int lrc = gc_launch_devloop_lane(ctx, a, (unsigned int)(nch * psplits_dev), max_arms, share_lane_nominal && !derived_nominal, 8);
+        a.derived = derived ? 1 : 0;
+        const int lrc = gc_launch_devloop_lane(ctx, a, scope, (unsigned int)(nch * psplits_dev), share_lane_nominal && !derived, 8);
         if (lrc != GC_OK) e = hipErrorUnknown;
         refused = lrc == GC_E_NOFIT;   // (only a grid that did not fit is retried with smaller teams)
       } else {
-        const int lrc = gc_launch_devloop(ctx, a, (unsigned int)(nch * psplits_dev), fast_nominal == 2, a.share_el != 0);
+        const int lrc = gc_launch_devloop(ctx, a, scope, (unsigned int)(nch * psplits_dev), fast_nominal == 2, a.share_el != 0);
         if (lrc != GC_OK) e = hipErrorUnknown;
         refused = lrc == GC_E_NOFIT;
       }
@@ -612,23 +609,14 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
       ++nb;
     }
     if (nb == 0) break;
-    const bool derived = any_mixed && all_mixed_derived && !any_three_plain && ctx->if_dtype == GC_I8 && ctx->if_layout != GC_REAL;
-    ctx->launch_derived = derived;
-    int fast = derived ? 0 : any_mixed ? -1 : (gc_fast_lds_ok(ctx) && !ctx->force_generic) ? 2 : 0;
-    for (int k = 0; k < nb && fast > 0; ++k) fast = std::min(fast, gc_block_lowrate_level(ctx, blocks[k]));
-    if (ctx->precision == GC_PREC_F64) fast = -1;  // no tagged records: gc_launch_correlator takes corr_f64.hip
-    bool share = true;
-    for (int k = 0; k < nb && share; ++k) share = gc_block_shares_el(ctx, blocks[k]);
-    ctx->scope_share_lane = true;
-    for (int k = 0; k < nb && ctx->scope_share_lane; ++k) ctx->scope_share_lane = gc_block_shares_el_lane(ctx, blocks[k]);
+    gc_scope_set_epoch(ctx, scope, mix, blocks, nb);
     const unsigned int tag = (unsigned int)(e + 1);
-    const bool polled = poll && fast >= 0;
+    const bool polled = gc_epoch_polled(ctx, scope, poll);
     const auto tt0 = std::chrono::steady_clock::now();
     if (persist) {
       for (int k = 0; k < nb; ++k) write_desc(slot[k], e, &blocks[k], 0ull);
     } else {
-      rc = gc_launch_correlator(ctx, blocks, nb, splits, splits == 1 ? partial : nullptr, partial, max_arms, fast, 0,
-                                polled ? tag : 0u, share);
+      rc = gc_launch_correlator(ctx, scope, blocks, nb, splits, splits == 1 ? partial : nullptr, partial, polled ? tag : 0u);
       if (rc) return rc;
     }
     const auto tt1 = std::chrono::steady_clock::now();
@@ -755,9 +743,10 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
     return GC_E_INVALID;
   }
   const bool f64 = ctx && ctx->precision == GC_PREC_F64;  // corr_f64.hip's device loop: every configuration gc_track takes
-  int max_arms = 1;
+  LaunchScope scope;
+  ChannelMix mix;
   bool single_r1 = true, all_derived = true;
-  int rc = track_preamble(ctx, p, nch, init, out, epochs_done, r, "gc_track_device", &max_arms, [&](const HostChannel& hcn, int ci) -> int {
+  int rc = track_preamble(ctx, p, nch, init, out, epochs_done, r, "gc_track_device", &scope, &mix, [&](const HostChannel& hcn, int ci) -> int {
     if (!hcn.d_tab[0]) {
       gc_set_error("gc_track_device: channel %d not configured", ci);
       return GC_E_STATE;
@@ -773,6 +762,7 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
     return GC_OK;
   });
   if (rc) return rc;
+  const int max_arms = scope.max_arms;
   // channels that share the device during this call (gc_track_multi): teams are sized for all of them
   const int nch_dev = ctx->concurrent_jobs ? std::max(nch, ctx->concurrent_channels) : nch;
   // three arms, the third derived from the second: Galileo E1-C CBOC (fold 5), BDS B1C wide-band (fold 4)
@@ -824,7 +814,7 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
   bool any_window = false;
   for (int c = 0; c < nch; ++c)
     for (int a = 0; a < ctx->ch[init[c].channel].arms; ++a) any_window = any_window || ctx->ch[init[c].channel].window[a] != 0;
-  const bool use_fast = single_r1 && lowrate > 0 && p->pilot_combine == 0 && gc_fast_table_mode(ctx) == 0 && !ctx->force_generic && !any_window;
+  const bool use_fast = single_r1 && lowrate > 0 && p->pilot_combine == 0 && gc_fast_table_mode(scope) == 0 && !ctx->force_generic && !any_window;
   int splits, msgs_per_member, lane_waves = gcorr::kLaneWaves;
   bool share_lane = true;
   const int spl = lowrate == 2 ? 16 : 8;
@@ -924,7 +914,7 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
   if (f64)  // one 16-wave workgroup per channel: no team, nothing to halve when the grid does not fit
     rc = gc_launch_devloop_f64(ctx, d_args, nch);
   else
-    rc = use_fast ? gc_launch_devloop(ctx, a, grid, lowrate == 2, share) : gc_launch_devloop_lane(ctx, a, grid, max_arms, share_lane && !cboc, lane_waves);
+    rc = use_fast ? gc_launch_devloop(ctx, a, scope, grid, lowrate == 2, share) : gc_launch_devloop_lane(ctx, a, scope, grid, share_lane && !cboc, lane_waves);
   if (rc == GC_E_NOFIT && splits > 1 && !f64) {
     // the grid does not fit the device whole: the same call again with teams half the size (see gc_track's persistent launch);
     // a structural refusal (no instantiation for these tables / arms) is not retried

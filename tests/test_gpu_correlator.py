@@ -303,6 +303,49 @@ def test_big_periodic_replay_lists_take_the_four_wave_kernels_and_match_the_orac
         assert np.abs(got[sub] - small).max() < 2e-7 * scale
 
 
+def test_replay_launch_does_not_depend_on_what_ran_in_between(engine, l1ca_scene):
+    """gc_replay_launch plans from the scope gc_replay_prepare kept with the list (LaunchScope, gc_internal.h), not from whatever the
+    context's last launch left behind: a prepared list of 2 one-arm channels x 4 epochs of 2 048 samples, then - on the same context -
+    gc_correlate on a three-arm channel with tables more than ten times longer and a 4-epoch gc_track of a two-arm channel, then gc_replay_launch
+    again without a second prepare.  Same kernel, bit-identical sums."""
+    import cu_sdr_collection_amd as P
+    from cu_sdr_collection_amd import _lib as L
+    from cu_sdr_collection_amd.receiver import track_params
+    S, sats, iq = l1ca_scene
+    engine.load_if(iq, fs=S.samplingFreq)
+    rng = np.random.default_rng(91)
+    ca = [P.codes.padded_table(P.codes.generateCAcode(s.prn)) for s in sats[:2]]
+    for k, t in enumerate(ca):
+        engine.set_channel(k, [t])
+    step = 1.023e6 / 18e6
+    descs = [dict(channel=i % 2, n=2048, s0=int(rng.integers(0, 10 ** 6)), rem=float(rng.uniform(0, step)), step=step, d=0.5,
+                  f=20e3 + float(rng.uniform(-5e3, 5e3)), phi=float(rng.uniform(-3, 3))) for i in range(8)]
+    engine.replay_prepare(_blocks(engine, descs))
+    engine.replay_launch()
+    first, kernel = engine.replay_fetch().copy(), engine.last_kernel()
+    for i, d in enumerate(descs):
+        assert np.abs(first[i, 0] - _oracle(iq, d, O.pad_code(O.generate_ca_code(sats[d["channel"]].prn)))).max() < TOL * _scale(iq, d), i
+    # another scope: three arms of 10 402 entries (the replay list's tables have 1 025) at ten times the rate (the lane kernel, other LDS needs, other splits)
+    engine.set_channel(2, [O.pad_code(rng.choice([-1.0, 1.0], size=10400)).astype(np.int8) for _ in range(3)])
+    other = engine.correlate(_blocks(engine, [dict(channel=2, n=9000, s0=4321, rem=0.1, step=10.23e6 / 18e6, d=0.3, f=20e3, phi=0.5)]))
+    assert other[0, :3].any() and engine.last_kernel() == 0 != kernel
+    # ... and a closed loop over a two-arm channel: its scope comes from the channel set and changes with every epoch
+    engine.set_channel(3, [ca[0], ca[1]])
+    ms = S.msToProcess
+    try:
+        S.msToProcess = 4
+        init = L.gc_channel_init(channel=3, prn=sats[0].prn, acquired_freq=S.IF + sats[0].doppler, code_freq=S.codeFreqBasis,
+                                 code_phase=int(np.ceil(sats[0].code_phase_samples)) + 1)
+        _, done, st = engine.track(track_params(S), [init])
+    finally:
+        S.msToProcess = ms
+    assert st == 0 and list(done) == [4]
+    engine.replay_launch()
+    again = engine.replay_fetch()
+    assert engine.last_kernel() == kernel
+    assert first.tobytes() == again.tobytes()
+
+
 def test_big_periodic_replay_with_eight_sample_chunks(engine, monkeypatch):
     """The same for a B1I-rate replica (2.046 Mcps at 18 Msps: 8.8 samples per chip -> 8-sample lane-chunks): four-wave
     kernels with float tables and with int8-pair tables."""

@@ -1,4 +1,4 @@
-"""gc_correlate / replay over the block descriptors validate_blocks accepts, not only the ones a receiver produces.
+"""gc_correlate / replay over the block descriptors gc_scope_from_blocks (csrc/launch_plan.h) accepts, not only the ones a receiver produces.
 
 Every other correlator test feeds blocks of one code period, rem in [0, step), spacing 0.25-0.5, a carrier near the IF and a
 handful of head alignments.  include/gnsscorr.h (gc_block) promises more: any blksize >= 1, any start sample, rem > -1 and
@@ -130,7 +130,7 @@ class Rig:
                                arm_mult=None if set(ch.mult) == {1.0} else ch.mult)
 
     def expected_kernel(self, rec, step):
-        """The kernel a small launch of this rig takes on this record (gnsscorr.hip validate_blocks, gc_correlate; corr_kernel.hip)."""
+        """The kernel a small launch of this rig takes on this record (csrc/launch_plan.h: gc_scope_from_blocks, gc_correlate_splits, gc_plan_launch)."""
         ch = self.chans[0]
         if self.double:
             return 6
