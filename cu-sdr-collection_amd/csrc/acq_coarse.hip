@@ -448,9 +448,11 @@ int ensure_scratch(gc_context* ctx, int n, long long nbh, int nprn, int nbins, i
   s->nbins = nbins;
   s->codes_cap = (size_t)nprn * (size_t)std::max(spc, n);
   const size_t ne = (size_t)n;
+  // tmp is also the intermediate of the code spectra's forward transforms (forward(): nprn of them in one launch) - more than the
+  // search's own nbh where a call has more code arms than bins x hops (a few bins, or one hop and 32 PRNs)
   if (hipMalloc((void**)&s->tw, ne * sizeof(float2)) != hipSuccess ||
       hipMalloc((void**)&s->sig, (size_t)nbh * ne * sizeof(float2)) != hipSuccess ||
-      hipMalloc((void**)&s->tmp, (size_t)nbh * ne * sizeof(float2)) != hipSuccess ||
+      hipMalloc((void**)&s->tmp, (size_t)std::max<long long>(nbh, nprn) * ne * sizeof(float2)) != hipSuccess ||
       hipMalloc((void**)&s->codespec, (size_t)nprn * ne * sizeof(float2)) != hipSuccess ||
       hipMalloc((void**)&s->results, (size_t)nbins * ne * sizeof(float)) != hipSuccess ||
       hipMalloc((void**)&s->codes, (size_t)nprn * (size_t)std::max(spc, n)) != hipSuccess ||
@@ -565,8 +567,40 @@ extern "C" int gc_acquire_coarse_multi(gc_context* ctx, const gc_acq_params* p, 
   return gc_acquire_coarse_offsets(ctx, p, nprn, narms, sampled_codes, nullptr, out);
 }
 
+// One row's whole float32 surface next to its result (gc_debug_acq_surface): where the search's sums go when a test asks for them
+struct SurfaceOut {
+  float* out;
+  long long cap;  // floats `out` holds
+  int nbins, n;   // what the search had: bins and transform points per bin (written whatever cap is)
+};
+static int coarse_search(gc_context* ctx, const gc_acq_params* p, int nprn, int narms, const int8_t* sampled_codes, const double* freq_offset,
+                         gc_acq_result* out, SurfaceOut* surface);
+
 extern "C" int gc_acquire_coarse_offsets(gc_context* ctx, const gc_acq_params* p, int nprn, int narms,
                                          const int8_t* sampled_codes, const double* freq_offset, gc_acq_result* out) {
+  return coarse_search(ctx, p, nprn, narms, sampled_codes, freq_offset, out, nullptr);
+}
+
+// Test hook: gc_acquire_coarse_multi for ONE PRN (codes: int8 [narms][code samples]), then the PRN searched once more the way the guard's
+// slow path searches it - every bin's sums written (guard_resolve's rerun) - and those nbins x n float32 sums copied out, out[bin * n + lag].
+// *nbins, *n: the search's bins and transform points (more than the block where the transform is padded: the lags from the block
+// length on mean nothing).  out_cap < nbins * n floats: GC_E_RANGE with the two sizes set and nothing copied.
+extern "C" int gc_debug_acq_surface(gc_context* ctx, const gc_acq_params* p, int narms, const int8_t* codes, float* out, int64_t out_cap, int32_t* nbins,
+                                    int32_t* n) {
+  if (!out || !nbins || !n || out_cap < 0) {
+    gc_set_error("gc_debug_acq_surface: bad arguments");
+    return GC_E_INVALID;
+  }
+  SurfaceOut so{out, (long long)out_cap, 0, 0};
+  gc_acq_result res;
+  const int rc = coarse_search(ctx, p, 1, narms, codes, nullptr, &res, &so);
+  *nbins = so.nbins;
+  *n = so.n;
+  return rc;
+}
+
+static int coarse_search(gc_context* ctx, const gc_acq_params* p, int nprn, int narms, const int8_t* sampled_codes, const double* freq_offset,
+                         gc_acq_result* out, SurfaceOut* surface) {
   if (!ctx || !p || nprn <= 0 || narms < 1 || narms > 4 || !sampled_codes || !out) {
     gc_set_error("gc_acquire_coarse: bad arguments");
     return GC_E_INVALID;
@@ -638,6 +672,14 @@ extern "C" int gc_acquire_coarse_offsets(gc_context* ctx, const gc_acq_params* p
   if (rc) return rc;
   s->shift.n = 0;  // the signal spectra of a circshift search, if any, are overwritten below
   const Plan& pl = s->plan;
+  if (surface) {  // the sizes first: a caller that does not know them asks with a buffer too small and pays for no search
+    surface->nbins = nbins;
+    surface->n = pl.n;
+    if (surface->cap < (long long)nbins * pl.n) {
+      gc_set_error("gc_debug_acq_surface: %d bins x %d points do not fit %lld floats", nbins, pl.n, surface->cap);
+      return GC_E_RANGE;
+    }
+  }
 
   // sigPower = sqrt(var(x(1:spc)) * spc), var normalised by N-1 (acquisition.m:151)
   GC_HIP(hipMemsetAsync(s->sums, 0, 16 * sizeof(long long), ctx->stream));
@@ -1002,6 +1044,18 @@ extern "C" int gc_acquire_coarse_offsets(gc_context* ctx, const gc_acq_params* p
     out[ip].peak = peak;
     out[ip].peak_metric = peak / sig_power / H;  // :200
     out[ip].coarse_freq = p->intermediate_freq + (freq_offset ? freq_offset[ip] : 0.0) + p->search_band - p->search_step * harg[0];
+  }
+  if (surface) {
+    if (fused) {
+      gc_set_error("gc_debug_acq_surface: the fused search kernel writes no sums");
+      return GC_E_UNSUPPORTED;
+    }
+    s->lane = 0;
+    s->nlanes = 1;
+    rc = run_item(0, 0, nbins, false);
+    if (rc) return rc;
+    GC_HIP(hipMemcpyAsync(surface->out, s->results, (size_t)nbins * pl.n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
   }
   return GC_OK;
 }

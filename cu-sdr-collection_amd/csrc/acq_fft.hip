@@ -440,7 +440,7 @@ __global__ __launch_bounds__(kFftThreads) void fft_pass_kernel(const PassArgs a)
       for (int i = tid; i < C * TW2; i += kFftThreads) {
         const int c = fdiv_small(i, inv_tw2), j = i - c * TW2;
         const int v = v0 + c;
-        if (v < a.nvec) {
+        if (v < a.nvec && (j < EH || j - EH < L)) {  // (vectors shorter than 16: the entries from L on are never used, and v * 15 may lie past the table's n entries)
           float2 w = a.tw[j < EH ? __mul24(v, j << 4) : __mul24(v, j - EH)];  // v * e < n for every e < L
           w.y *= sign;
           tw2[i] = w;
@@ -1627,6 +1627,27 @@ extern "C" int gc_debug_fft(gc_context* ctx, int n, int nbatch, const float* in,
   for (int b = 0; b < nbatch; ++b)
     for (int k1 = 0; k1 < pl.n1; ++k1)
       for (int k2 = 0; k2 < pl.n2; ++k2) o[(size_t)b * n + k1 + (size_t)pl.n1 * k2] = h[(size_t)b * n + (size_t)k1 * pl.n2 + k2];
+  return GC_OK;
+}
+
+// Test hook: the plan make_plan gives a length - the split n = n1 x n2, each pass's radices in stage order and the tile widths
+// choose_cols gives its two passes (columns: vectors of n1, element stride n2; rows: vectors of n2, contiguous).  Host code only:
+// no context, no HIP call.  GC_E_UNSUPPORTED where make_plan refuses the length.
+extern "C" int gc_debug_fft_plan(int n, int* n1, int* n2, int* rad1, int* nrad1, int* rad2, int* nrad2, int* cols1, int* cols2) {
+  if (n <= 1 || !n1 || !n2 || !rad1 || !nrad1 || !rad2 || !nrad2 || !cols1 || !cols2) return GC_E_INVALID;
+  Plan pl;
+  if (!make_plan(n, &pl)) {
+    gc_set_error("acquisition: FFT size %d is not of the form 2^a 3^b 5^c (or its factors are too large)", n);
+    return GC_E_UNSUPPORTED;
+  }
+  *n1 = pl.n1;
+  *n2 = pl.n2;
+  *nrad1 = pl.p1.nrad;
+  *nrad2 = pl.p2.nrad;
+  for (int i = 0; i < pl.p1.nrad; ++i) rad1[i] = pl.p1.rad[i];  // (at most kMaxRadices = 12 each)
+  for (int i = 0; i < pl.p2.nrad; ++i) rad2[i] = pl.p2.rad[i];
+  *cols1 = choose_cols(pl.n1, pl.n2);
+  *cols2 = choose_cols(pl.n2, 1);
   return GC_OK;
 }
 

@@ -541,6 +541,34 @@ class Engine:
                                        out.ctypes.data_as(C.c_void_p), int(inverse)))
         return out
 
+    def debug_acq_surface(self, params: L.gc_acq_params, codes: np.ndarray):
+        """gc_debug_acq_surface (test hook): codes int8 [spc] or [narms, spc] of ONE PRN -> the search's float32 surface
+        [nbins, n] as the guard's slow path writes it.  n is the transform length: the block's, or a longer one where the
+        search runs inside a padded transform (only the block's lags count then)."""
+        c8 = np.ascontiguousarray(codes, dtype=np.int8)
+        if c8.ndim == 1:
+            c8 = c8[None, :]
+        nbins, n = C.c_int32(0), C.c_int32(0)
+        out = np.empty(1, dtype=np.float32)
+        for _ in range(2):   # the first call only tells the sizes (GC_E_RANGE before anything is searched)
+            rc = self._lib.gc_debug_acq_surface(self._ctx, C.byref(params), c8.shape[0], c8.ctypes.data_as(C.c_void_p),
+                                                out.ctypes.data_as(C.POINTER(C.c_float)), out.shape[0], C.byref(nbins), C.byref(n))
+            if rc != L.GC_E_RANGE or nbins.value * n.value <= out.shape[0]:
+                break
+            out = np.empty(nbins.value * n.value, dtype=np.float32)
+        L.check(rc)
+        return out[:nbins.value * n.value].reshape(nbins.value, n.value)
+
+    @staticmethod
+    def debug_fft_plan(n: int):
+        """gc_debug_fft_plan (test hook, host code only): {"n1", "n2", "rad1", "rad2", "cols1", "cols2"} of an n-point transform -
+        the columns pass (vectors of n1, element stride n2) and the rows pass (vectors of n2), their radices in stage order and
+        tile widths.  Raises GnssCorrError (GC_E_UNSUPPORTED) where the planner refuses the length."""
+        n1, n2, k1, k2, c1, c2 = (C.c_int(0) for _ in range(6))
+        r1, r2 = (C.c_int * 12)(), (C.c_int * 12)()
+        L.check(L.load().gc_debug_fft_plan(int(n), C.byref(n1), C.byref(n2), r1, C.byref(k1), r2, C.byref(k2), C.byref(c1), C.byref(c2)))
+        return {"n1": n1.value, "n2": n2.value, "rad1": list(r1[:k1.value]), "rad2": list(r2[:k2.value]), "cols1": c1.value, "cols2": c2.value}
+
     def acquire_fine_l1ca(self, params: L.gc_acq_params, code: np.ndarray, code_phase: int,
                           coarse_freq: float) -> float:
         c8 = np.ascontiguousarray(code, dtype=np.int8)

@@ -587,6 +587,16 @@ int gc_debug_wave_transpose_sum(gc_context* ctx, int k, const float* in, float* 
 /* Test hook: the library's four-step mixed-radix FFT on `nbatch` host sequences of n complex64
  * values (n of the form 2^a 3^b 5^c); output in natural order, unnormalised. */
 int gc_debug_fft(gc_context* ctx, int n, int nbatch, const float* in, float* out, int inverse);
+/* Test hook (host code only, no context): the plan of an n-point transform - n = n1 x n2, the radices of the columns pass (vectors of
+ * n1, element stride n2) and of the rows pass (vectors of n2) in stage order (at most 12 each) and the two passes' tile widths (vectors
+ * per workgroup).  GC_E_UNSUPPORTED: no plan for this length (a prime factor above 5, or n2 > 2048). */
+int gc_debug_fft_plan(int n, int* n1, int* n2, int* rad1, int* nrad1, int* rad2, int* nrad2, int* cols1, int* cols2);
+/* Test hook: gc_acquire_coarse_multi for ONE PRN (codes: int8 [narms][code samples]), then that PRN's whole float32 search surface -
+ * the PRN searched again the way the float64 guard's slow path does it, every bin's sums written - as out[bin * n + lag].  *nbins, *n:
+ * the search's bins and transform points (a padded transform has more points than the block; only the block's lags count).
+ * GC_E_RANGE with both sizes set, before anything is searched, when out_cap (floats) is less than nbins * n. */
+int gc_debug_acq_surface(gc_context* ctx, const gc_acq_params* p, int narms, const int8_t* codes, float* out, int64_t out_cap, int32_t* nbins,
+                         int32_t* n);
 
 /* The float64 guard of the last search of this context (gc_acquire_coarse*, gc_acq_shift_search_batch): the searches transform in
  * float32, the reference decides in float64 (acquisition.m:196-206 max(max(results)), peakMetric > acqThreshold; BDS/B1I acquisition.m:
