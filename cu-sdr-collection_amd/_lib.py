@@ -15,6 +15,7 @@ GC_PREC_F32, GC_PREC_F64 = 0, 1   # gc_set_precision
 GC_MAX_ARMS = 3
 GC_SYNC_ZERO_IS_PLUS = 1   # gc_sync_xcorr flag
 GC_OUT_STRIDE = 6 * GC_MAX_ARMS
+GC_BANK_MAX_TAPS = 64      # gc_correlate_bank
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -138,6 +139,7 @@ SYMBOLS = {
     "gc_set_precision": (C.c_int, [_P, C.c_int]),
     "gc_get_precision": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "gc_correlate": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.POINTER(C.c_double)]),
+    "gc_correlate_bank": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gc_replay_prepare": (C.c_int, [_P, C.c_int64, C.POINTER(gc_block)]),
     "gc_replay_launch": (C.c_int, [_P]),
     "gc_replay_fetch": (C.c_int, [_P, C.POINTER(C.c_double)]),

@@ -35,6 +35,7 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                "corr_lane.hip@GC_LANE_PART=0", "corr_lane.hip@GC_LANE_PART=1", "corr_lane.hip@GC_LANE_PART=2", "corr_lane.hip@GC_LANE_PART=3",
                "track.hip", "multi.hip", "stream.hip",
                "corr_f64.hip",    # gc_set_precision(GC_PREC_F64): the float64 per-sample kernel and its device loop
+               "corr_bank.hip",   # gc_correlate_bank: a block's correlation function at up to 64 taps from one pass over its samples
                # the acquisition, one translation unit per part of the search (acq_internal.h is what they share)
                "acq_fft.hip", "acq_coarse.hip", "acq_shift.hip", "acq_fine.hip", "acq_cond.hip", "acq_guard.hip", "navsync.hip"]
 
@@ -60,7 +61,7 @@ FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-f
 # header compiled under the default -ffp-contract=fast, so the backend fuses them into v_fma_f64 (one rounding
 # instead of two: wrong table index at exact ties).  These translation units therefore forbid contraction;
 # wanted FMAs are written as fmaf() / fma().
-NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip"}
+NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip", "corr_bank.hip"}
 
 
 def _hipcc() -> str:

@@ -220,6 +220,17 @@ class Engine:
         L.check(self._lib.gc_correlate(self._ctx, n, blocks, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
+    def correlate_bank(self, blocks, offsets) -> np.ndarray:
+        """gc_correlate_bank: every block's correlation function at the code offsets `offsets` (chips, positive = late; at most
+        GC_BANK_MAX_TAPS of them, any order), the tables read periodically; el_spacing of the blocks is ignored.
+        Returns complex128 [nblocks, GC_MAX_ARMS, ntaps] = I + 1j * Q, unused arms zero."""
+        n = len(blocks)
+        off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        out = np.zeros((n, L.GC_MAX_ARMS, off.shape[0], 2))
+        L.check(self._lib.gc_correlate_bank(self._ctx, n, blocks, off.shape[0], off.ctypes.data_as(C.POINTER(C.c_double)),
+                                            out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[..., 0] + 1j * out[..., 1]
+
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition
         (corr_multi.hip), 5 hybrid for channels with a derived six-fold arm (corr_cboc.hip), 6 float64 (corr_f64.hip), -1 mixed

@@ -380,6 +380,58 @@ def tracking(fid: Engine, channel, settings, signal: str = "GPS_L1CA", device_lo
     return _tracking_finish(job, fields, done, status)
 
 
+BANK_CHANNEL = 255   # the engine's channel slot correlation_function() configures (the last one: tracking() fills from 0)
+
+
+def correlation_function(fid: Engine, trackResults_k, channel_k, settings, offsets, signal: str = "GPS_L1CA", epochs=None):
+    """The correlation function a tracked channel saw: R(o) at the code offsets `offsets` (chips, positive = late) on the blocks the
+    loop cut, rebuilt from the state tracking.m records per epoch (absoluteSample, remCodePhase, codeFreq, carrFreq, remCarrPhase:
+    tracking.m:212-216,249,277,314,332) - where on a BOC(1,1) peak the channel sits, what multipath does to the peak, a
+    discriminator's S-curve at another spacing.  One gc_correlate_bank call (include/gnsscorr.h).
+
+    trackResults_k, channel_k: one channel's entry of what tracking() returned / was given; the record must be loaded in `fid`.
+    epochs: indices of the epochs to evaluate (None: every epoch the channel completed - a channel that stopped early on a short
+    read, tracking.m:241-245, or was never tracked keeps codeFreq = inf in the epochs it did not reach: those are left out).
+    Returns complex128 [n_epochs, arms, ntaps], arms as the signal's tables (data, pilot, ...).
+    GPS L2C with its pilot (windowed CL table) is refused by the library: GnssCorrError with status GC_E_UNSUPPORTED.
+    Side effects on `fid`: the signal's tables go to the engine's LAST channel slot (BANK_CHANNEL = 255 - whatever a caller keeps
+    there is replaced; tracking() fills slots from 0) and the sampling frequency is set to settings.samplingFreq."""
+    from . import signals
+    spec = signals.SIGNALS[signal]
+    sat = getattr(channel_k, spec.id_field, trackResults_k.PRN)                       # as _tracking_prepare: 'K' for GLONASS
+    tables = spec.tables(sat, settings)
+    fid.set_channel(BANK_CHANNEL, tables, index_scale=spec.index_scale, arm_mult=spec.arm_mult, windows=spec.windows)
+    fid.set_sampling_freq(settings.samplingFreq)
+    pos_all = np.asarray(trackResults_k.absoluteSample, dtype=np.float64)
+    if epochs is None:
+        # epochs never reached keep codeFreq = remCodePhase = inf and absoluteSample = 0 (tracking.m:47-86)
+        epochs = np.nonzero(np.isfinite(np.asarray(trackResults_k.codeFreq, dtype=np.float64)) &
+                            np.isfinite(np.asarray(trackResults_k.remCodePhase, dtype=np.float64)))[0]
+    epochs = np.atleast_1d(np.asarray(epochs, dtype=np.int64))
+    blocks = fid.make_blocks(len(epochs))
+    fs = settings.samplingFreq
+    for n, e in enumerate(epochs):
+        b = blocks[n]
+        step = float(trackResults_k.codeFreq[e]) / fs
+        rem = float(trackResults_k.remCodePhase[e])
+        pos = float(pos_all[e])
+        length = settings.codeLength
+        if spec.doubled_code:
+            # GPS L2C records in single-code units with the position pushed back by the remainder (GPS_L2C tracking.m:223,250,376,382-383);
+            # with pilotTRKflag = 0 the channel has the CM table alone, no window, and the library takes it
+            step, rem, length = 2 * step, 2 * rem, 2 * settings.codeLength
+            pos = float(np.rint(pos - 1 + rem / step))
+        b.channel = BANK_CHANNEL
+        b.first_sample = int(pos)
+        b.rem_code_phase = rem
+        b.code_phase_step = step
+        b.blksize = int(math.ceil((length - rem) / step))                                      # tracking.m:219-222
+        b.el_spacing = 0.0
+        b.carr_freq = float(trackResults_k.carrFreq[e])
+        b.rem_carr_phase = float(trackResults_k.remCarrPhase[e])
+    return fid.correlate_bank(blocks, offsets)[:, :len(tables), :]
+
+
 def tracking_file(fid: Engine, path: str, channel, settings, window_samples: int, signal: str = "GPS_L1CA", pilot_fields: str | None = None,
                   precision: str | None = None, device_loop: bool = False):
     """tracking(fid, channel, settings) on a record FILE that need not fit the device: at most 2 * window_samples samples are

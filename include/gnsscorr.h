@@ -159,6 +159,22 @@ int gc_set_sampling_freq(gc_context* ctx, double fs);
 #define GC_OUT_STRIDE (6 * GC_MAX_ARMS)
 int gc_correlate(gc_context* ctx, int nblocks, const gc_block* blocks, double* out);
 
+/* The correlation function of every block at `ntaps` code offsets instead of three (csrc/corr_bank.hip): tap j correlates with the
+ * replica ramp ((rem + o_j)*R) : (step*R) : ((((N-1)*step + rem) + o_j)*R), o_j = tap_offsets[j] chips, positive = late
+ * (tracking.m:263-270; o = -d, 0, +d are the early, prompt and late ramps bit for bit), carrier and sums as gc_correlate.
+ * The padded table of n entries is read PERIODICALLY - index p = ceil(t*m_a), 0-based as in gc_correlate (MATLAB's p + 1), reads entry 1 + mod(p - 1, n - 2) - so
+ * offsets of several chips, negative phases and blocks longer than a code period are legal.  el_spacing is ignored.
+ * Synchronous, float32 kernels, bitwise reproducible; the library may walk the list in sub-batches of blocks.
+ * Accepted: what gc_correlate asks of a descriptor without its three conditions on el_spacing and the table's end, and instead
+ *   1 <= ntaps <= GC_BANK_MAX_TAPS, finite offsets (any order, duplicates allowed) with |o_j| * R * m_a < n_a - 2 for every arm,
+ *   2^-16 <= code_phase_step * R * max_a(m_a) <= 1 (at most one table entry per sample), every ramp index within int32.
+ * GC_E_INVALID also for table_offset != 0 and for a table whose pads are not its period (tab[0] != tab[n-2] or tab[n-1] != tab[1]);
+ * GC_E_UNSUPPORTED for a channel with a code window (gc_set_code_window), a step above one entry per sample, and under
+ * GC_PREC_F64; GC_E_RANGE / GC_E_STATE as gc_correlate.  Nothing is computed and `out` is not written on any error.
+ * out[((b * GC_MAX_ARMS + arm) * ntaps + j) * 2 + {0: I, 1: Q}], unused arms zero. */
+#define GC_BANK_MAX_TAPS 64
+int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, double* out);
+
 /* Replay (batched, open-loop) mode: descriptors stay resident in HBM so that the timed
  * region contains only kernel work (SURVEY.md §7 hard part 1a). */
 int gc_replay_prepare(gc_context* ctx, int64_t nblocks, const gc_block* blocks);

@@ -17,6 +17,8 @@
  *          gnsscorr_mex('load_if', h, int8_or_int16_vector, fileType, samplingFreq)
  *          gnsscorr_mex('set_channel', h, channelIdx0, {paddedCode1, ...}, indexScale)
  *   sums = gnsscorr_mex('correlate', h, blocks)      % blocks: 8 x nblocks double, see below
+ *   R    = gnsscorr_mex('correlate_bank', h, blocks, offsets)   % the blocks' correlation function at the code offsets `offsets` (chips,
+ *          late positive; gc_correlate_bank): 2 x ntaps x (3*nblocks), rows I, Q; reshape(R, 2, ntaps, 3, []) is (I|Q, tap, arm, block)
  *   [trk, epochs, status] = gnsscorr_mex('track', h, params_struct, channels)   % channels: 5 x nch
  *   res  = gnsscorr_mex('acquire_coarse', h, acq_struct, sampledCodes)          % int8 spc x nprn
  *   f    = gnsscorr_mex('acquire_fine_l1ca', h, acq_struct, caCode, codePhase, coarseFreq)
@@ -139,6 +141,28 @@ static gc_channel_init* channel_inits_from(const mxArray* a, int* nch_out) {
   return init;
 }
 
+/* blocks: 8 x nblocks, rows = channel, first_sample (0-based), blksize, remCodePhase, codePhaseStep, earlyLateSpc, carrFreq,
+ * remCarrPhase - the quantities of tracking.m:212-222,249,277 ('correlate', 'correlate_bank') */
+static gc_block* blocks_from(const mxArray* a, int* n_out) {
+  if (mxGetM(a) != 8) mexErrMsgIdAndTxt("gnsscorr:usage", "blocks must be 8 x nblocks");
+  const double* b = mxGetDoubles(a);
+  const int n = (int)mxGetN(a);
+  gc_block* blk = (gc_block*)mxCalloc((size_t)(n > 0 ? n : 1), sizeof(gc_block));
+  for (int i = 0; i < n; ++i) {
+    const double* r = b + 8 * i;
+    blk[i].channel = (int32_t)r[0];
+    blk[i].first_sample = (int64_t)r[1];
+    blk[i].blksize = (int32_t)r[2];
+    blk[i].rem_code_phase = r[3];
+    blk[i].code_phase_step = r[4];
+    blk[i].el_spacing = r[5];
+    blk[i].carr_freq = r[6];
+    blk[i].rem_carr_phase = r[7];
+  }
+  *n_out = n;
+  return blk;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   char cmd[32];
   if (nrhs < 1 || mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("gnsscorr:usage", "first argument: command string");
@@ -216,28 +240,26 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (gc_set_code_window(c, ch, a, (int)mxGetDoubles(prhs[6])[a])) fail("gc_set_code_window");
     }
   } else if (!strcmp(cmd, "correlate")) {
-    /* blocks rows: channel, first_sample (0-based), blksize, remCodePhase, codePhaseStep,
-     * earlyLateSpc, carrFreq, remCarrPhase — the quantities of tracking.m:212-222,249,277 */
-    const double* b = mxGetDoubles(prhs[2]);
-    int n = (int)mxGetN(prhs[2]);
-    if (mxGetM(prhs[2]) != 8) mexErrMsgIdAndTxt("gnsscorr:usage", "blocks must be 8 x nblocks");
-    gc_block* blk = (gc_block*)mxCalloc((size_t)n, sizeof(gc_block));
-    for (int i = 0; i < n; ++i) {
-      const double* r = b + 8 * i;
-      blk[i].channel = (int32_t)r[0];
-      blk[i].first_sample = (int64_t)r[1];
-      blk[i].blksize = (int32_t)r[2];
-      blk[i].rem_code_phase = r[3];
-      blk[i].code_phase_step = r[4];
-      blk[i].el_spacing = r[5];
-      blk[i].carr_freq = r[6];
-      blk[i].rem_carr_phase = r[7];
-    }
+    int n = 0;
+    gc_block* blk = blocks_from(prhs[2], &n);
     plhs[0] = mxCreateDoubleMatrix(GC_OUT_STRIDE, (mwSize)n, mxREAL); /* rows: I_E Q_E I_P Q_P I_L Q_L per arm */
     int rc = gc_correlate(handle(prhs[1]), n, blk, mxGetDoubles(plhs[0]));
     mxFree(blk);
     if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
     if (rc) fail("gc_correlate");
+  } else if (!strcmp(cmd, "correlate_bank")) {
+    /* blocks as for 'correlate' (the earlyLateSpc row is ignored), offsets: the taps' code offsets in chips.  The result is
+     * gc_correlate_bank's `out` as it lies in memory: (I|Q, tap, arm, block) with GC_MAX_ARMS arms per block, the last two folded. */
+    if (nrhs < 4 || !mxIsDouble(prhs[3])) mexErrMsgIdAndTxt("gnsscorr:usage", "correlate_bank: h, blocks 8 x nblocks, offsets");
+    int n = 0;
+    gc_block* blk = blocks_from(prhs[2], &n);
+    int ntaps = (int)mxGetNumberOfElements(prhs[3]);
+    const mwSize dims[3] = {2, (mwSize)ntaps, (mwSize)GC_MAX_ARMS * (mwSize)n};
+    plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    int rc = gc_correlate_bank(handle(prhs[1]), n, blk, ntaps, mxGetDoubles(prhs[3]), mxGetDoubles(plhs[0]));
+    mxFree(blk);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
+    if (rc) fail("gc_correlate_bank");
   } else if (!strcmp(cmd, "track") || !strcmp(cmd, "track_device") || !strcmp(cmd, "track_file") || !strcmp(cmd, "track_file_device")) {
     /* [trk, epochs, status] = gnsscorr_mex('track', h, p, chanTable)
        [trk, epochs, status] = gnsscorr_mex('track_file', h, p, chanTable, fileName, windowSamples, dataType, fileType[, 'QI']):
