@@ -148,26 +148,57 @@ __global__ void sigpower_kernel(const int8_t* __restrict__ x, long long first, i
   atomicAdd((unsigned long long*)&out3[2], (unsigned long long)s2);
 }
 
-// the same sums for the conditioned (complex float) signal: one workgroup, fixed summation order, float64
+// The conditioned (complex float) signal: one workgroup, fixed summation order, float64, two passes - the sums, then the squared
+// distances from the mean those sums give: out3 = {sum re, sum im, sum |x - mean|^2}.  (sum |x|^2 - n |mean|^2 cancels: a strong DC
+// under a weak signal loses the variance's low digits.)
 __global__ __launch_bounds__(1024) void sigpower_f32_kernel(const float2* __restrict__ x, long long first, int n, double* out3) {
-  double si = 0.0, sq = 0.0, s2 = 0.0;
+  __shared__ double red[2][1024];
+  auto reduce = [&](double a, double b) {
+    red[0][threadIdx.x] = a;
+    red[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int off = 512; off > 0; off >>= 1) {
+      if ((int)threadIdx.x < off)
+        for (int k = 0; k < 2; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
+      __syncthreads();
+    }
+  };
+  double si = 0.0, sq = 0.0;
   for (int i = threadIdx.x; i < n; i += 1024) {
     const float2 z = x[first + i];
     si += (double)z.x;
     sq += (double)z.y;
-    s2 += (double)z.x * (double)z.x + (double)z.y * (double)z.y;
   }
-  __shared__ double red[3][1024];
-  red[0][threadIdx.x] = si;
-  red[1][threadIdx.x] = sq;
-  red[2][threadIdx.x] = s2;
-  __syncthreads();
-  for (int off = 512; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
+  reduce(si, sq);
+  si = red[0][0];
+  sq = red[1][0];
+  __syncthreads();  // every thread has read the sums before the second reduction overwrites them
+  const double mr = si / (double)n, mi = sq / (double)n;
+  double s2 = 0.0;
+  for (int i = threadIdx.x; i < n; i += 1024) {
+    const float2 z = x[first + i];
+    const double dr = (double)z.x - mr, dq = (double)z.y - mi;
+    s2 += dr * dr + dq * dq;
   }
-  if (threadIdx.x < 3) out3[threadIdx.x] = red[threadIdx.x][0];
+  reduce(s2, 0.0);
+  if (threadIdx.x == 0) {
+    out3[0] = si;
+    out3[1] = sq;
+    out3[2] = red[0][0];
+  }
+}
+
+// var(x), normalised by n - 1, from what the two kernels above leave.  The int8 record: n*s2 - si^2 - sq^2 formed in integers (up to
+// 2^77: __int128), converted once and divided once - the float64 form (s2 - n |mean|^2) / (n - 1) cancels (100 000 samples of
+// 127 - 128i with seven of them 126 - 128i: 2.7e-8 relative).  The conditioned signal: the second pass' sum of squared distances.
+static double var_from_sums(const long long hs[3], long long n, bool cond) {
+  if (cond) {
+    double d[3];
+    std::memcpy(d, hs, sizeof d);  // the float kernel wrote doubles
+    return d[2] / (double)(n - 1);
+  }
+  const __int128 num = (__int128)n * hs[2] - (__int128)hs[0] * hs[0] - (__int128)hs[1] * hs[1];
+  return (double)num / (double)(n * (n - 1));
 }
 
 // One workgroup per row: maximum and its first position (MATLAB's max returns the first maximum).
@@ -701,12 +732,7 @@ static int coarse_search(gc_context* ctx, const gc_acq_params* p, int nprn, int 
   const char* lane_streams_env = GC_TUNE_ENV("GC_ACQ_LANE_STREAMS");
   AcqStreams* const shared = (lane_streams_env && std::strcmp(lane_streams_env, "own") == 0) ? nullptr : acq_streams(ctx->device);
   if (shared) ctx->stream = shared->main;
-  double sum3[3];
-  if (cond) std::memcpy(sum3, hs, sizeof sum3);  // the float kernel wrote doubles
-  else for (int k = 0; k < 3; ++k) sum3[k] = (double)hs[k];
-  const double mr = sum3[0] / cl, mi = sum3[1] / cl;
-  const double var = (sum3[2] - cl * (mr * mr + mi * mi)) / (cl - 1);
-  const double sig_power = std::sqrt(var * cl);
+  const double sig_power = std::sqrt(var_from_sums(hs, cl, cond) * cl);
 
   // signal spectra for every (bin, hop)
   PassArgs base;
@@ -1099,13 +1125,12 @@ extern "C" int gc_acq_signal_stats(gc_context* ctx, int64_t first_sample, int64_
   long long hs[3];
   GC_HIP(hipMemcpyAsync(hs, b.p, sizeof hs, hipMemcpyDeviceToHost, ctx->stream));
   GC_HIP(hipStreamSynchronize(ctx->stream));
-  double s3[3];
-  if (cond) std::memcpy(s3, hs, sizeof s3);
-  else for (int k = 0; k < 3; ++k) s3[k] = (double)hs[k];
-  const double mr = s3[0] / (double)n, mi = s3[1] / (double)n;
-  *mean_re = mr;
-  *mean_im = mi;
-  *var = (s3[2] - (double)n * (mr * mr + mi * mi)) / (double)(n - 1);
+  double s2[2];
+  if (cond) std::memcpy(s2, hs, sizeof s2);
+  else for (int k = 0; k < 2; ++k) s2[k] = (double)hs[k];
+  *mean_re = s2[0] / (double)n;
+  *mean_im = s2[1] / (double)n;
+  *var = var_from_sums(hs, n, cond);
   return GC_OK;
 }
 

@@ -161,6 +161,10 @@ static int fine_sums_enqueue(gc_context* ctx, const gc_fine_params* p, int ndet,
     gc_set_error("gc_acquire_fine_sums: bad arguments");
     return GC_E_INVALID;
   }
+  if (p->index_offset < 0) {  // fmod of a negative index is negative: the kernel would read in front of the code table
+    gc_set_error("gc_acquire_fine_sums: index_offset %d is negative (0: codeValueIndex over 0:K*spc-1, 1: over 1:K*spc)", p->index_offset);
+    return GC_E_INVALID;
+  }
   const bool cond = p->source == GC_ACQ_SOURCE_CONDITIONED;
   if (cond) {
     if (ctx->acq_cond_n <= 0) {

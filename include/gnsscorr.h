@@ -486,14 +486,17 @@ typedef struct gc_fine_params {
   int32_t ncodes;            /* code periods (40 L1CA, 20 L5/B2a, 100 E5a) */
   int32_t nbins;
   int32_t code_len;          /* settings.codeLength */
-  int32_t index_offset;      /* 0: codeValueIndex over (0:K*spc-1) (L1CA :210); 1: over (1:K*spc) (L5 :231) */
+  int32_t index_offset;      /* 0: codeValueIndex over (0:K*spc-1) (L1CA :210); 1: over (1:K*spc) (L5 :231); negative:
+                                GC_E_INVALID (the index would fall in front of the table) */
   int32_t source;            /* as gc_acq_params.source */
   double dc_re, dc_im;       /* subtracted from every sample first: sig - mean(sig), GPS_L2C acquisition.m:144 (0: nothing) */
 } gc_fine_params;
 
 /* mean(x) and var(x) (MATLAB's: normalised by n - 1, of a complex vector) of the n samples from first_sample of the IF record
  * or the conditioned signal (`source` as in gc_acq_params): sigPower = sqrt(var * n) of BDS/B1C acquisition.m:138, the mean
- * of GPS_L2C acquisition.m:144.  Exact integer sums for the int8 record. */
+ * of GPS_L2C acquisition.m:144.  The int8 record: exact integer sums, the mean one division of them, the variance the integer
+ * n*sum|x|^2 - |sum x|^2 divided once by n*(n - 1) - a few ulp whatever the DC (the searches' sigPower is formed the same way).
+ * The conditioned signal: float64 sums in a fixed order, the variance from a second pass over the distances from the mean. */
 int gc_acq_signal_stats(gc_context* ctx, int64_t first_sample, int64_t n, int32_t source, double* mean_re, double* mean_im,
                         double* var);
 
