@@ -16,6 +16,7 @@ GC_MAX_ARMS = 3
 GC_SYNC_ZERO_IS_PLUS = 1   # gc_sync_xcorr flag
 GC_OUT_STRIDE = 6 * GC_MAX_ARMS
 GC_BANK_MAX_TAPS = 64      # gc_correlate_bank
+GC_DDM_MAX_FREQS = 64      # gc_correlate_ddm
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -140,6 +141,8 @@ SYMBOLS = {
     "gc_get_precision": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "gc_correlate": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.POINTER(C.c_double)]),
     "gc_correlate_bank": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gc_correlate_ddm": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double)]),
     "gc_replay_prepare": (C.c_int, [_P, C.c_int64, C.POINTER(gc_block)]),
     "gc_replay_launch": (C.c_int, [_P]),
     "gc_replay_fetch": (C.c_int, [_P, C.POINTER(C.c_double)]),

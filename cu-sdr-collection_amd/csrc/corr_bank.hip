@@ -21,20 +21,11 @@
 //               entry 1 + mod(p - 1, n - 2), and since the pads are the period (checked on the host) c[k - 1] is the entry before.
 //   sums        float32 per chunk and (arm, tap) - lanes by fixed shuffles -, written as float64 partials and added over a
 //               block's chunks in index order by bank_combine_kernel.  No atomics: the same input gives the same bits.
-#include <algorithm>
-#include <cmath>
-
-#include "corr_common.h"
+#include "bank_common.h"
 
 using namespace gcorr;
 
 namespace {
-
-constexpr int kBankChunk = 1024;  // S: samples per work item
-constexpr int kBankWG = 256;      // threads per workgroup: kBankChunk / kBankWG consecutive samples per thread in the prefix sums
-constexpr int kBankSPT = kBankChunk / kBankWG;
-constexpr int kBankWaves = kBankWG / 64;
-constexpr long long kBankPartialBytes = 256LL << 20;  // partial sums of one sub-batch of blocks at most
 
 struct BankArgs {
   const uint8_t* if_base;
@@ -48,45 +39,6 @@ struct BankArgs {
   int nblocks;
   int ntaps;
   int arms;  // arms of the partial / out layout: the most a channel of the call has
-};
-
-template <int MODE>
-__device__ __forceinline__ void bank_load_sample(const uint8_t* __restrict__ base, long long idx, float& a, float& b) {
-  float x0, x1;
-  if constexpr (MODE == I8_IQ || MODE == I8_QI) {
-    const unsigned int w = *(const unsigned short*)(base + 2 * idx);  // one 16-bit load per sample
-    x0 = (float)(signed char)(w & 0xffu);
-    x1 = (float)(signed char)(w >> 8);
-  } else if constexpr (MODE == I16_IQ || MODE == I16_QI) {
-    const short* s = (const short*)base + 2 * idx;
-    x0 = (float)s[0];
-    x1 = (float)s[1];
-  } else if constexpr (MODE == I8_REAL) {
-    x0 = (float)((const signed char*)base)[idx];
-    x1 = 0.0f;
-  } else {
-    x0 = (float)((const short*)base)[idx];
-    x1 = 0.0f;
-  }
-  a = Fmt<MODE>::swap ? x1 : x0;
-  b = Fmt<MODE>::swap ? x0 : x1;
-}
-
-// One (arm, tap) ramp of a block: the reference's colon element i and its table index.
-struct BankRamp {
-  double a, b, sp, m;
-  int N;
-  __device__ __forceinline__ int index(int i) const {
-    const int back = N - 1 - i;
-    double t;
-    if (i < back)
-      t = __dadd_rn(a, __dmul_rn((double)i, sp));
-    else if (i > back)
-      t = __dadd_rn(b, -__dmul_rn((double)back, sp));
-    else
-      t = __dadd_rn(a, b) / 2.0;
-    return (int)ceil(__dmul_rn(t, m));
-  }
 };
 
 template <int MODE>
@@ -183,10 +135,7 @@ __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
       const int c_prev = tab[r], c_k = tab[r + 1];  // entries 1 + mod(k - 2, L) (= entry r: the pad is the period) and 1 + mod(k - 1, L)
       if (c_prev == c_k) continue;
       // the smallest sample with index >= k lies in (i0, i_last]: index(i0) < k <= index(i_last)
-      const double x = ((double)(k - 1) / rp.m - rp.a) / rp.sp;
-      int e = (int)fmin(fmax(floor(x) + 1.0, (double)(i0 + 1)), (double)i_last);
-      while (e > i0 + 1 && rp.index(e - 1) >= k) --e;
-      while (e < i_last && rp.index(e) < k) ++e;
+      const int e = rp.boundary(k, i0, i_last);
       const float d = (float)(c_prev - c_k);
       const float2 v = P[e - i0];
       acc.x = fmaf(d, v.x, acc.x);
@@ -219,106 +168,6 @@ __global__ void bank_combine_kernel(const BankArgs p) {
   if (arm < p.chans[p.blocks[b].channel].arms)
     for (int q = p.chunk_base[b]; q < p.chunk_base[b + 1]; ++q) s += p.partial[(long long)q * row + v];
   p.out[i] = s;
-}
-
-int bank_record_mode(const gc_context* ctx) {
-  if (ctx->if_dtype == GC_I8) return ctx->if_layout == GC_IQ ? I8_IQ : ctx->if_layout == GC_QI ? I8_QI : I8_REAL;
-  return ctx->if_layout == GC_IQ ? I16_IQ : ctx->if_layout == GC_QI ? I16_QI : I16_REAL;
-}
-
-// What gc_correlate_bank accepts (include/gnsscorr.h); *arms = the most arms a channel of the list has.
-int bank_validate(const gc_context* ctx, int nblocks, const gc_block* b, int ntaps, const double* off, int* arms) {
-  if (ntaps < 1 || ntaps > GC_BANK_MAX_TAPS) {
-    gc_set_error("gc_correlate_bank: %d taps (1 .. %d)", ntaps, GC_BANK_MAX_TAPS);
-    return GC_E_INVALID;
-  }
-  double omax = 0.0;
-  for (int j = 0; j < ntaps; ++j) {
-    if (!std::isfinite(off[j])) {
-      gc_set_error("gc_correlate_bank: tap offset %d is not finite", j);
-      return GC_E_INVALID;
-    }
-    omax = std::max(omax, std::fabs(off[j]));
-  }
-  if (nblocks == 0) return GC_OK;  // an empty list is no call sequence error, as in gc_correlate
-  if (ctx->precision != GC_PREC_F32) {
-    gc_set_error("gc_correlate_bank: float32 kernels only (gc_set_precision GC_PREC_F32)");
-    return GC_E_UNSUPPORTED;
-  }
-  if (!ctx->d_if) {
-    gc_set_error("no IF buffer loaded");
-    return GC_E_STATE;
-  }
-  if (!(ctx->fs > 0)) {
-    gc_set_error("sampling frequency not set (gc_set_sampling_freq)");
-    return GC_E_STATE;
-  }
-  *arms = 1;
-  bool seen[GC_MAX_CHANNELS] = {false};
-  for (int i = 0; i < nblocks; ++i) {
-    const gc_block& k = b[i];
-    if (k.channel < 0 || k.channel >= GC_MAX_CHANNELS || !ctx->ch[k.channel].configured) {
-      gc_set_error("block %d: channel %d not configured", i, k.channel);
-      return GC_E_STATE;
-    }
-    const HostChannel& c = ctx->ch[k.channel];
-    double max_mult = 1.0;
-    for (int a = 0; a < c.arms; ++a) {
-      if (!c.d_tab[a]) {
-        gc_set_error("block %d: channel %d arm %d has no code table", i, k.channel, a);
-        return GC_E_STATE;
-      }
-      if (k.table_offset[a] != 0) {
-        gc_set_error("block %d: gc_correlate_bank reads whole tables periodically (table_offset must be 0)", i);
-        return GC_E_INVALID;
-      }
-      max_mult = std::max(max_mult, c.mult[a]);
-    }
-    if (!seen[k.channel]) {  // per channel: no window, pads that are the period, every offset within one period
-      seen[k.channel] = true;
-      *arms = std::max(*arms, c.arms);
-      for (int a = 0; a < c.arms; ++a) {
-        if (c.window[a] > 0) {
-          gc_set_error("channel %d arm %d: gc_correlate_bank does not take a code window (gc_set_code_window)", k.channel, a);
-          return GC_E_UNSUPPORTED;
-        }
-        const std::vector<int8_t>& t = c.h_tab[a];
-        const int n = c.nent[a];
-        if ((int)t.size() != n || n < 3 || t[0] != t[n - 2] || t[n - 1] != t[1]) {
-          gc_set_error("channel %d arm %d: the table's pads are not its period ([c(end) c c(1)])", k.channel, a);
-          return GC_E_INVALID;
-        }
-        if (!(omax * c.index_scale * c.mult[a] < (double)(n - 2))) {
-          gc_set_error("channel %d arm %d: a tap offset of %g chips reaches a code period (%d entries) or more", k.channel, a, omax, n - 2);
-          return GC_E_INVALID;
-        }
-      }
-    }
-    if (k.blksize <= 0 || k.first_sample < 0 || !(k.code_phase_step > 0) || !(k.rem_code_phase > -1.0) ||
-        !std::isfinite(k.rem_code_phase) || !std::isfinite(k.carr_freq) || !std::isfinite(k.rem_carr_phase)) {
-      gc_set_error("block %d: invalid descriptor", i);
-      return GC_E_INVALID;
-    }
-    const double rate = k.code_phase_step * c.index_scale * max_mult;  // table entries per sample of the fastest arm
-    if (rate > 1.0) {
-      gc_set_error("block %d: %g table entries per sample (gc_correlate_bank takes at most one)", i, rate);
-      return GC_E_UNSUPPORTED;
-    }
-    if (!(rate >= 1.0 / 65536.0)) {
-      gc_set_error("block %d: %g table entries per sample (below 2^-16)", i, rate);
-      return GC_E_INVALID;
-    }
-    if (!(((double)k.blksize * k.code_phase_step + std::fabs(k.rem_code_phase) + omax) * c.index_scale * max_mult < 2147483000.0)) {
-      gc_set_error("block %d: the ramps' table indices leave int32", i);
-      return GC_E_INVALID;
-    }
-    if ((uint64_t)k.first_sample + (uint64_t)k.blksize > ctx->if_nsamples) {
-      gc_set_error("block %d: samples [%lld, %lld) exceed the IF buffer (%llu samples)", i, (long long)k.first_sample,
-                   (long long)(k.first_sample + k.blksize), (unsigned long long)ctx->if_nsamples);
-      return GC_E_RANGE;  // tracking.m:241-245
-    }
-  }
-  return GC_OK;
 }
 
 }  // namespace
@@ -360,7 +209,7 @@ extern "C" int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* b
     return GC_E_INVALID;
   }
   int arms = 1;
-  int rc = bank_validate(ctx, nblocks, blocks, ntaps, tap_offsets, &arms);
+  int rc = bank_validate("gc_correlate_bank", ctx, nblocks, blocks, ntaps, tap_offsets, &arms);
   if (rc) return rc;
   if (nblocks == 0) return GC_OK;
   GC_HIP(hipSetDevice(ctx->device));

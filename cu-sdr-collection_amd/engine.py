@@ -231,6 +231,20 @@ class Engine:
                                             out.ctypes.data_as(C.POINTER(C.c_double))))
         return out[..., 0] + 1j * out[..., 1]
 
+    def correlate_ddm(self, blocks, offsets, freqs) -> np.ndarray:
+        """gc_correlate_ddm: every block's correlation at the code offsets `offsets` (chips, as correlate_bank) and the carrier
+        offsets `freqs` (Hz, added to each block's carr_freq; at most GC_DDM_MAX_FREQS of them, any order) - bin m is
+        correlate_bank on the blocks with carr_freq + freqs[m], bit for bit.
+        Returns complex128 [nblocks, GC_MAX_ARMS, nfreq, ntaps] = I + 1j * Q, unused arms zero."""
+        n = len(blocks)
+        off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        frq = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        out = np.zeros((n, L.GC_MAX_ARMS, frq.shape[0], off.shape[0], 2))
+        L.check(self._lib.gc_correlate_ddm(self._ctx, n, blocks, off.shape[0], off.ctypes.data_as(C.POINTER(C.c_double)),
+                                           frq.shape[0], frq.ctypes.data_as(C.POINTER(C.c_double)),
+                                           out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[..., 0] + 1j * out[..., 1]
+
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition
         (corr_multi.hip), 5 hybrid for channels with a derived six-fold arm (corr_cboc.hip), 6 float64 (corr_f64.hip), -1 mixed

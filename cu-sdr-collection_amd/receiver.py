@@ -383,19 +383,9 @@ def tracking(fid: Engine, channel, settings, signal: str = "GPS_L1CA", device_lo
 BANK_CHANNEL = 255   # the engine's channel slot correlation_function() configures (the last one: tracking() fills from 0)
 
 
-def correlation_function(fid: Engine, trackResults_k, channel_k, settings, offsets, signal: str = "GPS_L1CA", epochs=None):
-    """The correlation function a tracked channel saw: R(o) at the code offsets `offsets` (chips, positive = late) on the blocks the
-    loop cut, rebuilt from the state tracking.m records per epoch (absoluteSample, remCodePhase, codeFreq, carrFreq, remCarrPhase:
-    tracking.m:212-216,249,277,314,332) - where on a BOC(1,1) peak the channel sits, what multipath does to the peak, a
-    discriminator's S-curve at another spacing.  One gc_correlate_bank call (include/gnsscorr.h).
-
-    trackResults_k, channel_k: one channel's entry of what tracking() returned / was given; the record must be loaded in `fid`.
-    epochs: indices of the epochs to evaluate (None: every epoch the channel completed - a channel that stopped early on a short
-    read, tracking.m:241-245, or was never tracked keeps codeFreq = inf in the epochs it did not reach: those are left out).
-    Returns complex128 [n_epochs, arms, ntaps], arms as the signal's tables (data, pilot, ...).
-    GPS L2C with its pilot (windowed CL table) is refused by the library: GnssCorrError with status GC_E_UNSUPPORTED.
-    Side effects on `fid`: the signal's tables go to the engine's LAST channel slot (BANK_CHANNEL = 255 - whatever a caller keeps
-    there is replaced; tracking() fills slots from 0) and the sampling frequency is set to settings.samplingFreq."""
+def _tracked_blocks(fid: Engine, trackResults_k, channel_k, settings, signal: str, epochs):
+    """The descriptors of the blocks a tracked channel's loop cut, from the state tracking.m records per epoch, on the engine's
+    BANK_CHANNEL slot (configured here with the signal's tables; the sampling frequency is set too).  Returns (blocks, arms)."""
     from . import signals
     spec = signals.SIGNALS[signal]
     sat = getattr(channel_k, spec.id_field, trackResults_k.PRN)                       # as _tracking_prepare: 'K' for GLONASS
@@ -429,7 +419,36 @@ def correlation_function(fid: Engine, trackResults_k, channel_k, settings, offse
         b.el_spacing = 0.0
         b.carr_freq = float(trackResults_k.carrFreq[e])
         b.rem_carr_phase = float(trackResults_k.remCarrPhase[e])
-    return fid.correlate_bank(blocks, offsets)[:, :len(tables), :]
+    return blocks, len(tables)
+
+
+def correlation_function(fid: Engine, trackResults_k, channel_k, settings, offsets, signal: str = "GPS_L1CA", epochs=None):
+    """The correlation function a tracked channel saw: R(o) at the code offsets `offsets` (chips, positive = late) on the blocks the
+    loop cut, rebuilt from the state tracking.m records per epoch (absoluteSample, remCodePhase, codeFreq, carrFreq, remCarrPhase:
+    tracking.m:212-216,249,277,314,332) - where on a BOC(1,1) peak the channel sits, what multipath does to the peak, a
+    discriminator's S-curve at another spacing.  One gc_correlate_bank call (include/gnsscorr.h).
+
+    trackResults_k, channel_k: one channel's entry of what tracking() returned / was given; the record must be loaded in `fid`.
+    epochs: indices of the epochs to evaluate (None: every epoch the channel completed - a channel that stopped early on a short
+    read, tracking.m:241-245, or was never tracked keeps codeFreq = inf in the epochs it did not reach: those are left out).
+    Returns complex128 [n_epochs, arms, ntaps], arms as the signal's tables (data, pilot, ...).
+    GPS L2C with its pilot (windowed CL table) is refused by the library: GnssCorrError with status GC_E_UNSUPPORTED.
+    Side effects on `fid`: the signal's tables go to the engine's LAST channel slot (BANK_CHANNEL = 255 - whatever a caller keeps
+    there is replaced; tracking() fills slots from 0) and the sampling frequency is set to settings.samplingFreq."""
+    blocks, arms = _tracked_blocks(fid, trackResults_k, channel_k, settings, signal, epochs)
+    return fid.correlate_bank(blocks, offsets)[:, :arms, :]
+
+
+def delay_doppler_map(fid: Engine, trackResults_k, channel_k, settings, offsets, freqs, signal: str = "GPS_L1CA", epochs=None):
+    """The delay-Doppler map a tracked channel saw: R(o, f) at the code offsets `offsets` (chips, positive = late) and the carrier
+    offsets `freqs` (Hz, added to the carrFreq the loop recorded for the epoch) on the blocks the loop cut - whether the PLL sits on
+    the main lobe or a side lobe, how good the acquisition's carrFreq was, what sits next to the peak.  The carrier phase of every
+    bin is remCarrPhase at the block's first sample: bins differ in frequency only.  The bin at 0 Hz is correlation_function()
+    bit for bit.  One gc_correlate_ddm call (include/gnsscorr.h).
+
+    Arguments, refusals and side effects as correlation_function().  Returns complex128 [n_epochs, arms, nfreq, ntaps]."""
+    blocks, arms = _tracked_blocks(fid, trackResults_k, channel_k, settings, signal, epochs)
+    return fid.correlate_ddm(blocks, offsets, freqs)[:, :arms]
 
 
 def tracking_file(fid: Engine, path: str, channel, settings, window_samples: int, signal: str = "GPS_L1CA", pilot_fields: str | None = None,

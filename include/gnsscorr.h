@@ -175,6 +175,21 @@ int gc_correlate(gc_context* ctx, int nblocks, const gc_block* blocks, double* o
 #define GC_BANK_MAX_TAPS 64
 int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, double* out);
 
+/* The bank's correlation function at `nfreq` carrier offsets as well: a delay-Doppler map of every block (csrc/corr_ddm.hip).
+ * Bin m of block b is what gc_correlate_bank returns for the same block with carr_freq replaced by the float64 sum
+ * carr_freq + freq_offsets[m] (Hz) - BIT FOR BIT; rem_carr_phase and every other field as they stand, so the carrier phase is
+ * referenced to the block's first sample and the bins differ in frequency only.  A result therefore does not depend on which other
+ * bins, taps or blocks are in the call.  One kernel computes every table boundary once for a group of bins, where nfreq bank calls
+ * repeat the upload, the samples' conversion and the boundary search per bin.
+ * Accepted: everything gc_correlate_bank accepts, and 1 <= nfreq <= GC_DDM_MAX_FREQS, finite offsets (any order, duplicates
+ * allowed) whose sums with carr_freq are finite.  GC_E_INVALID for nfreq out of range and a non-finite offset or sum; every refusal
+ * of the bank (GC_PREC_F64 and code windows: GC_E_UNSUPPORTED) with the bank's status.  Nothing is computed and `out` is not
+ * written on any error; an empty block list is GC_OK.
+ * out[((((b * GC_MAX_ARMS + arm) * nfreq + m) * ntaps + j) * 2 + {0: I, 1: Q}], unused arms zero. */
+#define GC_DDM_MAX_FREQS 64
+int gc_correlate_ddm(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, int nfreq,
+                     const double* freq_offsets, double* out);
+
 /* Replay (batched, open-loop) mode: descriptors stay resident in HBM so that the timed
  * region contains only kernel work (SURVEY.md §7 hard part 1a). */
 int gc_replay_prepare(gc_context* ctx, int64_t nblocks, const gc_block* blocks);

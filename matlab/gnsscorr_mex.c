@@ -19,6 +19,9 @@
  *   sums = gnsscorr_mex('correlate', h, blocks)      % blocks: 8 x nblocks double, see below
  *   R    = gnsscorr_mex('correlate_bank', h, blocks, offsets)   % the blocks' correlation function at the code offsets `offsets` (chips,
  *          late positive; gc_correlate_bank): 2 x ntaps x (3*nblocks), rows I, Q; reshape(R, 2, ntaps, 3, []) is (I|Q, tap, arm, block)
+ *   R    = gnsscorr_mex('correlate_ddm', h, blocks, offsets, freqs)   % the same at the carrier offsets `freqs` as well (Hz, added to the
+ *          blocks' carrFreq; gc_correlate_ddm: bin m is 'correlate_bank' at carrFreq + freqs(m), bit for bit): 2 x ntaps x (nfreq*3*nblocks);
+ *          reshape(R, 2, ntaps, nfreq, 3, []) is (I|Q, tap, bin, arm, block)
  *   [trk, epochs, status] = gnsscorr_mex('track', h, params_struct, channels)   % channels: 5 x nch
  *   res  = gnsscorr_mex('acquire_coarse', h, acq_struct, sampledCodes)          % int8 spc x nprn
  *   f    = gnsscorr_mex('acquire_fine_l1ca', h, acq_struct, caCode, codePhase, coarseFreq)
@@ -142,7 +145,7 @@ static gc_channel_init* channel_inits_from(const mxArray* a, int* nch_out) {
 }
 
 /* blocks: 8 x nblocks, rows = channel, first_sample (0-based), blksize, remCodePhase, codePhaseStep, earlyLateSpc, carrFreq,
- * remCarrPhase - the quantities of tracking.m:212-222,249,277 ('correlate', 'correlate_bank') */
+ * remCarrPhase - the quantities of tracking.m:212-222,249,277 ('correlate', 'correlate_bank', 'correlate_ddm') */
 static gc_block* blocks_from(const mxArray* a, int* n_out) {
   if (mxGetM(a) != 8) mexErrMsgIdAndTxt("gnsscorr:usage", "blocks must be 8 x nblocks");
   const double* b = mxGetDoubles(a);
@@ -260,6 +263,20 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxFree(blk);
     if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
     if (rc) fail("gc_correlate_bank");
+  } else if (!strcmp(cmd, "correlate_ddm")) {
+    /* blocks and offsets as for 'correlate_bank', freqs: the bins' carrier offsets in Hz.  The result is gc_correlate_ddm's `out` as
+     * it lies in memory: (I|Q, tap, bin, arm, block) with GC_MAX_ARMS arms per block, the last three folded. */
+    if (nrhs < 5 || !mxIsDouble(prhs[3]) || !mxIsDouble(prhs[4]))
+      mexErrMsgIdAndTxt("gnsscorr:usage", "correlate_ddm: h, blocks 8 x nblocks, offsets, freqs");
+    int n = 0;
+    gc_block* blk = blocks_from(prhs[2], &n);
+    int ntaps = (int)mxGetNumberOfElements(prhs[3]), nfreq = (int)mxGetNumberOfElements(prhs[4]);
+    const mwSize dims[3] = {2, (mwSize)ntaps, (mwSize)nfreq * (mwSize)GC_MAX_ARMS * (mwSize)n};
+    plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    int rc = gc_correlate_ddm(handle(prhs[1]), n, blk, ntaps, mxGetDoubles(prhs[3]), nfreq, mxGetDoubles(prhs[4]), mxGetDoubles(plhs[0]));
+    mxFree(blk);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
+    if (rc) fail("gc_correlate_ddm");
   } else if (!strcmp(cmd, "track") || !strcmp(cmd, "track_device") || !strcmp(cmd, "track_file") || !strcmp(cmd, "track_file_device")) {
     /* [trk, epochs, status] = gnsscorr_mex('track', h, p, chanTable)
        [trk, epochs, status] = gnsscorr_mex('track_file', h, p, chanTable, fileName, windowSamples, dataType, fileType[, 'QI']):

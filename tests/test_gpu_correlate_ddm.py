@@ -1,0 +1,365 @@
+"""gc_correlate_ddm (csrc/corr_ddm.hip): a block's correlation over code taps and carrier bins.
+
+The contract is an identity (include/gnsscorr.h): bin m is gc_correlate_bank on the block with carr_freq replaced by the float64 sum
+carr_freq + freq_offsets[m], BIT FOR BIT.  So the first check is bytes against Engine.correlate_bank, bin by bin; the second is a
+float64 per-sample restatement written here with the oracle's colon() (the bank test's definition at carr_freq + f_m).
+
+Tolerance of the restatement: 2e-6 of sum |x| over the block, the project's correlator-versus-oracle figure (the bank's TOL).  One
+mis-assigned sample of a 4 097-sample block is 2.4e-4 in those units.
+
+The kernel takes bins in groups of 4 per work item: the bin counts run over 1, one short of a group, a group, one more, two groups
+and one (for groups of 4 and of 8), 17 and the limit of 64."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from oracle import gnss_oracle as O
+
+pytestmark = pytest.mark.gpu
+TOL = 2e-6
+FS = 18e6
+PERIOD_L1 = 1023.0
+# the bank test's offsets: 0, thirds, halves, whole chips, several chips, and just under a period of the 1 023-chip code
+POOL = [0.0, 1.0 / 3, -1.0 / 3, 0.5, -0.5, 1.0, -1.0, 1.5, -1.5, 17.25, -17.25, 1022.9, -1022.9]
+FREQ_POOL = [0.0, 0.37, -0.37, 250.0, -250.0, 500.0, -500.0, 1e3, -1e3, 1e4, -1e4, 4.5e6, -4.5e6]
+PARTIAL_BUDGET = 256 << 20     # the library's budget for one sub-batch's partial sums (csrc/bank_common.h kBankPartialBytes)
+
+
+def _raw(rec, s0, n, layout="IQ"):
+    """raw = data1 + 1i*data2 of tracking.m:233-235 for the record's sample order (GLONASS: swapped; real: no imaginary part)."""
+    if layout == "REAL":
+        return rec[s0:s0 + n].astype(np.float64).astype(np.complex128)
+    seg = rec[2 * s0:2 * (s0 + n)].astype(np.float64)
+    return seg[1::2] + 1j * seg[0::2] if layout == "QI" else seg[0::2] + 1j * seg[1::2]
+
+
+def ddm_reference(raw, tables, rem, step, offsets, carr_freq, freqs, rem_carr, fs, r=1.0, arm_mult=None):
+    """The definition, per sample, in float64: the bank's with carr_freq + f_m.  Returns (complex128 [arms, nfreq, ntaps], number of
+    samples with an integer t_i over the taps)."""
+    n = raw.shape[0]
+    arm_mult = arm_mult or [1.0] * len(tables)
+    code = np.zeros((len(tables), len(offsets), n))
+    ties = 0
+    for j, o in enumerate(offsets):
+        t = O.colon((rem + o) * r, step * r, (((n - 1) * step + rem) + o) * r)
+        assert t.shape[0] == n
+        ties += int(np.sum(t == np.rint(t)))
+        for a, tab in enumerate(tables):
+            p = np.ceil(t * arm_mult[a]).astype(np.int64)           # index into the padded table [c(end) c c(1)] ...
+            code[a, j] = np.asarray(tab, dtype=np.float64)[1 + np.mod(p - 1, len(tab) - 2)]     # ... read periodically
+    out = np.zeros((len(tables), len(freqs), len(offsets)), dtype=np.complex128)
+    for m, f in enumerate(freqs):
+        cf = float(np.float64(carr_freq) + np.float64(f))
+        trig = ((cf * 2.0 * math.pi) * (np.arange(n, dtype=np.float64) / fs)) + rem_carr
+        mixed = np.exp(-1j * trig) * raw
+        out[:, m, :] = code @ mixed
+    return out, ties
+
+
+def _colon_has_n_elements(d, o, r=1.0):
+    """The bank test's rule: the definition takes element i of MATLAB's colon vector, so that vector must have N elements; a draw
+    whose colon comes out one short (two or three samples, a start that cancels to hundredths of a chip) is outside the definition
+    and is drawn again."""
+    n, rem, step = d["n"], d["rem"], d["step"]
+    return O.colon((rem + o) * r, step * r, (((n - 1) * step + rem) + o) * r).shape[0] == n
+
+
+def _blocks(engine, descs, df=0.0):
+    b = engine.make_blocks(len(descs))
+    for k, d in enumerate(descs):
+        b[k].channel = d.get("channel", 0)
+        b[k].blksize = d["n"]
+        b[k].first_sample = d["s0"]
+        b[k].rem_code_phase = d["rem"]
+        b[k].code_phase_step = d["step"]
+        b[k].el_spacing = d.get("d", 0.0)
+        b[k].carr_freq = float(np.float64(d["f"]) + np.float64(df))
+        b[k].rem_carr_phase = d["phi"]
+    return b
+
+
+def _check(engine, rec, descs, offsets, freqs, tables, r=1.0, arm_mult=None, layout="IQ", label=""):
+    """One call for all of `descs`; every block, arm, bin and tap against the restatement.  Returns (worst error / sum |x|, ties per block)."""
+    got = engine.correlate_ddm(_blocks(engine, descs), offsets, freqs)
+    assert got.shape == (len(descs), 3, len(freqs), len(offsets))
+    worst, ties = 0.0, []
+    for k, d in enumerate(descs):
+        raw = _raw(rec, d["s0"], d["n"], layout)
+        ref, nt = ddm_reference(raw, tables, d["rem"], d["step"], offsets, d["f"], freqs, d["phi"], FS, r, arm_mult)
+        ties.append(nt)
+        scale = float(np.sum(np.abs(raw.real) + np.abs(raw.imag)))
+        dev = got[k, :len(tables)] - ref
+        err = max(np.abs(dev.real).max(), np.abs(dev.imag).max()) / scale
+        worst = max(worst, err)
+        assert err < TOL, (label, k, d, err)
+        assert not got[k, len(tables):].any(), (label, k)
+    print(f"{label}: worst {worst:.3e} of sum |x| (bound {TOL:.1e})")
+    return worst, ties
+
+
+@pytest.fixture(scope="module")
+def noise_record():
+    """Random full-range int8 I/Q samples."""
+    return np.random.default_rng(20241018).integers(-128, 128, size=2 * 60000, dtype=np.int8)
+
+
+@pytest.fixture(scope="module")
+def ca_table():
+    return O.pad_code(O.generate_ca_code(7)).astype(np.int8)
+
+
+def _draw_bins(rng, nfreq):
+    """nfreq values of FREQ_POOL in random order: zero always, a duplicate from three bins on (64 bins hold the 13 values several
+    times over)."""
+    rest = [float(x) for x in rng.choice(np.array(FREQ_POOL[1:]), size=nfreq - 1, replace=nfreq - 1 > len(FREQ_POOL) - 1)]
+    vals = [0.0] + rest
+    if nfreq >= 3:
+        vals[-1] = vals[1]
+    return [float(x) for x in rng.permutation(np.array(vals))]
+
+
+@pytest.mark.parametrize("nfreq", [1, 2, 3, 4, 5, 7, 8, 9, 17, 64])
+def test_bin_by_bin_the_banks_bits(engine, noise_record, ca_table, nfreq):
+    """Block sizes around the wavefront (64), the chunk (1 024) and several chunks at three head alignments; 1, 3 and 33 taps; bins from
+    a third of a hertz to 4.5 MHz, both signs, unordered, duplicated.  Every bin's bytes are the bank's at the summed frequency."""
+    engine.load_if(noise_record, fs=FS)
+    engine.set_channel(0, [ca_table])
+    rng = np.random.default_rng(1000 + nfreq)
+    fill = list(rng.uniform(-2.0, 2.0, size=33 - len(POOL) - 2)) + [0.5, 0.5]
+    sets = [[-1.0 / 3], [0.0, 1022.9, -17.25], [float(x) for x in rng.permutation(np.array(POOL + fill))]]
+    assert [len(s) for s in sets] == [1, 3, 33]
+    descs = []
+    for n in (1, 2, 63, 64, 65, 1023, 1024, 1025, 2049, 4097):
+        for s0 in (0, 1, 7):
+            while True:
+                step = (1.023e6 + rng.uniform(-5, 5)) / FS
+                d = dict(n=n, s0=s0, rem=float(rng.uniform(-0.9, 1.0)), step=step, f=20e3 + float(rng.uniform(-5e3, 5e3)),
+                         phi=float(rng.uniform(-2 * np.pi, 2 * np.pi)))
+                if all(_colon_has_n_elements(d, o) for offsets in sets for o in offsets):
+                    break
+            descs.append(d)
+    for offsets in sets:
+        freqs = _draw_bins(rng, nfreq)
+        assert len(freqs) == nfreq and 0.0 in freqs and (nfreq < 3 or len(set(freqs)) < nfreq)
+        got = engine.correlate_ddm(_blocks(engine, descs), offsets, freqs)
+        assert got.shape == (len(descs), 3, nfreq, len(offsets)) and not got[:, 1:].any()
+        for m, f in enumerate(freqs):
+            want = engine.correlate_bank(_blocks(engine, descs, df=f), offsets)
+            assert np.ascontiguousarray(got[:, :, m]).tobytes() == want.tobytes(), (len(offsets), nfreq, m, f)
+        assert np.abs(got[:, 0]).max() > 0
+
+
+BINS3 = [0.0, -731.5, 5000.0]
+
+
+def test_channel_kinds_against_the_restatement(engine, noise_record):
+    """Two arms at R = 2 (Galileo E1 B + C), two arms at 10.23 Mcps (GPS L5 I + Q), three arms with ramp multipliers (1, 1, 6)
+    (BDS B1C wide-band)."""
+    from cu_sdr_collection_amd import codes
+    engine.load_if(noise_record, fs=FS)
+    offsets = [float(x) for x in np.linspace(-2.0, 2.0, 9)]
+    kinds = [("E1", [codes.padded_table(codes.generateE1Bcode(11)), codes.padded_table(codes.generateE1Ccode(11))], 2.0, None, 1.023e6),
+             ("L5", [codes.padded_table(codes.generateL5Icode(3)), codes.padded_table(codes.generateL5Qcode(3))], 1.0, None, 10.23e6),
+             ("B1C", [codes.padded_table(codes.generateDataBOC11(19)), codes.padded_table(codes.generatePilotBOC11(19)),
+                      codes.padded_table(codes.generatePilotBOC61(19))], 2.0, [1.0, 1.0, 6.0], 1.023e6)]
+    for ch, (name, tables, r, mult, rate) in enumerate(kinds):
+        tables = [np.asarray(t, dtype=np.int8) for t in tables]
+        engine.set_channel(ch, tables, index_scale=r, arm_mult=mult)
+        descs = [dict(channel=ch, n=4097, s0=9, rem=0.31, step=(rate + 3.0) / FS, f=-3.1e4, phi=2.0),
+                 dict(channel=ch, n=4097, s0=50001, rem=0.0, step=rate / FS, f=1.7e4, phi=-0.3)]
+        _check(engine, noise_record, descs, offsets, BINS3, tables, r=r, arm_mult=mult, label=name)
+
+
+@pytest.mark.parametrize("fmt", ["i8_qi", "i8_real", "i16_iq", "i16_qi", "i16_real"])
+def test_record_formats_against_the_restatement(engine, noise_record, ca_table, fmt):
+    """The kernel is instantiated per record format."""
+    import cu_sdr_collection_amd as P
+    dt, lay = fmt.split("_")
+    rec = noise_record[:2 * 20000] if dt == "i8" else (noise_record[:2 * 20000].astype(np.int16) * 37 + 5)   # the high byte matters
+    layout = {"iq": P._lib.GC_IQ, "qi": P._lib.GC_QI, "real": P._lib.GC_REAL}[lay]
+    engine.load_if(rec, layout=layout, fs=FS)
+    engine.set_channel(0, [ca_table])
+    descs = [dict(n=2049, s0=7, rem=0.25, step=(1.023e6 - 2.0) / FS, f=2.5e4, phi=1.1)]
+    _check(engine, rec, descs, POOL[:9], BINS3, [ca_table], layout=lay.upper(), label=fmt)
+
+
+def test_tie_dense_ramps_against_the_restatement(engine, noise_record, ca_table):
+    """Ramps whose samples sit exactly on table edges (the bank test's): rem = 0 with the nominal L1 C/A step, rem = 0.1 with step
+    0.2, integer and half-integer offsets, a negative remainder.  The restatement must itself see samples with an integer t_i in
+    the first three, or the case proves nothing."""
+    engine.load_if(noise_record, fs=FS)
+    engine.set_channel(0, [ca_table])
+    offsets = [-2.0, -1.0, -0.5, 0.0, 0.5, 1.0, 1.5, 0.1, -0.1]
+    descs = [dict(n=4097, s0=5, rem=0.0, step=1.023e6 / 18e6, f=2.2e4, phi=0.4),
+             dict(n=4097, s0=11, rem=0.1, step=0.2, f=2.2e4, phi=0.4),
+             dict(n=1000, s0=777, rem=0.1, step=0.2, f=-1.3e4, phi=-1.0),
+             dict(n=4097, s0=3, rem=-0.37, step=0.2, f=2.2e4, phi=0.4),
+             dict(n=2049, s0=1, rem=-0.37, step=1.023e6 / 18e6, f=2.2e4, phi=0.4)]
+    _, ties = _check(engine, noise_record, descs, offsets, BINS3, [ca_table], label="tie-dense")
+    assert ties[0] >= 2 and ties[1] > 100 and ties[2] > 100, ties
+
+
+def test_independence_and_reproducibility(engine, l1ca_scene):
+    """12 channels x 4 epochs, 17 taps, 17 bins: a cell does not depend on the run, nor on which other bins, blocks or taps are in the call."""
+    S, sats, iq = l1ca_scene
+    engine.load_if(iq, fs=S.samplingFreq)
+    for c in range(12):
+        engine.set_channel(c, [O.pad_code(O.generate_ca_code(c + 1)).astype(np.int8)])
+    rng = np.random.default_rng(8)
+    descs = []
+    for e in range(4):
+        for c in range(12):
+            step = (1.023e6 + rng.uniform(-5, 5)) / FS
+            rem = float(rng.uniform(0, step))
+            descs.append(dict(channel=c, n=int(np.ceil((1023.0 - rem) / step)), s0=18000 * e + int(rng.integers(0, 9000)), rem=rem, step=step,
+                              f=20e3 + float(rng.uniform(-5e3, 5e3)), phi=float(rng.uniform(-3, 3))))
+    offsets = [j / 4 for j in range(-8, 9)]
+    freqs = [125.0 * m for m in range(-8, 9)]
+    whole = engine.correlate_ddm(_blocks(engine, descs), offsets, freqs)
+    assert whole.shape == (48, 3, 17, 17)
+    assert engine.correlate_ddm(_blocks(engine, descs), offsets, freqs).tobytes() == whole.tobytes()
+    assert np.abs(whole[:, 0]).min() > 0 and not whole[:, 1:].any()
+    for m, f in enumerate(freqs):
+        one = engine.correlate_ddm(_blocks(engine, descs), offsets, [f])
+        assert one[:, :, 0].tobytes() == np.ascontiguousarray(whole[:, :, m]).tobytes(), m
+    for k, d in enumerate(descs):
+        one = engine.correlate_ddm(_blocks(engine, [d]), offsets, freqs)
+        assert one[0].tobytes() == whole[k].tobytes(), k
+    cols = [0, 3, 4, 11, 16]
+    sub = engine.correlate_ddm(_blocks(engine, descs), [offsets[j] for j in cols], freqs)
+    assert sub.tobytes() == np.ascontiguousarray(whole[:, :, :, cols]).tobytes()
+
+
+def test_a_list_walked_in_sub_batches_equals_its_parts(engine, noise_record, ca_table):
+    """Three arms, 64 taps and 64 bins: a chunk's partial sums are 196 608 bytes and the 256 MB budget holds 1 365 chunks.  273 blocks
+    of five chunks fill them, so block 273 of 280 begins the second sub-batch.  The two parts called separately, and a block called
+    alone, give the whole's bytes; the blocks either side of the seam agree with the restatement."""
+    engine.load_if(noise_record, fs=FS)
+    tabs = [ca_table, O.pad_code(O.generate_ca_code(8)).astype(np.int8), O.pad_code(O.generate_ca_code(9)).astype(np.int8)]
+    engine.set_channel(0, tabs)
+    nb, n = 280, 4097
+    chunk_bytes = 3 * 64 * 64 * 16
+    first = (PARTIAL_BUDGET // chunk_bytes) // 5
+    assert chunk_bytes == 196608 and PARTIAL_BUDGET // chunk_bytes == 1365 and first == 273 < nb
+    rng = np.random.default_rng(64)
+    rem, s0, f = rng.uniform(0, 1, nb), rng.integers(0, 60000 - n, nb), rng.uniform(-3e4, 3e4, nb)
+    descs = [dict(n=n, s0=int(s0[k]), rem=float(rem[k]), step=1.023e6 / FS, f=float(f[k]), phi=0.3) for k in range(nb)]
+    offsets = [float(x) for x in np.linspace(-3.0, 3.0, 64)]
+    freqs = [float(x) for x in np.linspace(-1575.0, 1575.0, 64)]
+    whole = engine.correlate_ddm(_blocks(engine, descs), offsets, freqs)
+    assert whole.shape == (nb, 3, 64, 64) and np.abs(whole).min() > 0
+    for part in (slice(0, first), slice(first, nb)):
+        assert engine.correlate_ddm(_blocks(engine, descs[part]), offsets, freqs).tobytes() == whole[part].tobytes()
+    for k in (0, first - 1, first, nb - 1):
+        assert engine.correlate_ddm(_blocks(engine, [descs[k]]), offsets, freqs)[0].tobytes() == whole[k].tobytes(), k
+    for k in (first - 1, first):
+        raw = _raw(noise_record, descs[k]["s0"], n)
+        ref, _ = ddm_reference(raw, tabs, descs[k]["rem"], descs[k]["step"], offsets, descs[k]["f"], freqs, descs[k]["phi"], FS)
+        dev = whole[k] - ref
+        err = max(np.abs(dev.real).max(), np.abs(dev.imag).max()) / float(np.sum(np.abs(raw.real) + np.abs(raw.imag)))
+        print(f"block {k} at the sub-batch seam: worst {err:.3e} of sum |x| (bound {TOL:.1e})")
+        assert err < TOL, (k, err)
+
+
+def test_an_empty_list_is_no_error_even_before_a_record_is_loaded():
+    import cu_sdr_collection_amd as P
+    with P.Engine(0) as fresh:
+        assert fresh.correlate_ddm(fresh.make_blocks(0), [0.0, 0.5], [0.0, 1.0, 2.0]).shape == (0, 3, 3, 2)
+        with pytest.raises(P.GnssCorrError) as e:
+            fresh.correlate_ddm(fresh.make_blocks(0), [0.0], [float("nan")])
+        assert e.value.status == P._lib.GC_E_INVALID
+
+
+def test_refusals_leave_the_output_untouched(engine, noise_record, ca_table):
+    import cu_sdr_collection_amd as P
+    L = P._lib
+    engine.load_if(noise_record, fs=FS)
+    engine.set_channel(0, [ca_table])
+    engine.set_channel(5, [ca_table], windows=[512])
+    broken = ca_table.copy()
+    broken[0] = -broken[0]                                   # [c(end) c c(1)] with a wrong first pad
+    engine.set_channel(6, [broken])
+    good = dict(channel=0, n=2049, s0=3, rem=0.2, step=1.023e6 / FS, f=2e4, phi=0.1)
+    dp = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+
+    def call(desc, offsets, freqs, nfreq=None):
+        off = np.asarray(offsets, dtype=np.float64)
+        frq = np.asarray(freqs, dtype=np.float64)
+        out = np.full((1, 3, max(len(frq), 1), max(len(off), 1), 2), 12345.0)
+        rc = engine._lib.gc_correlate_ddm(engine._ctx, 1, _blocks(engine, [desc]), len(off), dp(off),
+                                          len(frq) if nfreq is None else nfreq, dp(frq), dp(out))
+        assert np.all(out == 12345.0), "a refused call must not write its output"
+        return rc
+
+    assert call(good, [0.0], [0.0], nfreq=0) == L.GC_E_INVALID
+    assert call(good, [0.0], np.zeros(65)) == L.GC_E_INVALID
+    assert call(good, [0.0], [0.0, float("nan")]) == L.GC_E_INVALID
+    assert call(good, [0.0], [0.0, float("inf")]) == L.GC_E_INVALID
+    assert call(good, np.zeros(65), [0.0]) == L.GC_E_INVALID                        # 65 taps
+    assert call(good, [0.0, PERIOD_L1], [0.0]) == L.GC_E_INVALID                    # a full period
+    assert call(dict(good, channel=5), [0.0], [0.0]) == L.GC_E_UNSUPPORTED          # windowed channel
+    assert call(dict(good, channel=6), [0.0], [0.0]) == L.GC_E_INVALID              # broken pads
+    assert call(dict(good, step=1.5), [0.0], [0.0]) == L.GC_E_UNSUPPORTED           # more than one table entry per sample
+    assert call(dict(good, s0=60000 - 2048), [0.0], [0.0]) == L.GC_E_RANGE          # one sample past the record
+    assert call(dict(good, channel=200), [0.0], [0.0]) == L.GC_E_STATE
+    engine.set_precision("double")
+    try:
+        assert call(good, [0.0], [0.0]) == L.GC_E_UNSUPPORTED
+    finally:
+        engine.set_precision("single")
+    ok = engine.correlate_ddm(_blocks(engine, [good]), [0.0, 1022.9], [0.0, 250.0])
+    assert ok.shape == (1, 3, 2, 2) and np.abs(ok[0, 0]).min() > 0
+    with P.Engine(0) as fresh:
+        assert fresh.correlate_ddm(fresh.make_blocks(0), [0.0], [0.0, 1.0]).shape == (0, 3, 2, 1)
+
+
+def test_delay_doppler_map_of_a_tracked_channel_peaks_at_the_tracked_point(engine, l1ca_scene):
+    """receiver.delay_doppler_map on a 40-epoch tracking run.  Along frequency the epoch mean of |R(0, f)| falls over 0, 400, 800 Hz
+    on both sides (a 1 ms block's main lobe has its null at 1 kHz: noiseless amplitudes 1, 0.76, 0.23); along code, at 0 Hz, over
+    |o| = 0, 1/4, 1/2 - the C/A triangle.  The restatement, on the same recorded state, must show both orderings too (the scene has
+    other satellites and noise in it) and agree with the library cell by cell; the bin at 0 Hz is correlation_function's bytes."""
+    import cu_sdr_collection_amd as P
+    from types import SimpleNamespace
+    S, sats, iq = l1ca_scene
+    ms, nch = S.msToProcess, S.numberOfChannels
+    offsets = [-0.5, -0.25, 0.0, 0.25, 0.5]
+    freqs = [-800.0, -400.0, 0.0, 400.0, 800.0]
+    try:
+        S.msToProcess, S.numberOfChannels = 40, 2
+        ch = [SimpleNamespace(PRN=s.prn, acquiredFreq=S.IF + s.doppler + 4.0, codePhase=int(np.ceil(s.code_phase_samples)) + 1, status="T")
+              for s in sats[:2]]
+        engine.load_if(iq, fs=S.samplingFreq)
+        tr, _ = P.tracking(engine, ch, S)
+        got = P.delay_doppler_map(engine, tr[0], ch[0], S, offsets, freqs)
+        ends = P.delay_doppler_map(engine, tr[0], ch[0], S, offsets, freqs, epochs=[0, 39])
+        bank = P.correlation_function(engine, tr[0], ch[0], S, offsets)
+    finally:
+        S.msToProcess, S.numberOfChannels = ms, nch
+    assert got.shape == (40, 1, 5, 5) and got.dtype == np.complex128
+    assert ends.tobytes() == got[[0, 39]].tobytes()
+    assert np.ascontiguousarray(got[:, :, 2]).tobytes() == bank.tobytes()
+    tab = O.pad_code(O.generate_ca_code(sats[0].prn))
+    ref = np.zeros((40, 5, 5), dtype=np.complex128)
+    worst = 0.0
+    for e in range(40):
+        step = tr[0].codeFreq[e] / S.samplingFreq
+        rem = tr[0].remCodePhase[e]
+        n = int(np.ceil((S.codeLength - rem) / step))
+        s0 = int(tr[0].absoluteSample[e])
+        raw = _raw(iq, s0, n)
+        r, _ = ddm_reference(raw, [tab], rem, step, offsets, tr[0].carrFreq[e], freqs, tr[0].remCarrPhase[e], S.samplingFreq)
+        ref[e] = r[0]
+        dev = got[e, 0] - r[0]
+        err = max(np.abs(dev.real).max(), np.abs(dev.imag).max()) / float(np.sum(np.abs(raw.real) + np.abs(raw.imag)))
+        worst = max(worst, err)
+        assert err < TOL, (e, err)
+    print(f"tracked channel: worst {worst:.3e} of sum |x| (bound {TOL:.1e})")
+    for name, mean in (("restatement", np.abs(ref).mean(axis=0)), ("library", np.abs(got[:, 0]).mean(axis=0))):   # [bin, tap]
+        assert np.unravel_index(int(np.argmax(mean)), mean.shape) == (2, 2), (name, mean)
+        for side in (+1, -1):
+            along_f = [mean[2 + side * m, 2] for m in range(3)]          # |f| = 0, 400, 800 Hz at o = 0
+            along_o = [mean[2, 2 + side * j] for j in range(3)]          # |o| = 0, 1/4, 1/2 at 0 Hz
+            assert along_f[0] > along_f[1] > along_f[2], (name, side, along_f)
+            assert along_o[0] > along_o[1] > along_o[2], (name, side, along_o)
