@@ -35,8 +35,8 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                "corr_lane.hip@GC_LANE_PART=0", "corr_lane.hip@GC_LANE_PART=1", "corr_lane.hip@GC_LANE_PART=2", "corr_lane.hip@GC_LANE_PART=3",
                "track.hip", "multi.hip", "stream.hip",
                "corr_f64.hip",    # gc_set_precision(GC_PREC_F64): the float64 per-sample kernel and its device loop
-               "corr_bank.hip",   # gc_correlate_bank: a block's correlation function at up to 64 taps from one pass over its samples
-               "corr_ddm.hip",    # gc_correlate_ddm: the bank's numbers at up to 64 carrier offsets, every table boundary computed once per group of bins
+               "corr_bank.hip",   # gc_correlate_bank: a block's correlation function at up to 64 taps from one pass over its samples; gc_correlate_ddm:
+                                  # the same kernel at up to 64 carrier offsets, every table boundary computed once per group of bins
                # the acquisition, one translation unit per part of the search (acq_internal.h is what they share)
                "acq_fft.hip", "acq_coarse.hip", "acq_shift.hip", "acq_fine.hip", "acq_cond.hip", "acq_guard.hip", "navsync.hip"]
 
@@ -52,7 +52,7 @@ LIBS = {
     "libgnsscorr_tuning.so": [_tuned(u) for u in _CORR_UNITS],
     "libgnsssynth.so": ["synth.hip"],
 }
-HEADERS = ["gc_internal.h", "corr_common.h", "bank_common.h", "launch_plan.h", "devloop.h", "acq_guard.h", "acq_internal.h", os.path.join("..", "..", "include", "gnsscorr.h")]
+HEADERS = ["gc_internal.h", "corr_common.h", "launch_plan.h", "devloop.h", "acq_guard.h", "acq_internal.h", os.path.join("..", "..", "include", "gnsscorr.h")]
 # --offload-compress: the gfx950 code objects inside the fat binary are zstd-compressed (10.1 -> ~1.6 MB; the HIP runtime inflates them
 # when the library is loaded: ~20 ms once per process)
 FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
@@ -62,7 +62,7 @@ FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-f
 # header compiled under the default -ffp-contract=fast, so the backend fuses them into v_fma_f64 (one rounding
 # instead of two: wrong table index at exact ties).  These translation units therefore forbid contraction;
 # wanted FMAs are written as fmaf() / fma().
-NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip", "corr_bank.hip", "corr_ddm.hip"}
+NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip", "corr_bank.hip"}
 
 
 def _hipcc() -> str:

@@ -1,13 +1,23 @@
-// corr_bank.hip — gc_correlate_bank: the correlation function of a block at up to GC_BANK_MAX_TAPS code offsets.
+// corr_bank.hip — gc_correlate_bank: the correlation function of a block at up to GC_BANK_MAX_TAPS code offsets, and
+// gc_correlate_ddm: the same at up to GC_DDM_MAX_FREQS carrier offsets as well (a delay-Doppler map).
 //
-// The E/P/L kernels pay per sample and tap.  Here the samples of a block are read, converted and carrier-mixed ONCE, and every
-// tap then costs work per table entry its ramp crosses, not per sample (GPS L1 C/A at 18 Msps: 1 023 entries against 18 000
-// samples):
+// The DDM is defined as an identity: bin m of a block is what the bank returns for the block with carr_freq replaced by the
+// float64 sum carr_freq + freq_offsets[m], bit for bit.  The code says so: one chunk kernel over (record format, G bins per work
+// item), one combine kernel, one host driver.  The bank is G = 1 with no frequency offsets (none is added: -0.0 + 0.0 is +0.0);
+// the DDM is G = GC_DDM_GROUP.
 //
-//   work item   (block, chunk of kBankChunk consecutive samples), one workgroup of kBankWG threads each
-//   phase A     the chunk's samples mixed with the carrier - phase ph0 + i * carrFreq / fs reduced in float64, float32 sincospi,
-//               as the float32 correlators do - and their inclusive prefix sums P[0 .. n] left in LDS as float pairs.  The sums
-//               restart at every chunk: |P| stays below the chunk's sum |x|, which keeps float32 cancellation at the 1e-8 level.
+// The E/P/L kernels pay per sample and tap.  Here the samples of a block are read and converted ONCE, carrier-mixed once per bin,
+// and every tap then costs work per table entry its ramp crosses, not per sample (GPS L1 C/A at 18 Msps: 1 023 entries against
+// 18 000 samples):
+//
+//   work item   (block, chunk of kBankChunk consecutive samples, group of G consecutive bins), one workgroup of kBankWG threads
+//   phase A     a thread's kBankSPT consecutive samples are loaded and converted once and stay in registers.  Per bin of the
+//               group: phase ph0 + i * tau reduced in float64 (tau = carr_freq / fs, or (carr_freq + f_m) / fs), float32 sincospi
+//               as the float32 correlators do, the two products, the thread's running sums, the wave's shuffle scan, the waves
+//               before in index order: the inclusive prefix sums P_g[0 .. n] left in LDS as float pairs.  The sums restart at
+//               every chunk: |P| stays below the chunk's sum |x|, which keeps float32 cancellation at the 1e-8 level - so the
+//               chunk size is part of the identity.  No rotation recurrence across samples or bins: either would make a bin
+//               depend on its neighbours.
 //   phase B     per (arm, tap) the replica index p(i) = ceil(fl(t_i * m_a)) is non-decreasing in i (t_i strictly increasing for
 //               2^-16 <= step * R * m_a <= 1), so with k_lo = p(first), k_hi = p(last) and e(k) = the smallest sample whose
 //               index is >= k
@@ -19,13 +29,184 @@
 //               element (corr_f64.hip, corr_kernel.hip: forwards from the start in the first half, backwards from the end in
 //               the second, the mean in the middle).  Tables are read as int8 from device memory, periodically: index p reads
 //               entry 1 + mod(p - 1, n - 2), and since the pads are the period (checked on the host) c[k - 1] is the entry before.
-//   sums        float32 per chunk and (arm, tap) - lanes by fixed shuffles -, written as float64 partials and added over a
-//               block's chunks in index order by bank_combine_kernel.  No atomics: the same input gives the same bits.
-#include "bank_common.h"
+//               The entry's two table values, their comparison and e(k) - the float64 search that is the expensive part of a
+//               tap - do not depend on the carrier: computed once, then one read of P_g[e - i0] and two fmaf per bin.
+//   sums        float32 per chunk and (arm, bin, tap) - lanes by fixed shuffles -, written as float64 partials
+//               [chunk][arm][bin][tap][2] and added over a block's chunks in index order by bank_combine_kernel.  No atomics:
+//               the same input gives the same bits.
+#include <algorithm>
+#include <cmath>
+
+#include "corr_common.h"
 
 using namespace gcorr;
 
+// Bins per work item of the DDM: G * (kBankChunk + 1) float2 of LDS (4: 32.9 KB, four workgroups per CU).  Measured at 4, 8 and 16
+// (DESIGN.md 4.7): the smallest group won - phase A, per bin whatever the group, wants the waves the LDS leaves room for more than
+// phase B wants its boundaries shared further.  A throw-away build sets another value (scripts/ddm_timing.py).
+#ifndef GC_DDM_GROUP
+#define GC_DDM_GROUP 4
+#endif
+
 namespace {
+
+constexpr int kBankChunk = 1024;  // S: samples per work item
+constexpr int kBankWG = 256;      // threads per workgroup: kBankChunk / kBankWG consecutive samples per thread in the prefix sums
+constexpr int kBankSPT = kBankChunk / kBankWG;
+constexpr int kBankWaves = kBankWG / 64;
+constexpr long long kBankPartialBytes = 256LL << 20;  // partial sums of one sub-batch of blocks at most
+
+template <int MODE>
+__device__ __forceinline__ void bank_load_sample(const uint8_t* __restrict__ base, long long idx, float& a, float& b) {
+  float x0, x1;
+  if constexpr (MODE == I8_IQ || MODE == I8_QI) {
+    const unsigned int w = *(const unsigned short*)(base + 2 * idx);  // one 16-bit load per sample
+    x0 = (float)(signed char)(w & 0xffu);
+    x1 = (float)(signed char)(w >> 8);
+  } else if constexpr (MODE == I16_IQ || MODE == I16_QI) {
+    const short* s = (const short*)base + 2 * idx;
+    x0 = (float)s[0];
+    x1 = (float)s[1];
+  } else if constexpr (MODE == I8_REAL) {
+    x0 = (float)((const signed char*)base)[idx];
+    x1 = 0.0f;
+  } else {
+    x0 = (float)((const short*)base)[idx];
+    x1 = 0.0f;
+  }
+  a = Fmt<MODE>::swap ? x1 : x0;
+  b = Fmt<MODE>::swap ? x0 : x1;
+}
+
+// One (arm, tap) ramp of a block: the reference's colon element i and its table index.
+struct BankRamp {
+  double a, b, sp, m;
+  int N;
+  __device__ __forceinline__ int index(int i) const {
+    const int back = N - 1 - i;
+    double t;
+    if (i < back)
+      t = __dadd_rn(a, __dmul_rn((double)i, sp));
+    else if (i > back)
+      t = __dadd_rn(b, -__dmul_rn((double)back, sp));
+    else
+      t = __dadd_rn(a, b) / 2.0;
+    return (int)ceil(__dmul_rn(t, m));
+  }
+  // e(k): the smallest sample of the chunk [i0, i_last] whose index is >= k, for index(i0) < k <= index(i_last) - it lies in
+  // (i0, i_last].  A candidate from a float64 division, corrected with the element rule itself: down while sample e - 1 already
+  // has index >= k, up while sample e has index < k.
+  __device__ __forceinline__ int boundary(int k, int i0, int i_last) const {
+    const double x = ((double)(k - 1) / m - a) / sp;
+    int e = (int)fmin(fmax(floor(x) + 1.0, (double)(i0 + 1)), (double)i_last);
+    while (e > i0 + 1 && index(e - 1) >= k) --e;
+    while (e < i_last && index(e) < k) ++e;
+    return e;
+  }
+};
+
+int bank_record_mode(const gc_context* ctx) {
+  if (ctx->if_dtype == GC_I8) return ctx->if_layout == GC_IQ ? I8_IQ : ctx->if_layout == GC_QI ? I8_QI : I8_REAL;
+  return ctx->if_layout == GC_IQ ? I16_IQ : ctx->if_layout == GC_QI ? I16_QI : I16_REAL;
+}
+
+// What gc_correlate_bank accepts (include/gnsscorr.h), for it and for the functions defined through it (`fn`: the name in the
+// error texts); *arms = the most arms a channel of the list has.
+int bank_validate(const char* fn, const gc_context* ctx, int nblocks, const gc_block* b, int ntaps, const double* off, int* arms) {
+  if (ntaps < 1 || ntaps > GC_BANK_MAX_TAPS) {
+    gc_set_error("%s: %d taps (1 .. %d)", fn, ntaps, GC_BANK_MAX_TAPS);
+    return GC_E_INVALID;
+  }
+  double omax = 0.0;
+  for (int j = 0; j < ntaps; ++j) {
+    if (!std::isfinite(off[j])) {
+      gc_set_error("%s: tap offset %d is not finite", fn, j);
+      return GC_E_INVALID;
+    }
+    omax = std::max(omax, std::fabs(off[j]));
+  }
+  if (nblocks == 0) return GC_OK;  // an empty list is no call sequence error, as in gc_correlate
+  if (ctx->precision != GC_PREC_F32) {
+    gc_set_error("%s: float32 kernels only (gc_set_precision GC_PREC_F32)", fn);
+    return GC_E_UNSUPPORTED;
+  }
+  if (!ctx->d_if) {
+    gc_set_error("no IF buffer loaded");
+    return GC_E_STATE;
+  }
+  if (!(ctx->fs > 0)) {
+    gc_set_error("sampling frequency not set (gc_set_sampling_freq)");
+    return GC_E_STATE;
+  }
+  *arms = 1;
+  bool seen[GC_MAX_CHANNELS] = {false};
+  for (int i = 0; i < nblocks; ++i) {
+    const gc_block& k = b[i];
+    if (k.channel < 0 || k.channel >= GC_MAX_CHANNELS || !ctx->ch[k.channel].configured) {
+      gc_set_error("block %d: channel %d not configured", i, k.channel);
+      return GC_E_STATE;
+    }
+    const HostChannel& c = ctx->ch[k.channel];
+    double max_mult = 1.0;
+    for (int a = 0; a < c.arms; ++a) {
+      if (!c.d_tab[a]) {
+        gc_set_error("block %d: channel %d arm %d has no code table", i, k.channel, a);
+        return GC_E_STATE;
+      }
+      if (k.table_offset[a] != 0) {
+        gc_set_error("block %d: %s reads whole tables periodically (table_offset must be 0)", i, fn);
+        return GC_E_INVALID;
+      }
+      max_mult = std::max(max_mult, c.mult[a]);
+    }
+    if (!seen[k.channel]) {  // per channel: no window, pads that are the period, every offset within one period
+      seen[k.channel] = true;
+      *arms = std::max(*arms, c.arms);
+      for (int a = 0; a < c.arms; ++a) {
+        if (c.window[a] > 0) {
+          gc_set_error("channel %d arm %d: %s does not take a code window (gc_set_code_window)", k.channel, a, fn);
+          return GC_E_UNSUPPORTED;
+        }
+        const std::vector<int8_t>& t = c.h_tab[a];
+        const int n = c.nent[a];
+        if ((int)t.size() != n || n < 3 || t[0] != t[n - 2] || t[n - 1] != t[1]) {
+          gc_set_error("channel %d arm %d: the table's pads are not its period ([c(end) c c(1)])", k.channel, a);
+          return GC_E_INVALID;
+        }
+        if (!(omax * c.index_scale * c.mult[a] < (double)(n - 2))) {
+          gc_set_error("channel %d arm %d: a tap offset of %g chips reaches a code period (%d entries) or more", k.channel, a, omax, n - 2);
+          return GC_E_INVALID;
+        }
+      }
+    }
+    if (k.blksize <= 0 || k.first_sample < 0 || !(k.code_phase_step > 0) || !(k.rem_code_phase > -1.0) ||
+        !std::isfinite(k.rem_code_phase) || !std::isfinite(k.carr_freq) || !std::isfinite(k.rem_carr_phase)) {
+      gc_set_error("block %d: invalid descriptor", i);
+      return GC_E_INVALID;
+    }
+    const double rate = k.code_phase_step * c.index_scale * max_mult;  // table entries per sample of the fastest arm
+    if (rate > 1.0) {
+      gc_set_error("block %d: %g table entries per sample (%s takes at most one)", i, rate, fn);
+      return GC_E_UNSUPPORTED;
+    }
+    if (!(rate >= 1.0 / 65536.0)) {
+      gc_set_error("block %d: %g table entries per sample (below 2^-16)", i, rate);
+      return GC_E_INVALID;
+    }
+    if (!(((double)k.blksize * k.code_phase_step + std::fabs(k.rem_code_phase) + omax) * c.index_scale * max_mult < 2147483000.0)) {
+      gc_set_error("block %d: the ramps' table indices leave int32", i);
+      return GC_E_INVALID;
+    }
+    if ((uint64_t)k.first_sample + (uint64_t)k.blksize > ctx->if_nsamples) {
+      gc_set_error("block %d: samples [%lld, %lld) exceed the IF buffer (%llu samples)", i, (long long)k.first_sample,
+                   (long long)(k.first_sample + k.blksize), (unsigned long long)ctx->if_nsamples);
+      return GC_E_RANGE;  // tracking.m:241-245
+    }
+  }
+  return GC_OK;
+}
+constexpr int kDdmGroup = GC_DDM_GROUP;
+static_assert(kDdmGroup >= 1 && kDdmGroup * (kBankChunk + 1) * 8 + kDdmGroup * kBankWaves * 8 <= 160 * 1024, "a workgroup's LDS");
 
 struct BankArgs {
   const uint8_t* if_base;
@@ -33,19 +214,23 @@ struct BankArgs {
   const DevChannel* chans;
   const int32_t* chunk_base;  // [nblocks + 1]: chunks before block b
   const double* offsets;      // [ntaps] chips
-  double* partial;            // [total chunks][arms][ntaps][2]
-  double* out;                // [nblocks][arms][ntaps][2]
+  const double* freqs;        // [nfreq] Hz; nullptr (the bank): one bin at carr_freq as given, nothing added
+  double* partial;            // [total chunks][arms][nfreq][ntaps][2]
+  double* out;                // [nblocks][arms][nfreq][ntaps][2]
   double fs;
   int nblocks;
   int ntaps;
+  int nfreq;
   int arms;  // arms of the partial / out layout: the most a channel of the call has
 };
 
-template <int MODE>
+template <int MODE, int G>
 __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
-  __shared__ float2 P[kBankChunk + 1];
-  __shared__ float2 wsum[kBankWaves];
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ float2 P[G][kBankChunk + 1];
+  __shared__ float2 wsum[G][kBankWaves];
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  // uniform over the wavefront, which the compiler cannot prove by itself: with it phase B's per-pair values and branches are scalar
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // the block this chunk belongs to: the last b with chunk_base[b] <= blockIdx.x (uniform)
   const int item = (int)blockIdx.x;
   int lo = 0, hi = p.nblocks;
@@ -59,63 +244,80 @@ __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
   const int N = blk.blksize;
   const int i0 = (item - p.chunk_base[lo]) * kBankChunk;
   const int n = min(kBankChunk, N - i0);  // 1 .. kBankChunk samples in this chunk
+  const int m0 = (int)blockIdx.y * G;
+  const int gn = min(G, p.nfreq - m0);  // 1 .. G bins in this group (uniform)
 
-  // ---- phase A: mix, prefix sums --------------------------------------------------------------------------------------------
-  const double tau = blk.carr_freq / p.fs;
-  const double ph0 = blk.rem_carr_phase * 0.15915494309189535;
-#pragma unroll
-  for (int r = 0; r < kBankSPT; ++r) {
-    const int li = r * kBankWG + tid;
-    float2 x = make_float2(0.0f, 0.0f);
-    if (li < n) {
-      float a, b;
-      bank_load_sample<MODE>(p.if_base, blk.first_sample + i0 + li, a, b);
-      const double ph = ph0 + (double)(i0 + li) * tau;
-      float sn, cs;
-      sincospif(2.0f * (float)(ph - floor(ph)), &sn, &cs);
-      x = make_float2(a * cs + b * sn, b * cs - a * sn);
-    }
-    P[li] = x;
-  }
-  __syncthreads();
-  float2 s[kBankSPT];
+  // ---- phase A: the thread's samples once, then per bin mix and prefix sums -------------------------------------------------
+  // (Loading at stride kBankWG through LDS instead, as the bank did while it had a kernel of its own, gives the same values in
+  // the same order and the same times: DESIGN.md 4.6 "compared across the move".)
+  float xa[kBankSPT], xb[kBankSPT];
 #pragma unroll
   for (int q = 0; q < kBankSPT; ++q) {
-    const float2 v = P[kBankSPT * tid + q];
-    s[q] = q == 0 ? v : make_float2(s[q - 1].x + v.x, s[q - 1].y + v.y);
+    const int li = kBankSPT * tid + q;
+    xa[q] = 0.0f;
+    xb[q] = 0.0f;
+    if (li < n) bank_load_sample<MODE>(p.if_base, blk.first_sample + i0 + li, xa[q], xb[q]);
   }
-  float2 incl = s[kBankSPT - 1];  // inclusive scan of the threads' totals over the wave, then the waves before in index order
+  const double ph0 = blk.rem_carr_phase * 0.15915494309189535;
+  float2 s[G][kBankSPT];
+  float2 before[G];
 #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float ux = __shfl_up(incl.x, o, 64), uy = __shfl_up(incl.y, o, 64);
-    if (lane >= o) {
-      incl.x += ux;
-      incl.y += uy;
+  for (int g = 0; g < G; ++g) {
+    if (g < gn) {
+      const double tau = (p.freqs ? __dadd_rn(blk.carr_freq, p.freqs[m0 + g]) : blk.carr_freq) / p.fs;
+#pragma unroll
+      for (int q = 0; q < kBankSPT; ++q) {
+        const int li = kBankSPT * tid + q;
+        float2 x = make_float2(0.0f, 0.0f);
+        if (li < n) {
+          const float a = xa[q], b = xb[q];
+          const double ph = ph0 + (double)(i0 + li) * tau;
+          float sn, cs;
+          sincospif(2.0f * (float)(ph - floor(ph)), &sn, &cs);
+          x = make_float2(a * cs + b * sn, b * cs - a * sn);
+        }
+        s[g][q] = q == 0 ? x : make_float2(s[g][q - 1].x + x.x, s[g][q - 1].y + x.y);
+      }
+      float2 incl = s[g][kBankSPT - 1];  // inclusive scan of the threads' totals over the wave
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const float ux = __shfl_up(incl.x, o, 64), uy = __shfl_up(incl.y, o, 64);
+        if (lane >= o) {
+          incl.x += ux;
+          incl.y += uy;
+        }
+      }
+      if (lane == 63) wsum[g][wave] = incl;
+      // what precedes this thread's samples in its wave: the inclusive value of the lane below (no subtraction, no second rounding)
+      const float ex = __shfl_up(incl.x, 1, 64), ey = __shfl_up(incl.y, 1, 64);
+      before[g] = lane == 0 ? make_float2(0.0f, 0.0f) : make_float2(ex, ey);
     }
   }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();  // every thread has read its samples: P is rewritten in place, shifted by one
-  // what precedes this thread's samples: the inclusive value of the lane below (no subtraction, no second rounding) and the waves before
-  const float ex = __shfl_up(incl.x, 1, 64), ey = __shfl_up(incl.y, 1, 64);
-  float2 before = lane == 0 ? make_float2(0.0f, 0.0f) : make_float2(ex, ey);
-  float2 wbase = make_float2(0.0f, 0.0f);
-  for (int w = 0; w < wave; ++w) {
-    wbase.x += wsum[w].x;
-    wbase.y += wsum[w].y;
-  }
-  before.x += wbase.x;
-  before.y += wbase.y;
+  __syncthreads();
 #pragma unroll
-  for (int q = 0; q < kBankSPT; ++q) P[kBankSPT * tid + q + 1] = make_float2(before.x + s[q].x, before.y + s[q].y);
-  if (tid == 0) P[0] = make_float2(0.0f, 0.0f);
+  for (int g = 0; g < G; ++g) {
+    if (g < gn) {
+      float2 wbase = make_float2(0.0f, 0.0f);  // the waves before, in index order
+      for (int w = 0; w < wave; ++w) {
+        wbase.x += wsum[g][w].x;
+        wbase.y += wsum[g][w].y;
+      }
+      float2 bf = before[g];
+      bf.x += wbase.x;
+      bf.y += wbase.y;
+#pragma unroll
+      for (int q = 0; q < kBankSPT; ++q) P[g][kBankSPT * tid + q + 1] = make_float2(bf.x + s[g][q].x, bf.y + s[g][q].y);
+      if (tid == 0) P[g][0] = make_float2(0.0f, 0.0f);
+    }
+  }
   __syncthreads();
 
-  // ---- phase B: a wavefront per (arm, tap) pair, a lane per table entry the chunk crosses --------------------------------------
+  // ---- phase B: a wavefront per (arm, tap) pair, a lane per table entry the chunk crosses; every boundary once for the group ----
   const int arms = chn->arms;
   const double R = chn->index_scale, rem = blk.rem_code_phase, step = blk.code_phase_step;
   const double nm1s = __dmul_rn((double)(N - 1), step);
   const int i_last = i0 + n - 1;
-  double* __restrict__ prow = p.partial + (long long)item * p.arms * p.ntaps * 2;
+  double* __restrict__ prow = p.partial + (long long)item * p.arms * p.nfreq * p.ntaps * 2;
   for (int pair = wave; pair < arms * p.ntaps; pair += kBankWaves) {
     const int arm = pair / p.ntaps, j = pair - arm * p.ntaps;
     const double o = p.offsets[j];
@@ -128,7 +330,9 @@ __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
     const int8_t* __restrict__ tab = chn->tab[arm];
     const int L = chn->nent[arm] - 2;  // the code's period in entries
     const int k_lo = rp.index(i0), k_hi = rp.index(i_last);
-    float2 acc = make_float2(0.0f, 0.0f);
+    float2 acc[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[g] = make_float2(0.0f, 0.0f);
     for (int k = k_lo + 1 + lane; k <= k_hi; k += 64) {
       int r = (k - 1) % L;
       if (r < 0) r += L;
@@ -137,95 +341,113 @@ __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
       // the smallest sample with index >= k lies in (i0, i_last]: index(i0) < k <= index(i_last)
       const int e = rp.boundary(k, i0, i_last);
       const float d = (float)(c_prev - c_k);
-      const float2 v = P[e - i0];
-      acc.x = fmaf(d, v.x, acc.x);
-      acc.y = fmaf(d, v.y, acc.y);
-    }
 #pragma unroll
-    for (int sh = 32; sh > 0; sh >>= 1) {
-      acc.x += __shfl_down(acc.x, sh, 64);
-      acc.y += __shfl_down(acc.y, sh, 64);
+      for (int g = 0; g < G; ++g) {
+        if (g < gn) {
+          const float2 v = P[g][e - i0];
+          acc[g].x = fmaf(d, v.x, acc[g].x);
+          acc[g].y = fmaf(d, v.y, acc[g].y);
+        }
+      }
     }
-    if (lane == 0) {
-      int r = (k_hi - 1) % L;
-      if (r < 0) r += L;
-      const float c_end = (float)tab[r + 1];
-      prow[2 * pair] = (double)fmaf(c_end, P[n].x, acc.x);
-      prow[2 * pair + 1] = (double)fmaf(c_end, P[n].y, acc.y);
+    int r = (k_hi - 1) % L;
+    if (r < 0) r += L;
+    const float c_end = (float)tab[r + 1];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      if (g < gn) {
+        float2 a = acc[g];
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) {
+          a.x += __shfl_down(a.x, sh, 64);
+          a.y += __shfl_down(a.y, sh, 64);
+        }
+        if (lane == 0) {
+          double* dst = prow + 2 * (((long long)arm * p.nfreq + m0 + g) * p.ntaps + j);
+          dst[0] = (double)fmaf(c_end, P[g][n].x, a.x);
+          dst[1] = (double)fmaf(c_end, P[g][n].y, a.y);
+        }
+      }
     }
   }
 }
 
-// out[b][arm][tap][c] = the block's chunk partials in chunk order; arms the block's channel does not have are zero.
+// out[b][arm][bin][tap][c] = the block's chunk partials in chunk order; arms the block's channel does not have are zero.
 __global__ void bank_combine_kernel(const BankArgs p) {
-  const long long row = (long long)p.arms * p.ntaps * 2;
+  const long long row = (long long)p.arms * p.nfreq * p.ntaps * 2;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)p.nblocks * row) return;
   const int b = (int)(i / row);
   const int v = (int)(i - (long long)b * row);
-  const int arm = v / (2 * p.ntaps);
+  const int arm = v / (2 * p.nfreq * p.ntaps);
   double s = 0.0;
   if (arm < p.chans[p.blocks[b].channel].arms)
     for (int q = p.chunk_base[b]; q < p.chunk_base[b + 1]; ++q) s += p.partial[(long long)q * row + v];
   p.out[i] = s;
 }
 
-}  // namespace
-
-int gc_launch_correlator_bank(gc_context* ctx, const gc_block* d_blocks, int nblocks, const int32_t* d_chunk_base, int total_chunks,
-                              int ntaps, const double* d_offsets, int arms, double* d_partial, double* d_out) {
-  if (nblocks <= 0 || total_chunks <= 0) return GC_OK;
-  BankArgs a;
-  a.if_base = ctx->d_if;
-  a.blocks = d_blocks;
-  a.chans = ctx->d_channels;
-  a.chunk_base = d_chunk_base;
-  a.offsets = d_offsets;
-  a.partial = d_partial;
-  a.out = d_out;
-  a.fs = ctx->fs;
-  a.nblocks = nblocks;
-  a.ntaps = ntaps;
-  a.arms = arms;
-  const dim3 grid((unsigned int)total_chunks), block(kBankWG);
+// The chunk kernel over `total_chunks` work items and the groups of G bins, then the combine.
+template <int G>
+int bank_launch(gc_context* ctx, const BankArgs& a, int total_chunks) {
+  const dim3 grid((unsigned int)total_chunks, (unsigned int)((a.nfreq + G - 1) / G)), block(kBankWG);
   switch (bank_record_mode(ctx)) {
-    case I8_IQ: hipLaunchKernelGGL(bank_chunk_kernel<I8_IQ>, grid, block, 0, ctx->stream, a); break;
-    case I8_QI: hipLaunchKernelGGL(bank_chunk_kernel<I8_QI>, grid, block, 0, ctx->stream, a); break;
-    case I16_IQ: hipLaunchKernelGGL(bank_chunk_kernel<I16_IQ>, grid, block, 0, ctx->stream, a); break;
-    case I16_QI: hipLaunchKernelGGL(bank_chunk_kernel<I16_QI>, grid, block, 0, ctx->stream, a); break;
-    case I8_REAL: hipLaunchKernelGGL(bank_chunk_kernel<I8_REAL>, grid, block, 0, ctx->stream, a); break;
-    default: hipLaunchKernelGGL(bank_chunk_kernel<I16_REAL>, grid, block, 0, ctx->stream, a); break;
+    case I8_IQ: hipLaunchKernelGGL((bank_chunk_kernel<I8_IQ, G>), grid, block, 0, ctx->stream, a); break;
+    case I8_QI: hipLaunchKernelGGL((bank_chunk_kernel<I8_QI, G>), grid, block, 0, ctx->stream, a); break;
+    case I16_IQ: hipLaunchKernelGGL((bank_chunk_kernel<I16_IQ, G>), grid, block, 0, ctx->stream, a); break;
+    case I16_QI: hipLaunchKernelGGL((bank_chunk_kernel<I16_QI, G>), grid, block, 0, ctx->stream, a); break;
+    case I8_REAL: hipLaunchKernelGGL((bank_chunk_kernel<I8_REAL, G>), grid, block, 0, ctx->stream, a); break;
+    default: hipLaunchKernelGGL((bank_chunk_kernel<I16_REAL, G>), grid, block, 0, ctx->stream, a); break;
   }
   GC_HIP(hipGetLastError());
-  const long long nout = (long long)nblocks * arms * ntaps * 2;
+  const long long nout = (long long)a.nblocks * a.arms * a.nfreq * a.ntaps * 2;
   hipLaunchKernelGGL(bank_combine_kernel, dim3((unsigned int)((nout + 255) / 256)), dim3(256), 0, ctx->stream, a);
   GC_HIP(hipGetLastError());
   return GC_OK;
 }
 
-extern "C" int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, double* out) {
-  if (!ctx || nblocks < 0 || !tap_offsets || (nblocks > 0 && (!blocks || !out))) {
-    gc_set_error("gc_correlate_bank: bad arguments");
-    return GC_E_INVALID;
+// Both functions after their argument check.  freq_offsets == nullptr is the bank: one bin (nfreq = 1) at carr_freq as given.
+int bank_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, int nfreq,
+             const double* freq_offsets, double* out) {
+  if (freq_offsets) {
+    if (nfreq < 1 || nfreq > GC_DDM_MAX_FREQS) {
+      gc_set_error("%s: %d frequency bins (1 .. %d)", fn, nfreq, GC_DDM_MAX_FREQS);
+      return GC_E_INVALID;
+    }
+    for (int m = 0; m < nfreq; ++m)
+      if (!std::isfinite(freq_offsets[m])) {
+        gc_set_error("%s: frequency offset %d is not finite", fn, m);
+        return GC_E_INVALID;
+      }
   }
   int arms = 1;
-  int rc = bank_validate("gc_correlate_bank", ctx, nblocks, blocks, ntaps, tap_offsets, &arms);
+  int rc = bank_validate(fn, ctx, nblocks, blocks, ntaps, tap_offsets, &arms);
   if (rc) return rc;
   if (nblocks == 0) return GC_OK;
+  if (freq_offsets)
+    for (int i = 0; i < nblocks; ++i)
+      for (int m = 0; m < nfreq; ++m)
+        if (!std::isfinite(blocks[i].carr_freq + freq_offsets[m])) {  // what the bank answers to that carr_freq
+          gc_set_error("block %d: invalid descriptor (carr_freq + frequency offset %d is not finite)", i, m);
+          return GC_E_INVALID;
+        }
   GC_HIP(hipSetDevice(ctx->device));
   if ((rc = gc_sync_channels(ctx))) return rc;
-  const long long row = (long long)arms * ntaps * 2;  // doubles per chunk (partials) and per block (results)
+  const long long row = (long long)arms * nfreq * ntaps * 2;  // doubles per chunk (partials) and per block (results)
+  const long long full = (long long)GC_MAX_ARMS * nfreq * ntaps * 2;
   const long long max_chunks = std::max<long long>(1, std::min<long long>(kBankPartialBytes / (row * 8), 0x40000000LL));
   GcBuf& bblk = ctx->bank[gc_context::BANK_BLOCKS];
   GcBuf& btap = ctx->bank[gc_context::BANK_TAPS];
+  GcBuf& bfrq = ctx->bank[gc_context::BANK_FREQS];
   GcBuf& bchk = ctx->bank[gc_context::BANK_CHUNKS];
   GcBuf& bpar = ctx->bank[gc_context::BANK_PARTIAL];
   GcBuf& bout = ctx->bank[gc_context::BANK_OUT];
-  if (gc_buf_reserve(btap, sizeof(double) * GC_BANK_MAX_TAPS, false) != hipSuccess) {
-    gc_set_error("gc_correlate_bank: device allocation failed");
+  if (gc_buf_reserve(btap, sizeof(double) * GC_BANK_MAX_TAPS, false) != hipSuccess ||
+      (freq_offsets && gc_buf_reserve(bfrq, sizeof(double) * GC_DDM_MAX_FREQS, false) != hipSuccess)) {
+    gc_set_error("%s: device allocation failed", fn);
     return GC_E_NOMEM;
   }
   GC_HIP(hipMemcpyAsync(btap.p, tap_offsets, sizeof(double) * (size_t)ntaps, hipMemcpyHostToDevice, ctx->stream));
+  if (freq_offsets) GC_HIP(hipMemcpyAsync(bfrq.p, freq_offsets, sizeof(double) * (size_t)nfreq, hipMemcpyHostToDevice, ctx->stream));
   std::vector<int32_t> base;
   std::vector<double> compact;
   for (int first = 0; first < nblocks;) {
@@ -243,15 +465,28 @@ extern "C" int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* b
         gc_buf_reserve(bchk, sizeof(int32_t) * (size_t)(nb + 1), false) != hipSuccess ||
         gc_buf_reserve(bpar, sizeof(double) * (size_t)(chunks * row), false) != hipSuccess ||
         gc_buf_reserve(bout, sizeof(double) * (size_t)(nb * row), false) != hipSuccess) {
-      gc_set_error("gc_correlate_bank: device allocation failed (%d blocks, %lld chunks, %d taps)", nb, chunks, ntaps);
+      if (freq_offsets) gc_set_error("%s: device allocation failed (%d blocks, %lld chunks, %d taps, %d bins)", fn, nb, chunks, ntaps, nfreq);
+      else gc_set_error("%s: device allocation failed (%d blocks, %lld chunks, %d taps)", fn, nb, chunks, ntaps);
       return GC_E_NOMEM;
     }
     GC_HIP(hipMemcpyAsync(bblk.p, blocks + first, sizeof(gc_block) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
     GC_HIP(hipMemcpyAsync(bchk.p, base.data(), sizeof(int32_t) * (size_t)(nb + 1), hipMemcpyHostToDevice, ctx->stream));
-    rc = gc_launch_correlator_bank(ctx, (const gc_block*)bblk.p, nb, (const int32_t*)bchk.p, (int)chunks, ntaps, (const double*)btap.p, arms,
-                                   (double*)bpar.p, (double*)bout.p);
-    if (rc) return rc;
-    double* dst = out + (size_t)first * GC_MAX_ARMS * ntaps * 2;
+    BankArgs a;
+    a.if_base = ctx->d_if;
+    a.blocks = (const gc_block*)bblk.p;
+    a.chans = ctx->d_channels;
+    a.chunk_base = (const int32_t*)bchk.p;
+    a.offsets = (const double*)btap.p;
+    a.freqs = freq_offsets ? (const double*)bfrq.p : nullptr;
+    a.partial = (double*)bpar.p;
+    a.out = (double*)bout.p;
+    a.fs = ctx->fs;
+    a.nblocks = nb;
+    a.ntaps = ntaps;
+    a.nfreq = nfreq;
+    a.arms = arms;
+    if ((rc = freq_offsets ? bank_launch<kDdmGroup>(ctx, a, (int)chunks) : bank_launch<1>(ctx, a, (int)chunks))) return rc;
+    double* dst = out + (size_t)first * full;
     if (arms == GC_MAX_ARMS) {
       GC_HIP(hipMemcpyAsync(dst, bout.p, sizeof(double) * (size_t)(nb * row), hipMemcpyDeviceToHost, ctx->stream));
       GC_HIP(hipStreamSynchronize(ctx->stream));
@@ -260,12 +495,31 @@ extern "C" int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* b
       GC_HIP(hipMemcpyAsync(compact.data(), bout.p, sizeof(double) * compact.size(), hipMemcpyDeviceToHost, ctx->stream));
       GC_HIP(hipStreamSynchronize(ctx->stream));
       for (int b = 0; b < nb; ++b) {
-        double* o = dst + (size_t)b * GC_MAX_ARMS * ntaps * 2;
+        double* o = dst + (size_t)b * full;
         std::memcpy(o, compact.data() + (size_t)b * row, sizeof(double) * (size_t)row);
-        std::memset(o + row, 0, sizeof(double) * (size_t)(GC_MAX_ARMS * ntaps * 2 - row));
+        std::memset(o + row, 0, sizeof(double) * (size_t)(full - row));
       }
     }
     first += nb;
   }
   return GC_OK;
+}
+
+}  // namespace
+
+extern "C" int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, double* out) {
+  if (!ctx || nblocks < 0 || !tap_offsets || (nblocks > 0 && (!blocks || !out))) {
+    gc_set_error("gc_correlate_bank: bad arguments");
+    return GC_E_INVALID;
+  }
+  return bank_run("gc_correlate_bank", ctx, nblocks, blocks, ntaps, tap_offsets, 1, nullptr, out);
+}
+
+extern "C" int gc_correlate_ddm(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, int nfreq,
+                                const double* freq_offsets, double* out) {
+  if (!ctx || nblocks < 0 || !tap_offsets || !freq_offsets || (nblocks > 0 && (!blocks || !out))) {
+    gc_set_error("gc_correlate_ddm: bad arguments");
+    return GC_E_INVALID;
+  }
+  return bank_run("gc_correlate_ddm", ctx, nblocks, blocks, ntaps, tap_offsets, nfreq, freq_offsets, out);
 }

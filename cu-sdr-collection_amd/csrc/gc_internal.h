@@ -263,12 +263,6 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
 // trackResults.CNo.VSMValue of finished records on the host (the host-closed loops; the device loop estimates in one pass inside devloop_post - both end in gcorr::cno_ratio, devloop.h)
 void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const double* out, const int32_t* epochs_done);
 
-// corr_bank.hip (gc_correlate_bank): one launch over the chunks of `nblocks` validated descriptors on the device - chunk_base[b] is
-// the number of chunks (of 1 024 samples, the last of a block shorter) before block b (nblocks + 1 entries) -, then the chunks' float64 partial
-// sums [chunk][arms][ntaps][2] added in chunk order into d_out [nblocks][arms][ntaps][2] (arms a channel does not have: zero).
-int gc_launch_correlator_bank(gc_context* ctx, const gc_block* d_blocks, int nblocks, const int32_t* d_chunk_base, int total_chunks,
-                              int ntaps, const double* d_offsets, int arms, double* d_partial, double* d_out);
-
 int gc_bytes_per_sample(int dtype, int layout);
 void gc_acq_free(gc_context* ctx);  // acq_coarse.hip
 int gc_sync_channels(gc_context* ctx);

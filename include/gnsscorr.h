@@ -175,7 +175,7 @@ int gc_correlate(gc_context* ctx, int nblocks, const gc_block* blocks, double* o
 #define GC_BANK_MAX_TAPS 64
 int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, double* out);
 
-/* The bank's correlation function at `nfreq` carrier offsets as well: a delay-Doppler map of every block (csrc/corr_ddm.hip).
+/* The bank's correlation function at `nfreq` carrier offsets as well: a delay-Doppler map of every block (csrc/corr_bank.hip).
  * Bin m of block b is what gc_correlate_bank returns for the same block with carr_freq replaced by the float64 sum
  * carr_freq + freq_offsets[m] (Hz) - BIT FOR BIT; rem_carr_phase and every other field as they stand, so the carrier phase is
  * referenced to the block's first sample and the bins differ in frequency only.  A result therefore does not depend on which other

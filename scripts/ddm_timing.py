@@ -9,8 +9,8 @@ The two sides' bytes are compared on the way.
 
     python scripts/ddm_timing.py [--reps 15] [--warmup 3] [--grids 33x17,5x64]
 
-Another group size (bins per work item, csrc/corr_ddm.hip) is a throw-away build, never a run-time switch:
-    scripts/variants.sh corr_ddm "DDM4:-DGC_DDM_GROUP=4" "DDM16:-DGC_DDM_GROUP=16"
+Another group size (bins per work item, csrc/corr_bank.hip) is a throw-away build, never a run-time switch:
+    scripts/variants.sh corr_bank "DDM4:-DGC_DDM_GROUP=4" "DDM16:-DGC_DDM_GROUP=16"
     GC_LIB_PATH=cu-sdr-collection_amd/lib/libgnsscorr_DDM4.so python scripts/ddm_timing.py --grids 33x17
 
 --dump-bank FILE writes the bytes gc_correlate_bank returns for the list at the first grid's taps (to compare two builds of the

@@ -1,75 +1,20 @@
 """gc_correlate_bank (csrc/corr_bank.hip): a block's correlation function at many code offsets, against a float64 restatement
-of its definition (include/gnsscorr.h) written here with the oracle's colon().
+of its definition (include/gnsscorr.h) written with the oracle's colon() (tests/bank_cases.py).
 
 Tolerance: 2e-6 of sum |x| over the block, the project's correlator-versus-oracle figure (TOL_ORACLE of
 tests/test_gpu_full_size.py).  One mis-assigned sample of a 4 097-sample block is 2.4e-4 in those units: the bound hides no
 boundary error.  The kernel takes every table boundary from the float64 element rule itself, so ties are exact; what remains is
 float32 mixing and float32 prefix sums restarted every 1 024 samples."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
+from bank_cases import FS, PERIOD_L1, POOL, _blocks, _colon_has_n_elements, _raw, bank_reference, ca_table, noise_record  # noqa: F401  (fixtures)
 from oracle import gnss_oracle as O
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-6
-FS = 18e6
-PERIOD_L1 = 1023.0
-# the offsets the shapes are run at: 0, thirds, halves, whole chips, several chips, and just under a period of the 1 023-chip code
-POOL = [0.0, 1.0 / 3, -1.0 / 3, 0.5, -0.5, 1.0, -1.0, 1.5, -1.5, 17.25, -17.25, 1022.9, -1022.9]
-
-
-def _raw(rec, s0, n, layout="IQ"):
-    """raw = data1 + 1i*data2 of tracking.m:233-235 for the record's sample order (GLONASS: swapped; real: no imaginary part)."""
-    if layout == "REAL":
-        return rec[s0:s0 + n].astype(np.float64).astype(np.complex128)
-    seg = rec[2 * s0:2 * (s0 + n)].astype(np.float64)
-    return seg[1::2] + 1j * seg[0::2] if layout == "QI" else seg[0::2] + 1j * seg[1::2]
-
-
-def bank_reference(raw, tables, rem, step, offsets, carr_freq, rem_carr, fs, r=1.0, arm_mult=None):
-    """The definition, per sample, in float64.  Returns (complex128 [arms, ntaps], number of samples with an integer t_i)."""
-    n = raw.shape[0]
-    arm_mult = arm_mult or [1.0] * len(tables)
-    trig = ((carr_freq * 2.0 * math.pi) * (np.arange(n, dtype=np.float64) / fs)) + rem_carr
-    mixed = np.exp(-1j * trig) * raw
-    out = np.zeros((len(tables), len(offsets)), dtype=np.complex128)
-    ties = 0
-    for j, o in enumerate(offsets):
-        t = O.colon((rem + o) * r, step * r, (((n - 1) * step + rem) + o) * r)
-        assert t.shape[0] == n
-        ties += int(np.sum(t == np.rint(t)))
-        for a, tab in enumerate(tables):
-            p = np.ceil(t * arm_mult[a]).astype(np.int64)           # index into the padded table [c(end) c c(1)] ...
-            c = np.asarray(tab, dtype=np.float64)[1 + np.mod(p - 1, len(tab) - 2)]     # ... read periodically
-            out[a, j] = np.sum(c * mixed)
-    return out, ties
-
-
-def _colon_has_n_elements(d, o, r=1.0):
-    """The definition takes element i of MATLAB's colon vector, so that vector must have N elements.  A block of two or three
-    samples whose start (rem + o) cancels to a few hundredths of a chip has end points that carry more rounding (an ulp of 1) than
-    the colon's own end-point tolerance (2 eps of the LARGER END POINT) forgives: MATLAB then builds N - 1 elements and tracking.m
-    would stop on the size mismatch.  Such a draw is outside the definition and is drawn again; blocks of a code period are never
-    near it (their end point is ~1e3 chips)."""
-    n, rem, step = d["n"], d["rem"], d["step"]
-    return O.colon((rem + o) * r, step * r, (((n - 1) * step + rem) + o) * r).shape[0] == n
-
-
-def _blocks(engine, descs):
-    b = engine.make_blocks(len(descs))
-    for k, d in enumerate(descs):
-        b[k].channel = d.get("channel", 0)
-        b[k].blksize = d["n"]
-        b[k].first_sample = d["s0"]
-        b[k].rem_code_phase = d["rem"]
-        b[k].code_phase_step = d["step"]
-        b[k].el_spacing = d.get("d", 0.0)
-        b[k].carr_freq = d["f"]
-        b[k].rem_carr_phase = d["phi"]
-    return b
 
 
 def _check(engine, rec, descs, offsets, tables, r=1.0, arm_mult=None, layout="IQ", label=""):
@@ -89,17 +34,6 @@ def _check(engine, rec, descs, offsets, tables, r=1.0, arm_mult=None, layout="IQ
         assert not got[k, len(tables):].any(), (label, k)
     print(f"{label}: worst {worst:.3e} of sum |x| (bound {TOL:.1e})")
     return worst, ties
-
-
-@pytest.fixture(scope="module")
-def noise_record():
-    """Random full-range int8 I/Q samples."""
-    return np.random.default_rng(20241018).integers(-128, 128, size=2 * 60000, dtype=np.int8)
-
-
-@pytest.fixture(scope="module")
-def ca_table():
-    return O.pad_code(O.generate_ca_code(7)).astype(np.int8)
 
 
 @pytest.mark.parametrize("ntaps", [1, 2, 3, 33, 64])

@@ -1,8 +1,8 @@
-"""gc_correlate_ddm (csrc/corr_ddm.hip): a block's correlation over code taps and carrier bins.
+"""gc_correlate_ddm (csrc/corr_bank.hip): a block's correlation over code taps and carrier bins.
 
 The contract is an identity (include/gnsscorr.h): bin m is gc_correlate_bank on the block with carr_freq replaced by the float64 sum
 carr_freq + freq_offsets[m], BIT FOR BIT.  So the first check is bytes against Engine.correlate_bank, bin by bin; the second is a
-float64 per-sample restatement written here with the oracle's colon() (the bank test's definition at carr_freq + f_m).
+float64 per-sample restatement written with the oracle's colon() (tests/bank_cases.py: the bank's definition at carr_freq + f_m).
 
 Tolerance of the restatement: 2e-6 of sum |x| over the block, the project's correlator-versus-oracle figure (the bank's TOL).  One
 mis-assigned sample of a 4 097-sample block is 2.4e-4 in those units.
@@ -10,74 +10,17 @@ mis-assigned sample of a 4 097-sample block is 2.4e-4 in those units.
 The kernel takes bins in groups of 4 per work item: the bin counts run over 1, one short of a group, a group, one more, two groups
 and one (for groups of 4 and of 8), 17 and the limit of 64."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
+from bank_cases import FS, PERIOD_L1, POOL, _blocks, _colon_has_n_elements, _raw, ca_table, ddm_reference, noise_record  # noqa: F401  (fixtures)
 from oracle import gnss_oracle as O
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-6
-FS = 18e6
-PERIOD_L1 = 1023.0
-# the bank test's offsets: 0, thirds, halves, whole chips, several chips, and just under a period of the 1 023-chip code
-POOL = [0.0, 1.0 / 3, -1.0 / 3, 0.5, -0.5, 1.0, -1.0, 1.5, -1.5, 17.25, -17.25, 1022.9, -1022.9]
 FREQ_POOL = [0.0, 0.37, -0.37, 250.0, -250.0, 500.0, -500.0, 1e3, -1e3, 1e4, -1e4, 4.5e6, -4.5e6]
-PARTIAL_BUDGET = 256 << 20     # the library's budget for one sub-batch's partial sums (csrc/bank_common.h kBankPartialBytes)
-
-
-def _raw(rec, s0, n, layout="IQ"):
-    """raw = data1 + 1i*data2 of tracking.m:233-235 for the record's sample order (GLONASS: swapped; real: no imaginary part)."""
-    if layout == "REAL":
-        return rec[s0:s0 + n].astype(np.float64).astype(np.complex128)
-    seg = rec[2 * s0:2 * (s0 + n)].astype(np.float64)
-    return seg[1::2] + 1j * seg[0::2] if layout == "QI" else seg[0::2] + 1j * seg[1::2]
-
-
-def ddm_reference(raw, tables, rem, step, offsets, carr_freq, freqs, rem_carr, fs, r=1.0, arm_mult=None):
-    """The definition, per sample, in float64: the bank's with carr_freq + f_m.  Returns (complex128 [arms, nfreq, ntaps], number of
-    samples with an integer t_i over the taps)."""
-    n = raw.shape[0]
-    arm_mult = arm_mult or [1.0] * len(tables)
-    code = np.zeros((len(tables), len(offsets), n))
-    ties = 0
-    for j, o in enumerate(offsets):
-        t = O.colon((rem + o) * r, step * r, (((n - 1) * step + rem) + o) * r)
-        assert t.shape[0] == n
-        ties += int(np.sum(t == np.rint(t)))
-        for a, tab in enumerate(tables):
-            p = np.ceil(t * arm_mult[a]).astype(np.int64)           # index into the padded table [c(end) c c(1)] ...
-            code[a, j] = np.asarray(tab, dtype=np.float64)[1 + np.mod(p - 1, len(tab) - 2)]     # ... read periodically
-    out = np.zeros((len(tables), len(freqs), len(offsets)), dtype=np.complex128)
-    for m, f in enumerate(freqs):
-        cf = float(np.float64(carr_freq) + np.float64(f))
-        trig = ((cf * 2.0 * math.pi) * (np.arange(n, dtype=np.float64) / fs)) + rem_carr
-        mixed = np.exp(-1j * trig) * raw
-        out[:, m, :] = code @ mixed
-    return out, ties
-
-
-def _colon_has_n_elements(d, o, r=1.0):
-    """The bank test's rule: the definition takes element i of MATLAB's colon vector, so that vector must have N elements; a draw
-    whose colon comes out one short (two or three samples, a start that cancels to hundredths of a chip) is outside the definition
-    and is drawn again."""
-    n, rem, step = d["n"], d["rem"], d["step"]
-    return O.colon((rem + o) * r, step * r, (((n - 1) * step + rem) + o) * r).shape[0] == n
-
-
-def _blocks(engine, descs, df=0.0):
-    b = engine.make_blocks(len(descs))
-    for k, d in enumerate(descs):
-        b[k].channel = d.get("channel", 0)
-        b[k].blksize = d["n"]
-        b[k].first_sample = d["s0"]
-        b[k].rem_code_phase = d["rem"]
-        b[k].code_phase_step = d["step"]
-        b[k].el_spacing = d.get("d", 0.0)
-        b[k].carr_freq = float(np.float64(d["f"]) + np.float64(df))
-        b[k].rem_carr_phase = d["phi"]
-    return b
+PARTIAL_BUDGET = 256 << 20     # the library's budget for one sub-batch's partial sums (csrc/corr_bank.hip kBankPartialBytes)
 
 
 def _check(engine, rec, descs, offsets, freqs, tables, r=1.0, arm_mult=None, layout="IQ", label=""):
@@ -97,17 +40,6 @@ def _check(engine, rec, descs, offsets, freqs, tables, r=1.0, arm_mult=None, lay
         assert not got[k, len(tables):].any(), (label, k)
     print(f"{label}: worst {worst:.3e} of sum |x| (bound {TOL:.1e})")
     return worst, ties
-
-
-@pytest.fixture(scope="module")
-def noise_record():
-    """Random full-range int8 I/Q samples."""
-    return np.random.default_rng(20241018).integers(-128, 128, size=2 * 60000, dtype=np.int8)
-
-
-@pytest.fixture(scope="module")
-def ca_table():
-    return O.pad_code(O.generate_ca_code(7)).astype(np.int8)
 
 
 def _draw_bins(rng, nfreq):
