@@ -143,6 +143,9 @@ SYMBOLS = {
     "gc_correlate_bank": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gc_correlate_ddm": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)]),
+    "gc_correlate_ddm_integrate": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int,
+                                             C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gc_replay_prepare": (C.c_int, [_P, C.c_int64, C.POINTER(gc_block)]),
     "gc_replay_launch": (C.c_int, [_P]),
     "gc_replay_fetch": (C.c_int, [_P, C.POINTER(C.c_double)]),

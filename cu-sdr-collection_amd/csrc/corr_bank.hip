@@ -1,5 +1,7 @@
-// corr_bank.hip — gc_correlate_bank: the correlation function of a block at up to GC_BANK_MAX_TAPS code offsets, and
-// gc_correlate_ddm: the same at up to GC_DDM_MAX_FREQS carrier offsets as well (a delay-Doppler map).
+// corr_bank.hip — gc_correlate_bank: the correlation function of a block at up to GC_BANK_MAX_TAPS code offsets,
+// gc_correlate_ddm: the same at up to GC_DDM_MAX_FREQS carrier offsets as well (a delay-Doppler map), and
+// gc_correlate_ddm_integrate: those maps added coherently over runs of blocks, then as power over runs, where the chunk partials are
+// (its kernels and driver: the last part of this file).
 //
 // The DDM is defined as an identity: bin m of a block is what the bank returns for the block with carr_freq replaced by the
 // float64 sum carr_freq + freq_offsets[m], bit for bit.  The code says so: one chunk kernel over (record format, G bins per work
@@ -386,9 +388,9 @@ __global__ void bank_combine_kernel(const BankArgs p) {
   p.out[i] = s;
 }
 
-// The chunk kernel over `total_chunks` work items and the groups of G bins, then the combine.
+// The chunk kernel over `total_chunks` work items and the groups of G bins.
 template <int G>
-int bank_launch(gc_context* ctx, const BankArgs& a, int total_chunks) {
+int bank_launch_chunks(gc_context* ctx, const BankArgs& a, int total_chunks) {
   const dim3 grid((unsigned int)total_chunks, (unsigned int)((a.nfreq + G - 1) / G)), block(kBankWG);
   switch (bank_record_mode(ctx)) {
     case I8_IQ: hipLaunchKernelGGL((bank_chunk_kernel<I8_IQ, G>), grid, block, 0, ctx->stream, a); break;
@@ -399,15 +401,14 @@ int bank_launch(gc_context* ctx, const BankArgs& a, int total_chunks) {
     default: hipLaunchKernelGGL((bank_chunk_kernel<I16_REAL, G>), grid, block, 0, ctx->stream, a); break;
   }
   GC_HIP(hipGetLastError());
-  const long long nout = (long long)a.nblocks * a.arms * a.nfreq * a.ntaps * 2;
-  hipLaunchKernelGGL(bank_combine_kernel, dim3((unsigned int)((nout + 255) / 256)), dim3(256), 0, ctx->stream, a);
-  GC_HIP(hipGetLastError());
   return GC_OK;
 }
 
-// Both functions after their argument check.  freq_offsets == nullptr is the bank: one bin (nfreq = 1) at carr_freq as given.
-int bank_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, int nfreq,
-             const double* freq_offsets, double* out) {
+// ---- what gc_correlate_bank / gc_correlate_ddm (bank_run) and gc_correlate_ddm_integrate (ddm_integrate_run) share ------------------
+
+// The argument check of the functions defined through the bank.  freq_offsets == nullptr is the bank itself.
+int bank_check(const char* fn, const gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, int nfreq,
+               const double* freq_offsets, int* arms) {
   if (freq_offsets) {
     if (nfreq < 1 || nfreq > GC_DDM_MAX_FREQS) {
       gc_set_error("%s: %d frequency bins (1 .. %d)", fn, nfreq, GC_DDM_MAX_FREQS);
@@ -419,10 +420,8 @@ int bank_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* block
         return GC_E_INVALID;
       }
   }
-  int arms = 1;
-  int rc = bank_validate(fn, ctx, nblocks, blocks, ntaps, tap_offsets, &arms);
+  int rc = bank_validate(fn, ctx, nblocks, blocks, ntaps, tap_offsets, arms);
   if (rc) return rc;
-  if (nblocks == 0) return GC_OK;
   if (freq_offsets)
     for (int i = 0; i < nblocks; ++i)
       for (int m = 0; m < nfreq; ++m)
@@ -430,17 +429,16 @@ int bank_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* block
           gc_set_error("block %d: invalid descriptor (carr_freq + frequency offset %d is not finite)", i, m);
           return GC_E_INVALID;
         }
+  return GC_OK;
+}
+
+// The channels, the tap offsets and the frequency offsets on the device.
+int bank_upload_grids(const char* fn, gc_context* ctx, int ntaps, const double* tap_offsets, int nfreq, const double* freq_offsets) {
   GC_HIP(hipSetDevice(ctx->device));
-  if ((rc = gc_sync_channels(ctx))) return rc;
-  const long long row = (long long)arms * nfreq * ntaps * 2;  // doubles per chunk (partials) and per block (results)
-  const long long full = (long long)GC_MAX_ARMS * nfreq * ntaps * 2;
-  const long long max_chunks = std::max<long long>(1, std::min<long long>(kBankPartialBytes / (row * 8), 0x40000000LL));
-  GcBuf& bblk = ctx->bank[gc_context::BANK_BLOCKS];
+  int rc = gc_sync_channels(ctx);
+  if (rc) return rc;
   GcBuf& btap = ctx->bank[gc_context::BANK_TAPS];
   GcBuf& bfrq = ctx->bank[gc_context::BANK_FREQS];
-  GcBuf& bchk = ctx->bank[gc_context::BANK_CHUNKS];
-  GcBuf& bpar = ctx->bank[gc_context::BANK_PARTIAL];
-  GcBuf& bout = ctx->bank[gc_context::BANK_OUT];
   if (gc_buf_reserve(btap, sizeof(double) * GC_BANK_MAX_TAPS, false) != hipSuccess ||
       (freq_offsets && gc_buf_reserve(bfrq, sizeof(double) * GC_DDM_MAX_FREQS, false) != hipSuccess)) {
     gc_set_error("%s: device allocation failed", fn);
@@ -448,59 +446,364 @@ int bank_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* block
   }
   GC_HIP(hipMemcpyAsync(btap.p, tap_offsets, sizeof(double) * (size_t)ntaps, hipMemcpyHostToDevice, ctx->stream));
   if (freq_offsets) GC_HIP(hipMemcpyAsync(bfrq.p, freq_offsets, sizeof(double) * (size_t)nfreq, hipMemcpyHostToDevice, ctx->stream));
+  return GC_OK;
+}
+
+// Chunks whose partial sums (`row` doubles each) fit the budget of one sub-batch.
+long long bank_max_chunks(long long row) { return std::max<long long>(1, std::min<long long>(kBankPartialBytes / (row * 8), 0x40000000LL)); }
+
+// The sub-batch that begins at block `first`: blocks while their chunks' partial sums fit (one block at least).  base[k] = chunks
+// before its block k; returns the number of blocks.
+int bank_cut(const gc_block* blocks, int nblocks, int first, long long max_chunks, std::vector<int32_t>& base) {
+  base.assign(1, 0);
+  int nb = 0;
+  while (first + nb < nblocks) {
+    const long long c = ((long long)blocks[first + nb].blksize + kBankChunk - 1) / kBankChunk;
+    if (nb > 0 && base.back() + c > max_chunks) break;
+    base.push_back((int32_t)(base.back() + c));
+    ++nb;
+  }
+  return nb;
+}
+
+int bank_nomem(const char* fn, bool ddm, int nb, long long chunks, int ntaps, int nfreq) {
+  if (ddm) gc_set_error("%s: device allocation failed (%d blocks, %lld chunks, %d taps, %d bins)", fn, nb, chunks, ntaps, nfreq);
+  else gc_set_error("%s: device allocation failed (%d blocks, %lld chunks, %d taps)", fn, nb, chunks, ntaps);
+  return GC_E_NOMEM;
+}
+
+// A sub-batch's descriptors and chunk index to the device, room for its partial sums, and the chunk kernel.  *a: the arguments the
+// kernels after it take (`out` is the caller's to set).
+int bank_chunks(const char* fn, gc_context* ctx, const gc_block* blocks, int nb, const std::vector<int32_t>& base, int ntaps, int nfreq,
+                bool ddm, int arms, BankArgs* a) {
+  const long long row = (long long)arms * nfreq * ntaps * 2, chunks = base.back();
+  GcBuf& bblk = ctx->bank[gc_context::BANK_BLOCKS];
+  GcBuf& bchk = ctx->bank[gc_context::BANK_CHUNKS];
+  GcBuf& bpar = ctx->bank[gc_context::BANK_PARTIAL];
+  if (gc_buf_reserve(bblk, sizeof(gc_block) * (size_t)nb, false) != hipSuccess ||
+      gc_buf_reserve(bchk, sizeof(int32_t) * (size_t)(nb + 1), false) != hipSuccess ||
+      gc_buf_reserve(bpar, sizeof(double) * (size_t)(chunks * row), false) != hipSuccess)
+    return bank_nomem(fn, ddm, nb, chunks, ntaps, nfreq);
+  GC_HIP(hipMemcpyAsync(bblk.p, blocks, sizeof(gc_block) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
+  GC_HIP(hipMemcpyAsync(bchk.p, base.data(), sizeof(int32_t) * (size_t)(nb + 1), hipMemcpyHostToDevice, ctx->stream));
+  a->if_base = ctx->d_if;
+  a->blocks = (const gc_block*)bblk.p;
+  a->chans = ctx->d_channels;
+  a->chunk_base = (const int32_t*)bchk.p;
+  a->offsets = (const double*)ctx->bank[gc_context::BANK_TAPS].p;
+  a->freqs = ddm ? (const double*)ctx->bank[gc_context::BANK_FREQS].p : nullptr;
+  a->partial = (double*)bpar.p;
+  a->out = nullptr;
+  a->fs = ctx->fs;
+  a->nblocks = nb;
+  a->ntaps = ntaps;
+  a->nfreq = nfreq;
+  a->arms = arms;
+  return ddm ? bank_launch_chunks<kDdmGroup>(ctx, *a, (int)chunks) : bank_launch_chunks<1>(ctx, *a, (int)chunks);
+}
+
+// n device rows of `row` doubles to host rows of `full` >= row doubles; waits for the stream.  The device rows hold the call's arms
+// only: the others are zero on the host's side.
+int bank_fetch(gc_context* ctx, double* dst, const void* src, long long n, long long row, long long full, std::vector<double>& compact) {
+  if (row == full) {
+    GC_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)(n * row), hipMemcpyDeviceToHost, ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
+    return GC_OK;
+  }
+  compact.resize((size_t)(n * row));
+  GC_HIP(hipMemcpyAsync(compact.data(), src, sizeof(double) * compact.size(), hipMemcpyDeviceToHost, ctx->stream));
+  GC_HIP(hipStreamSynchronize(ctx->stream));
+  for (long long b = 0; b < n; ++b) {
+    double* o = dst + (size_t)b * full;
+    std::memcpy(o, compact.data() + (size_t)b * row, sizeof(double) * (size_t)row);
+    std::memset(o + row, 0, sizeof(double) * (size_t)(full - row));
+  }
+  return GC_OK;
+}
+
+// gc_correlate_bank and gc_correlate_ddm after their argument check.  freq_offsets == nullptr is the bank: one bin (nfreq = 1) at
+// carr_freq as given.
+int bank_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, int nfreq,
+             const double* freq_offsets, double* out) {
+  int arms = 1;
+  int rc = bank_check(fn, ctx, nblocks, blocks, ntaps, tap_offsets, nfreq, freq_offsets, &arms);
+  if (rc) return rc;
+  if (nblocks == 0) return GC_OK;
+  if ((rc = bank_upload_grids(fn, ctx, ntaps, tap_offsets, nfreq, freq_offsets))) return rc;
+  const long long row = (long long)arms * nfreq * ntaps * 2;  // doubles per chunk (partials) and per block (results)
+  const long long full = (long long)GC_MAX_ARMS * nfreq * ntaps * 2;
+  const long long max_chunks = bank_max_chunks(row);
+  GcBuf& bout = ctx->bank[gc_context::BANK_OUT];
   std::vector<int32_t> base;
   std::vector<double> compact;
   for (int first = 0; first < nblocks;) {
-    // the sub-batch: blocks from `first` while their chunks' partial sums fit (one block at least)
-    base.assign(1, 0);
-    int nb = 0;
-    while (first + nb < nblocks) {
-      const long long c = ((long long)blocks[first + nb].blksize + kBankChunk - 1) / kBankChunk;
-      if (nb > 0 && base.back() + c > max_chunks) break;
-      base.push_back((int32_t)(base.back() + c));
-      ++nb;
-    }
-    const long long chunks = base.back();
-    if (gc_buf_reserve(bblk, sizeof(gc_block) * (size_t)nb, false) != hipSuccess ||
-        gc_buf_reserve(bchk, sizeof(int32_t) * (size_t)(nb + 1), false) != hipSuccess ||
-        gc_buf_reserve(bpar, sizeof(double) * (size_t)(chunks * row), false) != hipSuccess ||
-        gc_buf_reserve(bout, sizeof(double) * (size_t)(nb * row), false) != hipSuccess) {
-      if (freq_offsets) gc_set_error("%s: device allocation failed (%d blocks, %lld chunks, %d taps, %d bins)", fn, nb, chunks, ntaps, nfreq);
-      else gc_set_error("%s: device allocation failed (%d blocks, %lld chunks, %d taps)", fn, nb, chunks, ntaps);
-      return GC_E_NOMEM;
-    }
-    GC_HIP(hipMemcpyAsync(bblk.p, blocks + first, sizeof(gc_block) * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
-    GC_HIP(hipMemcpyAsync(bchk.p, base.data(), sizeof(int32_t) * (size_t)(nb + 1), hipMemcpyHostToDevice, ctx->stream));
+    const int nb = bank_cut(blocks, nblocks, first, max_chunks, base);
+    if (gc_buf_reserve(bout, sizeof(double) * (size_t)(nb * row), false) != hipSuccess)
+      return bank_nomem(fn, freq_offsets != nullptr, nb, base.back(), ntaps, nfreq);
     BankArgs a;
-    a.if_base = ctx->d_if;
-    a.blocks = (const gc_block*)bblk.p;
-    a.chans = ctx->d_channels;
-    a.chunk_base = (const int32_t*)bchk.p;
-    a.offsets = (const double*)btap.p;
-    a.freqs = freq_offsets ? (const double*)bfrq.p : nullptr;
-    a.partial = (double*)bpar.p;
+    if ((rc = bank_chunks(fn, ctx, blocks + first, nb, base, ntaps, nfreq, freq_offsets != nullptr, arms, &a))) return rc;
     a.out = (double*)bout.p;
-    a.fs = ctx->fs;
-    a.nblocks = nb;
-    a.ntaps = ntaps;
-    a.nfreq = nfreq;
-    a.arms = arms;
-    if ((rc = freq_offsets ? bank_launch<kDdmGroup>(ctx, a, (int)chunks) : bank_launch<1>(ctx, a, (int)chunks))) return rc;
-    double* dst = out + (size_t)first * full;
-    if (arms == GC_MAX_ARMS) {
-      GC_HIP(hipMemcpyAsync(dst, bout.p, sizeof(double) * (size_t)(nb * row), hipMemcpyDeviceToHost, ctx->stream));
-      GC_HIP(hipStreamSynchronize(ctx->stream));
-    } else {  // the device rows hold the call's arms only: the others are zero on the host's side
-      compact.resize((size_t)(nb * row));
-      GC_HIP(hipMemcpyAsync(compact.data(), bout.p, sizeof(double) * compact.size(), hipMemcpyDeviceToHost, ctx->stream));
-      GC_HIP(hipStreamSynchronize(ctx->stream));
-      for (int b = 0; b < nb; ++b) {
-        double* o = dst + (size_t)b * full;
-        std::memcpy(o, compact.data() + (size_t)b * row, sizeof(double) * (size_t)row);
-        std::memset(o + row, 0, sizeof(double) * (size_t)(full - row));
-      }
-    }
+    hipLaunchKernelGGL(bank_combine_kernel, dim3((unsigned int)((nb * row + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    GC_HIP(hipGetLastError());
+    if ((rc = bank_fetch(ctx, out + (size_t)first * full, bout.p, nb, row, full, compact))) return rc;
     first += nb;
+  }
+  return GC_OK;
+}
+
+// ---- gc_correlate_ddm_integrate: the DDM's cells added coherently over runs of blocks, then as power over runs ----------------------
+//
+// The chunk kernel's partials [chunk][arm][bin][tap] stay where they are.  ddm_integrate_kernel, a thread per cell (run, arm, bin,
+// tap), adds each block's partials in chunk order - bank_combine_kernel's sum, so D is the DDM's bits -, rotates by the (block, bin)
+// phasor ddm_rotation_kernel left in a scratch array, weights and accumulates in block order.  ddm_power_kernel, a thread per map
+// cell, adds the runs' powers in run order.  A run or map the sub-batch walk cuts goes on from its own float64 accumulators in the
+// next sub-batch: the additions are the same ones in the same order wherever the cut falls.
+
+struct DdmBlockAux {
+  long long dn;  // first_sample - first_sample of the run's first block
+  double w;      // the block's weight
+};
+
+struct DdmArgs {
+  const gc_block* blocks;
+  const DevChannel* chans;
+  const int32_t* chunk_base;  // [nblocks + 1]
+  const double* freqs;        // [nfreq]
+  const DdmBlockAux* aux;     // [nblocks]
+  const double2* partial;     // [total chunks][arms][nfreq][ntaps]
+  double2* rot;               // [nblocks][nfreq]: (cospi(2u), sinpi(2u))
+  const int32_t* run_base;    // [nruns + 1]: the sub-batch's blocks before run r
+  double2* coh;               // [nruns][arms][nfreq][ntaps]
+  const int32_t* map_base;    // [nmaps + 1]: the sub-batch's finished runs before map q
+  double* pow;                // [nmaps][arms][nfreq][ntaps]
+  double fs;
+  int nblocks, ntaps, nfreq, arms, nruns, nmaps;
+  int carry_run;  // run 0 began in an earlier sub-batch: its cells go on from coh[0]
+  int carry_map;  // map 0 likewise, from pow[0]
+};
+
+__global__ void ddm_rotation_kernel(const DdmArgs p) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)p.nblocks * p.nfreq) return;
+  const int b = (int)(i / p.nfreq), m = (int)(i - (long long)b * p.nfreq);
+  const double x = __dmul_rn(p.freqs[m], (double)p.aux[b].dn) / p.fs;
+  const double u = x - rint(x);
+  double s, c;
+  sincospi(2.0 * u, &s, &c);
+  p.rot[i] = make_double2(c, s);
+}
+
+__global__ __launch_bounds__(256) void ddm_integrate_kernel(const DdmArgs p) {
+  const int plane = p.nfreq * p.ntaps;
+  const long long cells = (long long)p.arms * plane;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)p.nruns * cells) return;
+  const int r = (int)(i / cells);
+  const int v = (int)(i - (long long)r * cells);  // (arm, bin, tap), the tap fastest: a wavefront reads consecutive cells of a partial row
+  const int arm = v / plane, m = (v - arm * plane) / p.ntaps;
+  double re = 0.0, im = 0.0;
+  if (r == 0 && p.carry_run) {
+    re = p.coh[i].x;
+    im = p.coh[i].y;
+  }
+  const int b0 = p.run_base[r], b1 = p.run_base[r + 1];
+  if (arm < p.chans[p.blocks[b0].channel].arms)
+    for (int b = b0; b < b1; ++b) {
+      double dr = 0.0, di = 0.0;
+      for (int q = p.chunk_base[b]; q < p.chunk_base[b + 1]; ++q) {
+        const double2 t = p.partial[(long long)q * cells + v];
+        dr += t.x;
+        di += t.y;
+      }
+      const double2 cs = p.rot[(long long)b * p.nfreq + m];
+      const double w = p.aux[b].w;
+      re += w * (cs.x * dr + cs.y * di);
+      im += w * (cs.x * di - cs.y * dr);
+    }
+  p.coh[i] = make_double2(re, im);
+}
+
+__global__ __launch_bounds__(256) void ddm_power_kernel(const DdmArgs p) {
+  const long long cells = (long long)p.arms * p.nfreq * p.ntaps;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)p.nmaps * cells) return;
+  const int q = (int)(i / cells);
+  const long long v = i - (long long)q * cells;
+  double acc = q == 0 && p.carry_map ? p.pow[i] : 0.0;
+  for (int r = p.map_base[q]; r < p.map_base[q + 1]; ++r) {
+    const double2 z = p.coh[(long long)r * cells + v];
+    acc += (z.x * z.x + z.y * z.y);
+  }
+  p.pow[i] = acc;
+}
+
+// One sub-batch of the integrating walk: its blocks [first, first + nb), the runs r0 .. r0 + nr - 1 that have blocks in it - the
+// first nfin of them end in it -, and the maps q0 .. q0 + nm - 1 those finished runs belong to, the first mfin of which end with them.
+struct DdmStep {
+  int first = 0, nb = 0;
+  int r0 = 0, nr = 0, nfin = 0;
+  int q0 = 0, nm = 0, mfin = 0;
+};
+
+// The step after `s` (s.nb == 0: the first).  run_start / map_start: blocks before run r / runs before map q.
+void ddm_next_step(DdmStep& s, const gc_block* blocks, int nblocks, long long max_chunks, const std::vector<int>& run_start,
+                   const std::vector<int>& map_start, std::vector<int32_t>& base) {
+  s.first += s.nb;
+  s.r0 += s.nfin;
+  s.q0 += s.mfin;
+  s.nb = bank_cut(blocks, nblocks, s.first, max_chunks, base);
+  const int end = s.first + s.nb;
+  int r1 = s.r0;
+  while (run_start[r1 + 1] < end) ++r1;
+  s.nr = r1 - s.r0 + 1;
+  s.nfin = run_start[r1 + 1] == end ? s.nr : s.nr - 1;
+  s.nm = s.mfin = 0;
+  if (map_start.size() > 1 && s.nfin > 0) {
+    const int rend = s.r0 + s.nfin;
+    int q1 = s.q0;
+    while (map_start[q1 + 1] < rend) ++q1;
+    s.nm = q1 - s.q0 + 1;
+    s.mfin = map_start[q1 + 1] == rend ? s.nm : s.nm - 1;
+  }
+}
+
+int ddm_integrate_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* blocks, const double* weights, int ntaps,
+                      const double* tap_offsets, int nfreq, const double* freq_offsets, int nruns, const int32_t* run_len, int nmaps,
+                      const int32_t* map_len, double* coh, double* pow) {
+  int arms = 1;
+  int rc = bank_check(fn, ctx, nblocks, blocks, ntaps, tap_offsets, nfreq, freq_offsets, &arms);
+  if (rc) return rc;
+  if (nmaps < 0 || (nblocks > 0 && nruns < 1)) {
+    gc_set_error("%s: %d runs, %d maps for %d blocks", fn, nruns, nmaps, nblocks);
+    return GC_E_INVALID;
+  }
+  std::vector<int> run_start(1, 0), map_start(1, 0);  // blocks before run r, runs before map q
+  for (int r = 0; r < nruns; ++r) {
+    if (run_len[r] < 1 || run_len[r] > nblocks - run_start.back()) {
+      gc_set_error("%s: run %d has %d blocks (1 at least, %d in all)", fn, r, (int)run_len[r], nblocks);
+      return GC_E_INVALID;
+    }
+    run_start.push_back(run_start.back() + run_len[r]);
+  }
+  if (run_start.back() != nblocks) {
+    gc_set_error("%s: the runs hold %d blocks of %d", fn, run_start.back(), nblocks);
+    return GC_E_INVALID;
+  }
+  for (int q = 0; q < nmaps; ++q) {
+    if (map_len[q] < 1 || map_len[q] > nruns - map_start.back()) {
+      gc_set_error("%s: map %d has %d runs (1 at least, %d in all)", fn, q, (int)map_len[q], nruns);
+      return GC_E_INVALID;
+    }
+    map_start.push_back(map_start.back() + map_len[q]);
+  }
+  if (nmaps > 0 && map_start.back() != nruns) {
+    gc_set_error("%s: the maps hold %d runs of %d", fn, map_start.back(), nruns);
+    return GC_E_INVALID;
+  }
+  for (int r = 0; r < nruns; ++r)
+    for (int b = run_start[r] + 1; b < run_start[r + 1]; ++b)
+      if (blocks[b].channel != blocks[run_start[r]].channel) {
+        gc_set_error("%s: run %d has blocks of channels %d and %d", fn, r, blocks[run_start[r]].channel, blocks[b].channel);
+        return GC_E_INVALID;
+      }
+  if (weights)
+    for (int b = 0; b < nblocks; ++b)
+      if (!std::isfinite(weights[b])) {
+        gc_set_error("%s: the weight of block %d is not finite", fn, b);
+        return GC_E_INVALID;
+      }
+  if (nmaps > 0 ? !pow : !coh) {
+    gc_set_error(nmaps > 0 ? "%s: power maps asked for without an output" : "%s: neither coherent sums nor power maps asked for", fn);
+    return GC_E_INVALID;
+  }
+  if (nblocks == 0) return GC_OK;
+  if ((rc = bank_upload_grids(fn, ctx, ntaps, tap_offsets, nfreq, freq_offsets))) return rc;
+  const long long cells = (long long)arms * nfreq * ntaps, full = (long long)GC_MAX_ARMS * nfreq * ntaps;
+  const long long max_chunks = bank_max_chunks(2 * cells);
+  std::vector<int32_t> base, index, mindex;  // chunks before a block, blocks before a run, finished runs before a map: of a sub-batch
+  // The walk once without the device: the most blocks, runs and maps a sub-batch holds.  The accumulators a cut run or map goes on
+  // from live in these buffers, so they must not be reallocated during the walk.
+  int max_nb = 0, max_nr = 0, max_nm = 0;
+  for (DdmStep s; s.first + s.nb < nblocks;) {
+    ddm_next_step(s, blocks, nblocks, max_chunks, run_start, map_start, base);
+    max_nb = std::max(max_nb, s.nb);
+    max_nr = std::max(max_nr, s.nr);
+    max_nm = std::max(max_nm, s.nm);
+  }
+  GcBuf& baux = ctx->bank[gc_context::BANK_AUX];
+  GcBuf& brot = ctx->bank[gc_context::BANK_ROT];
+  GcBuf& brun = ctx->bank[gc_context::BANK_RUNS];
+  GcBuf& bcoh = ctx->bank[gc_context::BANK_COH];
+  GcBuf& bmap = ctx->bank[gc_context::BANK_MAPS];
+  GcBuf& bpow = ctx->bank[gc_context::BANK_POW];
+  if (gc_buf_reserve(baux, sizeof(DdmBlockAux) * (size_t)max_nb, false) != hipSuccess ||
+      gc_buf_reserve(brot, sizeof(double2) * (size_t)max_nb * (size_t)nfreq, false) != hipSuccess ||
+      gc_buf_reserve(brun, sizeof(int32_t) * (size_t)(max_nr + 1), false) != hipSuccess ||
+      gc_buf_reserve(bcoh, sizeof(double2) * (size_t)(max_nr * cells), false) != hipSuccess ||
+      gc_buf_reserve(bmap, sizeof(int32_t) * (size_t)(max_nm + 1), false) != hipSuccess ||
+      gc_buf_reserve(bpow, sizeof(double) * (size_t)(std::max(max_nm, 1) * cells), false) != hipSuccess) {
+    gc_set_error("%s: device allocation failed (%d blocks, %d runs, %d maps in a sub-batch, %d taps, %d bins)", fn, max_nb, max_nr, max_nm,
+                 ntaps, nfreq);
+    return GC_E_NOMEM;
+  }
+  std::vector<DdmBlockAux> aux;
+  std::vector<double> compact;
+  for (DdmStep s; s.first + s.nb < nblocks;) {
+    ddm_next_step(s, blocks, nblocks, max_chunks, run_start, map_start, base);
+    BankArgs a;
+    if ((rc = bank_chunks(fn, ctx, blocks + s.first, s.nb, base, ntaps, nfreq, true, arms, &a))) return rc;
+    const int end = s.first + s.nb;
+    aux.resize((size_t)s.nb);
+    index.resize((size_t)s.nr + 1);
+    for (int k = 0; k < s.nr; ++k) {
+      const int b0 = run_start[s.r0 + k], lo = std::max(b0, s.first), hi = std::min(run_start[s.r0 + k + 1], end);
+      index[k] = lo - s.first;
+      index[k + 1] = hi - s.first;
+      for (int b = lo; b < hi; ++b) aux[b - s.first] = DdmBlockAux{blocks[b].first_sample - blocks[b0].first_sample, weights ? weights[b] : 1.0};
+    }
+    GC_HIP(hipMemcpyAsync(baux.p, aux.data(), sizeof(DdmBlockAux) * aux.size(), hipMemcpyHostToDevice, ctx->stream));
+    GC_HIP(hipMemcpyAsync(brun.p, index.data(), sizeof(int32_t) * index.size(), hipMemcpyHostToDevice, ctx->stream));
+    DdmArgs d;
+    d.blocks = a.blocks;
+    d.chans = a.chans;
+    d.chunk_base = a.chunk_base;
+    d.freqs = a.freqs;
+    d.aux = (const DdmBlockAux*)baux.p;
+    d.partial = (const double2*)a.partial;
+    d.rot = (double2*)brot.p;
+    d.run_base = (const int32_t*)brun.p;
+    d.coh = (double2*)bcoh.p;
+    d.map_base = (const int32_t*)bmap.p;
+    d.pow = (double*)bpow.p;
+    d.fs = ctx->fs;
+    d.nblocks = s.nb;
+    d.ntaps = ntaps;
+    d.nfreq = nfreq;
+    d.arms = arms;
+    d.nruns = s.nr;
+    d.nmaps = s.nm;
+    d.carry_run = run_start[s.r0] < s.first;
+    d.carry_map = s.nm > 0 && map_start[s.q0] < s.r0;
+    hipLaunchKernelGGL(ddm_rotation_kernel, dim3((unsigned int)(((long long)s.nb * nfreq + 255) / 256)), dim3(256), 0, ctx->stream, d);
+    GC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ddm_integrate_kernel, dim3((unsigned int)((s.nr * cells + 255) / 256)), dim3(256), 0, ctx->stream, d);
+    GC_HIP(hipGetLastError());
+    if (s.nm > 0) {
+      mindex.resize((size_t)s.nm + 1);
+      for (int k = 0; k <= s.nm; ++k) mindex[k] = std::min(std::max(map_start[s.q0 + k] - s.r0, 0), s.nfin);
+      GC_HIP(hipMemcpyAsync(bmap.p, mindex.data(), sizeof(int32_t) * mindex.size(), hipMemcpyHostToDevice, ctx->stream));
+      hipLaunchKernelGGL(ddm_power_kernel, dim3((unsigned int)((s.nm * cells + 255) / 256)), dim3(256), 0, ctx->stream, d);
+      GC_HIP(hipGetLastError());
+      if (s.mfin > 0 && (rc = bank_fetch(ctx, pow + (size_t)s.q0 * full, bpow.p, s.mfin, cells, full, compact))) return rc;
+      if (s.mfin < s.nm && s.nm > 1)  // the map that goes on: to the front
+        GC_HIP(hipMemcpyAsync(bpow.p, (const double*)bpow.p + (size_t)(s.nm - 1) * cells, sizeof(double) * (size_t)cells, hipMemcpyDeviceToDevice,
+                              ctx->stream));
+    }
+    if (coh && s.nfin > 0 && (rc = bank_fetch(ctx, coh + (size_t)s.r0 * 2 * full, bcoh.p, s.nfin, 2 * cells, 2 * full, compact))) return rc;
+    if (s.nfin < s.nr && s.nr > 1)  // the run that goes on: to the front
+      GC_HIP(hipMemcpyAsync(bcoh.p, (const double2*)bcoh.p + (size_t)(s.nr - 1) * cells, sizeof(double2) * (size_t)cells, hipMemcpyDeviceToDevice,
+                            ctx->stream));
+    GC_HIP(hipStreamSynchronize(ctx->stream));
   }
   return GC_OK;
 }
@@ -522,4 +825,16 @@ extern "C" int gc_correlate_ddm(gc_context* ctx, int nblocks, const gc_block* bl
     return GC_E_INVALID;
   }
   return bank_run("gc_correlate_ddm", ctx, nblocks, blocks, ntaps, tap_offsets, nfreq, freq_offsets, out);
+}
+
+extern "C" int gc_correlate_ddm_integrate(gc_context* ctx, int nblocks, const gc_block* blocks, const double* block_weights, int ntaps,
+                                          const double* tap_offsets, int nfreq, const double* freq_offsets, int nruns,
+                                          const int32_t* run_len, int nmaps, const int32_t* map_len, double* coh, double* pow) {
+  if (!ctx || nblocks < 0 || !tap_offsets || !freq_offsets || (nblocks > 0 && !blocks) || nruns < 0 || (nruns > 0 && !run_len) ||
+      (nmaps > 0 && !map_len)) {
+    gc_set_error("gc_correlate_ddm_integrate: bad arguments");
+    return GC_E_INVALID;
+  }
+  return ddm_integrate_run("gc_correlate_ddm_integrate", ctx, nblocks, blocks, block_weights, ntaps, tap_offsets, nfreq, freq_offsets, nruns,
+                           run_len, nmaps, map_len, coh, pow);
 }

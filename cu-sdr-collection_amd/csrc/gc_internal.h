@@ -198,8 +198,11 @@ struct gc_context {
   enum { TRK_CHAN = 0, TRK_DESC, TRK_PART, TRK_ARGS, TRK_RECORDS, TRK_HDESC, TRK_CNO, TRK_NBUF };
   GcBuf trk[TRK_NBUF];  // gc_track / gc_track_device: channel state, descriptor and partial-sum messages, arguments, records
   GcBuf nav[3];  // gc_sync_xcorr: prompt stream, pattern, result
-  enum { BANK_BLOCKS = 0, BANK_TAPS, BANK_CHUNKS, BANK_PARTIAL, BANK_OUT, BANK_FREQS, BANK_NBUF };
-  GcBuf bank[BANK_NBUF];  // gc_correlate_bank, gc_correlate_ddm: descriptors, tap offsets, chunk index, per-chunk partial sums, results, frequency offsets
+  enum { BANK_BLOCKS = 0, BANK_TAPS, BANK_CHUNKS, BANK_PARTIAL, BANK_OUT, BANK_FREQS,
+         BANK_AUX, BANK_ROT, BANK_RUNS, BANK_COH, BANK_MAPS, BANK_POW, BANK_NBUF };
+  // gc_correlate_bank, gc_correlate_ddm: descriptors, tap offsets, chunk index, per-chunk partial sums, results, frequency offsets;
+  // gc_correlate_ddm_integrate: per-block sample distance and weight, per-(block, bin) rotations, run index, coherent sums, map index, power maps
+  GcBuf bank[BANK_NBUF];
   double* cno_out = nullptr;  // gc_set_cno_output: caller-owned C/N0 buffer of the next tracking calls
   long long cno_cap = 0;
   int persist_member_cap = 0;  // gc_track_device: team size limit of the retry after a grid that did not fit the device (0: none)

@@ -245,6 +245,34 @@ class Engine:
                                            out.ctypes.data_as(C.POINTER(C.c_double))))
         return out[..., 0] + 1j * out[..., 1]
 
+    def correlate_ddm_integrate(self, blocks, offsets, freqs, run_len, weights=None, map_len=None, coherent=True):
+        """gc_correlate_ddm_integrate: correlate_ddm's cells added coherently over runs of blocks, then as power over runs, on the
+        device - only the maps come back.  run_len: the blocks of every run, in order (one channel per run); weights: one real factor per
+        block (+1 / -1 wipes a data bit, 0 drops the block; None: all 1); map_len: the runs of every power map, in order (None: no power
+        maps); coherent=False leaves the coherent sums on the device.  Within a run bin m of block b is rotated by
+        exp(-2j pi freqs[m] (first_sample[b] - first_sample[first block of the run]) / fs) before it is added (include/gnsscorr.h).
+        Returns (complex128 [nruns, GC_MAX_ARMS, nfreq, ntaps] or None, float64 [nmaps, GC_MAX_ARMS, nfreq, ntaps] or None), unused arms zero."""
+        n = len(blocks)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        frq = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        runs = np.ascontiguousarray(run_len, dtype=np.int32).reshape(-1)
+        maps = None if map_len is None else np.ascontiguousarray(map_len, dtype=np.int32).reshape(-1)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if w.shape[0] != n:
+                raise ValueError("correlate_ddm_integrate: one weight per block")
+        nmaps = 0 if maps is None else maps.shape[0]
+        coh = np.zeros((runs.shape[0], L.GC_MAX_ARMS, frq.shape[0], off.shape[0], 2)) if coherent else None
+        pw = np.zeros((nmaps, L.GC_MAX_ARMS, frq.shape[0], off.shape[0])) if maps is not None else None
+        L.check(self._lib.gc_correlate_ddm_integrate(self._ctx, n, blocks, None if w is None else w.ctypes.data_as(dp), off.shape[0],
+                                                     off.ctypes.data_as(dp), frq.shape[0], frq.ctypes.data_as(dp), runs.shape[0],
+                                                     runs.ctypes.data_as(ip), nmaps, None if maps is None else maps.ctypes.data_as(ip),
+                                                     None if coh is None else coh.ctypes.data_as(dp),
+                                                     None if pw is None else pw.ctypes.data_as(dp)))
+        return (None if coh is None else coh[..., 0] + 1j * coh[..., 1]), pw
+
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition
         (corr_multi.hip), 5 hybrid for channels with a derived six-fold arm (corr_cboc.hip), 6 float64 (corr_f64.hip), -1 mixed

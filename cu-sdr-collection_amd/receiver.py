@@ -451,6 +451,53 @@ def delay_doppler_map(fid: Engine, trackResults_k, channel_k, settings, offsets,
     return fid.correlate_ddm(blocks, offsets, freqs)[:, :arms]
 
 
+def integrated_delay_doppler_map(fid: Engine, trackResults_k, channel_k, settings, offsets, freqs, coherent, noncoherent=None, wipe="prompt",
+                                 signal: str = "GPS_L1CA", epochs=None):
+    """delay_doppler_map() integrated over epochs on the device: the evaluated epochs, in order, form runs of `coherent` consecutive
+    epochs whose maps are added coherently - every bin rotated to the carrier phase at the run's first block, which is what makes bins
+    closer than 1 / (block length) resolvable - and, with `noncoherent` = M, the powers |.|^2 of M consecutive runs are added to one map.
+    A trailing incomplete run (and a trailing incomplete map) is dropped.  One gc_correlate_ddm_integrate call (include/gnsscorr.h): the
+    per-epoch maps never leave the device.
+
+    wipe: the data-bit or secondary-code wipe-off, one weight per evaluated epoch - "prompt": +1 where the recorded I_P of the epoch is
+    >= 0, else -1; None: no weights; an array: the caller's own (one per evaluated epoch, any finite value; 0 drops an epoch).
+    Returns complex128 [n_runs, arms, nfreq, ntaps] (noncoherent=None) or float64 [n_maps, arms, nfreq, ntaps].
+    Other arguments, refusals and side effects as correlation_function()."""
+    blocks, arms = _tracked_blocks(fid, trackResults_k, channel_k, settings, signal, epochs)
+    coherent = int(coherent)
+    if coherent < 1 or (noncoherent is not None and int(noncoherent) < 1):
+        raise ValueError("integrated_delay_doppler_map: coherent and noncoherent count epochs and runs (1 at least)")
+    nruns = len(blocks) // coherent
+    if noncoherent is not None:
+        nruns -= nruns % int(noncoherent)
+    nblk = nruns * coherent
+    if isinstance(wipe, str) and wipe == "prompt":
+        if epochs is None:           # the epochs _tracked_blocks evaluated
+            epochs = np.nonzero(np.isfinite(np.asarray(trackResults_k.codeFreq, dtype=np.float64)) &
+                                np.isfinite(np.asarray(trackResults_k.remCodePhase, dtype=np.float64)))[0]
+        ip = np.asarray(trackResults_k.I_P, dtype=np.float64)[np.atleast_1d(np.asarray(epochs, dtype=np.int64))]
+        weights = np.where(ip >= 0, 1.0, -1.0)
+    elif wipe is None:
+        weights = None
+    else:
+        weights = np.asarray(wipe, dtype=np.float64).reshape(-1)
+        if weights.shape[0] != len(blocks):
+            raise ValueError("integrated_delay_doppler_map: one weight per evaluated epoch")
+    used = fid.make_blocks(nblk)
+    for n in range(nblk):
+        used[n] = blocks[n]
+    if weights is not None:
+        weights = weights[:nblk]
+    if noncoherent is None:
+        coh, _ = fid.correlate_ddm_integrate(used, offsets, freqs, [coherent] * nruns, weights=weights)
+        return coh[:, :arms]
+    if nruns == 0:                   # not one complete map: nothing to ask the library for
+        return np.zeros((0, arms, np.asarray(freqs).size, np.asarray(offsets).size))
+    _, pw = fid.correlate_ddm_integrate(used, offsets, freqs, [coherent] * nruns, weights=weights,
+                                        map_len=[int(noncoherent)] * (nruns // int(noncoherent)), coherent=False)
+    return pw[:, :arms]
+
+
 def tracking_file(fid: Engine, path: str, channel, settings, window_samples: int, signal: str = "GPS_L1CA", pilot_fields: str | None = None,
                   precision: str | None = None, device_loop: bool = False):
     """tracking(fid, channel, settings) on a record FILE that need not fit the device: at most 2 * window_samples samples are

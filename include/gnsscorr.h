@@ -190,6 +190,41 @@ int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* blocks, int 
 int gc_correlate_ddm(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, int nfreq,
                      const double* freq_offsets, double* out);
 
+/* Delay-Doppler maps over runs of blocks: gc_correlate_ddm's cells added coherently over each run, then as power over runs
+ * (csrc/corr_bank.hip).  Only the maps come back; the per-block cells never leave the device.
+ * Block cell: D[b][arm][m][j] is the cell gc_correlate_ddm returns for block b, BIT FOR BIT (the same chunk kernel, the same
+ *   chunk-order sum of partials).
+ * Runs: the blocks are partitioned in order into nruns runs, run r of run_len[r] >= 1 blocks, the lengths summing to nblocks.  All
+ *   blocks of a run name the same channel; first_sample may go in any order inside a run (dn below may be negative, blocks may overlap).
+ * Coherent cell of run r, whose first block is b0: the accumulator starts at +0.0 and the blocks are added in block order,
+ *     dn = first_sample[b] - first_sample[b0]          (int64, exact as a double)
+ *     x  = (freq_offsets[m] * (double)dn) / fs         (one product, one division, each rounded once)
+ *     u  = x - rint(x)                                 (exact)
+ *     c  = cospi(2u),  s = sinpi(2u)                   (float64)
+ *     w  = block_weights ? block_weights[b] : 1.0
+ *     re += w * (c * D.re + s * D.im)
+ *     im += w * (c * D.im - s * D.re)
+ *   every operation rounded by itself (no fused multiply-add): w e^{-i 2 pi f dn / fs} D, the rotation that refers bin m's carrier
+ *   phase - which the DDM refers to each block's own first sample - to the run's first block.  Where freq_offsets[m] == 0 the rotation
+ *   is exactly 1; a run of one block with weight 1 is D itself.
+ * Weights: real and finite; +1 / -1 wipes a data bit or secondary-code chip, 0 drops a block, any other finite value is legal.
+ * Power maps: the runs are partitioned in order into nmaps maps, map q of map_len[q] >= 1 runs, the lengths summing to nruns.
+ *   pow[q][arm][m][j] starts at +0.0; per run, in run order, p += (re * re + im * im), no fused multiply-add.
+ * Outputs: coh[(((r * GC_MAX_ARMS + arm) * nfreq + m) * ntaps + j) * 2 + {0: re, 1: im}],
+ *   pow[((q * GC_MAX_ARMS + arm) * nfreq + m) * ntaps + j]; arms the run's channel does not have are zero.  coh may be null (the
+ *   coherent sums then never leave the device); pow may be null exactly when nmaps == 0; at least one of the two is asked for.
+ * Independence: a cell depends on its own run's blocks only (pow: its own map's) - not on the other runs, taps or bins of the call,
+ *   not on the run's position in the list, not on where the library cuts the list into sub-batches.  The same input gives the same
+ *   bytes.
+ * Refusals: every refusal of gc_correlate_ddm, with its status.  GC_E_INVALID also for nruns < 1 with blocks present, a run_len or
+ *   map_len below 1, lengths that do not sum, two channels in one run, a non-finite weight, nmaps < 0, nmaps > 0 with pow null,
+ *   nmaps == 0 with coh null.  nblocks == 0 with nruns == 0 and nmaps == 0 is GC_OK (no record needed).  A refused call writes
+ *   neither output. */
+int gc_correlate_ddm_integrate(gc_context* ctx, int nblocks, const gc_block* blocks, const double* block_weights,
+                               int ntaps, const double* tap_offsets, int nfreq, const double* freq_offsets,
+                               int nruns, const int32_t* run_len, int nmaps, const int32_t* map_len,
+                               double* coh, double* pow);
+
 /* Replay (batched, open-loop) mode: descriptors stay resident in HBM so that the timed
  * region contains only kernel work (SURVEY.md §7 hard part 1a). */
 int gc_replay_prepare(gc_context* ctx, int64_t nblocks, const gc_block* blocks);

@@ -22,6 +22,11 @@
  *   R    = gnsscorr_mex('correlate_ddm', h, blocks, offsets, freqs)   % the same at the carrier offsets `freqs` as well (Hz, added to the
  *          blocks' carrFreq; gc_correlate_ddm: bin m is 'correlate_bank' at carrFreq + freqs(m), bit for bit): 2 x ntaps x (nfreq*3*nblocks);
  *          reshape(R, 2, ntaps, nfreq, 3, []) is (I|Q, tap, bin, arm, block)
+ *   [C, P] = gnsscorr_mex('correlate_ddm_integrate', h, blocks, offsets, freqs, runLen[, weights[, mapLen[, coherent]]])   % 'correlate_ddm'
+ *          integrated on the device (gc_correlate_ddm_integrate): runLen(r) consecutive blocks of one channel are added coherently, every
+ *          bin rotated to the carrier phase at the run's first block, each block times weights(b) ([] = 1: +1 / -1 wipes a data bit);
+ *          mapLen(q) consecutive runs are added as power ([] = no power maps, one output).  C: 2 x ntaps x (nfreq*3*nruns), rows re, im
+ *          ([] with coherent = 0: the coherent sums stay on the device); P: ntaps x (nfreq*3*nmaps)
  *   [trk, epochs, status] = gnsscorr_mex('track', h, params_struct, channels)   % channels: 5 x nch
  *   res  = gnsscorr_mex('acquire_coarse', h, acq_struct, sampledCodes)          % int8 spc x nprn
  *   f    = gnsscorr_mex('acquire_fine_l1ca', h, acq_struct, caCode, codePhase, coarseFreq)
@@ -145,7 +150,7 @@ static gc_channel_init* channel_inits_from(const mxArray* a, int* nch_out) {
 }
 
 /* blocks: 8 x nblocks, rows = channel, first_sample (0-based), blksize, remCodePhase, codePhaseStep, earlyLateSpc, carrFreq,
- * remCarrPhase - the quantities of tracking.m:212-222,249,277 ('correlate', 'correlate_bank', 'correlate_ddm') */
+ * remCarrPhase - the quantities of tracking.m:212-222,249,277 ('correlate', 'correlate_bank', 'correlate_ddm', 'correlate_ddm_integrate') */
 static gc_block* blocks_from(const mxArray* a, int* n_out) {
   if (mxGetM(a) != 8) mexErrMsgIdAndTxt("gnsscorr:usage", "blocks must be 8 x nblocks");
   const double* b = mxGetDoubles(a);
@@ -277,6 +282,34 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxFree(blk);
     if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
     if (rc) fail("gc_correlate_ddm");
+  } else if (!strcmp(cmd, "correlate_ddm_integrate")) {
+    /* blocks, offsets and freqs as for 'correlate_ddm'; runLen, weights, mapLen: double vectors (weights and mapLen may be []).  The
+     * results are gc_correlate_ddm_integrate's `coh` and `pow` as they lie in memory: (re|im, tap, bin, arm, run) and (tap, bin, arm, map)
+     * with GC_MAX_ARMS arms, the last three folded. */
+    if (nrhs < 6 || !mxIsDouble(prhs[3]) || !mxIsDouble(prhs[4]) || !mxIsDouble(prhs[5]) || (nrhs > 6 && !mxIsDouble(prhs[6])) ||
+        (nrhs > 7 && !mxIsDouble(prhs[7])))
+      mexErrMsgIdAndTxt("gnsscorr:usage", "correlate_ddm_integrate: h, blocks 8 x nblocks, offsets, freqs, runLen[, weights[, mapLen[, coherent]]]");
+    int n = 0;
+    gc_block* blk = blocks_from(prhs[2], &n);
+    const int ntaps = (int)mxGetNumberOfElements(prhs[3]), nfreq = (int)mxGetNumberOfElements(prhs[4]);
+    const int nruns = (int)mxGetNumberOfElements(prhs[5]);
+    const int nw = nrhs > 6 ? (int)mxGetNumberOfElements(prhs[6]) : 0, nmaps = nrhs > 7 ? (int)mxGetNumberOfElements(prhs[7]) : 0;
+    const int coherent = nrhs > 8 ? mxGetScalar(prhs[8]) != 0 : 1;
+    if (nw != 0 && nw != n) mexErrMsgIdAndTxt("gnsscorr:usage", "correlate_ddm_integrate: weights must be [] or one per block");
+    if (nmaps > 0 && nlhs < 2) mexErrMsgIdAndTxt("gnsscorr:usage", "correlate_ddm_integrate: [C, P] = ... takes the power maps of mapLen");
+    int32_t* len = (int32_t*)mxCalloc((size_t)(nruns + nmaps > 0 ? nruns + nmaps : 1), sizeof *len);
+    for (int r = 0; r < nruns; ++r) len[r] = (int32_t)mxGetDoubles(prhs[5])[r];
+    for (int q = 0; q < nmaps; ++q) len[nruns + q] = (int32_t)mxGetDoubles(prhs[7])[q];
+    const mwSize cdims[3] = {2, (mwSize)ntaps, (mwSize)nfreq * (mwSize)GC_MAX_ARMS * (mwSize)nruns};
+    plhs[0] = coherent ? mxCreateNumericArray(3, cdims, mxDOUBLE_CLASS, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    if (nlhs > 1) plhs[1] = mxCreateDoubleMatrix((mwSize)ntaps, (mwSize)nfreq * (mwSize)GC_MAX_ARMS * (mwSize)nmaps, mxREAL);
+    int rc = gc_correlate_ddm_integrate(handle(prhs[1]), n, blk, nw ? mxGetDoubles(prhs[6]) : NULL, ntaps, mxGetDoubles(prhs[3]), nfreq,
+                                        mxGetDoubles(prhs[4]), nruns, len, nmaps, len + nruns, coherent ? mxGetDoubles(plhs[0]) : NULL,
+                                        nmaps > 0 ? mxGetDoubles(plhs[1]) : NULL);
+    mxFree(len);
+    mxFree(blk);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
+    if (rc) fail("gc_correlate_ddm_integrate");
   } else if (!strcmp(cmd, "track") || !strcmp(cmd, "track_device") || !strcmp(cmd, "track_file") || !strcmp(cmd, "track_file_device")) {
     /* [trk, epochs, status] = gnsscorr_mex('track', h, p, chanTable)
        [trk, epochs, status] = gnsscorr_mex('track_file', h, p, chanTable, fileName, windowSamples, dataType, fileType[, 'QI']):
