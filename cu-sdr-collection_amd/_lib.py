@@ -17,6 +17,7 @@ GC_SYNC_ZERO_IS_PLUS = 1   # gc_sync_xcorr flag
 GC_OUT_STRIDE = 6 * GC_MAX_ARMS
 GC_BANK_MAX_TAPS = 64      # gc_correlate_bank
 GC_DDM_MAX_FREQS = 64      # gc_correlate_ddm
+GC_DDM_MAX_HYP = 128       # gc_correlate_ddm_search
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -38,6 +39,14 @@ class gc_block(C.Structure):
                 ("rem_code_phase", C.c_double), ("code_phase_step", C.c_double),
                 ("el_spacing", C.c_double), ("carr_freq", C.c_double), ("rem_carr_phase", C.c_double),
                 ("table_offset", C.c_int32 * GC_MAX_ARMS), ("reserved", C.c_int32)]
+
+
+class gc_ddm_peak(C.Structure):
+    """gc_correlate_ddm_search: the first maximum of a power map's plane."""
+    _fields_ = [("power", C.c_double), ("bin", C.c_int32), ("tap", C.c_int32)]
+
+
+DDM_PEAK_DTYPE = [("power", "<f8"), ("bin", "<i4"), ("tap", "<i4")]   # gc_ddm_peak as a numpy structured type
 
 
 class gc_track_params(C.Structure):
@@ -146,6 +155,9 @@ SYMBOLS = {
     "gc_correlate_ddm_integrate": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int,
                                              C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gc_correlate_ddm_search": (C.c_int, [_P, C.c_int, C.POINTER(gc_block), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int,
+                                          C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(gc_ddm_peak)]),
     "gc_replay_prepare": (C.c_int, [_P, C.c_int64, C.POINTER(gc_block)]),
     "gc_replay_launch": (C.c_int, [_P]),
     "gc_replay_fetch": (C.c_int, [_P, C.POINTER(C.c_double)]),

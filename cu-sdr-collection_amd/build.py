@@ -37,7 +37,8 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                "corr_f64.hip",    # gc_set_precision(GC_PREC_F64): the float64 per-sample kernel and its device loop
                "corr_bank.hip",   # gc_correlate_bank: a block's correlation function at up to 64 taps from one pass over its samples; gc_correlate_ddm:
                                   # the same kernel at up to 64 carrier offsets, every table boundary computed once per group of bins;
-                                  # gc_correlate_ddm_integrate: those maps added over runs of blocks on the device
+                                  # gc_correlate_ddm_integrate: those maps added over runs of blocks on the device;
+                                  # gc_correlate_ddm_search: that integration under many hypotheses, peaks picked on the device
                # the acquisition, one translation unit per part of the search (acq_internal.h is what they share)
                "acq_fft.hip", "acq_coarse.hip", "acq_shift.hip", "acq_fine.hip", "acq_cond.hip", "acq_guard.hip", "navsync.hip"]
 

@@ -1,7 +1,8 @@
 // corr_bank.hip — gc_correlate_bank: the correlation function of a block at up to GC_BANK_MAX_TAPS code offsets,
 // gc_correlate_ddm: the same at up to GC_DDM_MAX_FREQS carrier offsets as well (a delay-Doppler map), and
-// gc_correlate_ddm_integrate: those maps added coherently over runs of blocks, then as power over runs, where the chunk partials are
-// (its kernels and driver: the last part of this file).
+// gc_correlate_ddm_integrate: those maps added coherently over runs of blocks, then as power over runs, where the chunk partials are,
+// and gc_correlate_ddm_search: that integration under many hypotheses (shifts of the run grid, weight rows) from one chunk pass, every
+// map's peak picked on the device (their kernels and drivers: the last two parts of this file).
 //
 // The DDM is defined as an identity: bin m of a block is what the bank returns for the block with carr_freq replaced by the
 // float64 sum carr_freq + freq_offsets[m], bit for bit.  The code says so: one chunk kernel over (record format, G bins per work
@@ -808,7 +809,381 @@ int ddm_integrate_run(const char* fn, gc_context* ctx, int nblocks, const gc_blo
   return GC_OK;
 }
 
+// ---- gc_correlate_ddm_search: gc_correlate_ddm_integrate under many hypotheses, each map's peak picked here ---------------------------
+//
+// Per sub-batch of bank_cut's walk the chunk kernel runs once and bank_combine_kernel forms every block's cell D once
+// ([block][arm][bin][tap], BANK_OUT).  The sub-batch's blocks are then taken in tiles of blocks (search_tile_blocks: what bounds the
+// memory).  Per tile the host lays out one SearchAux per (hypothesis, block) - dn to the first block of the run the block has in THAT
+// hypothesis, its weight there, and where runs and maps begin and end -, search_rotation_kernel forms the phasors per (hypothesis,
+// block, bin) with ddm_rotation_kernel's expression, and search_integrate_kernel, a thread per (hypothesis, cell), walks the tile's
+// blocks with its open run (re, im) and open map (p) in registers: ddm_integrate_kernel's and ddm_power_kernel's additions in their
+// order.  The two accumulators are kept per (hypothesis, cell) between tiles and sub-batches, so a cut never shows; a finished run
+// goes into its map at once and is stored only when the caller asked for coh.  search_peak_kernel reduces every finished plane.
+
+enum { SRCH_IN = 1, SRCH_RUN_START = 2, SRCH_RUN_END = 4, SRCH_MAP_START = 8, SRCH_MAP_END = 16 };
+
+struct SearchAux {
+  long long dn;   // first_sample - first_sample of the first block of the run this block belongs to in the hypothesis
+  double w;       // the block's weight in the hypothesis
+  int32_t flags;  // SRCH_*; 0: the block is outside the hypothesis's window
+  int32_t pad_;
+};
+
+struct SearchArgs {
+  const gc_block* blocks;  // the sub-batch's
+  const DevChannel* chans;
+  const double* freqs;        // [nfreq]
+  const SearchAux* aux;       // [nhyp][nt]
+  const double2* cell;        // [sub-batch blocks][arms][nfreq][ntaps]: D
+  double2* rot;               // [nhyp][nt][nfreq]: (cospi(2u), sinpi(2u))
+  double2* racc;              // [nhyp][arms][nfreq][ntaps]: the open run
+  double* macc;               // [nhyp][arms][nfreq][ntaps]: the open map
+  double2* coh;               // [nhyp][nslot_r][arms][nfreq][ntaps]: the runs that end in this tile; nullptr: not asked for
+  double* pow;                // [nhyp][nslot_m][arms][nfreq][ntaps]: the maps that end in this tile; nullptr: none asked for
+  const int32_t* maps_done;   // [nhyp]: maps of the hypothesis that end in this tile
+  gc_ddm_peak* peaks;         // [nhyp][nslot_m][arms]
+  double fs;
+  int t0, nt;  // the tile: blocks t0 .. t0 + nt - 1 of the sub-batch
+  int ntaps, nfreq, arms, nhyp, nslot_r, nslot_m;
+};
+
+constexpr long long kSearchTileBytes = 128LL << 20;  // per-(hypothesis, block) scratch and finished runs / maps of one tile at most
+
+__global__ void search_rotation_kernel(const SearchArgs p) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)p.nhyp * p.nt * p.nfreq) return;
+  const long long hk = i / p.nfreq;
+  const int m = (int)(i - hk * p.nfreq);
+  const SearchAux a = p.aux[hk];
+  if (!(a.flags & SRCH_IN)) return;
+  const double x = __dmul_rn(p.freqs[m], (double)a.dn) / p.fs;
+  const double u = x - rint(x);
+  double s, c;
+  sincospi(2.0 * u, &s, &c);
+  p.rot[i] = make_double2(c, s);
+}
+
+__global__ __launch_bounds__(256) void search_integrate_kernel(const SearchArgs p) {
+  const int plane = p.nfreq * p.ntaps;
+  const int cells = p.arms * plane;
+  const int v = (int)(blockIdx.x * blockDim.x + threadIdx.x);  // (arm, bin, tap), the tap fastest
+  if (v >= cells) return;
+  const int h = (int)blockIdx.y;
+  const int arm = v / plane, m = (v - arm * plane) / p.ntaps;
+  const SearchAux* __restrict__ ax = p.aux + (long long)h * p.nt;
+  const double2* __restrict__ rot = p.rot + (long long)h * p.nt * p.nfreq + m;
+  const long long sv = (long long)h * cells + v;
+  double re = p.racc[sv].x, im = p.racc[sv].y, pw = p.macc[sv];  // the run / map that began in an earlier tile (else reset below)
+  int sr = 0, sm = 0;
+  for (int k = 0; k < p.nt; ++k) {
+    const SearchAux a = ax[k];
+    if (!(a.flags & SRCH_IN)) continue;
+    if (a.flags & SRCH_RUN_START) re = im = 0.0;
+    if (a.flags & SRCH_MAP_START) pw = 0.0;
+    const int b = p.t0 + k;
+    if (arm < p.chans[p.blocks[b].channel].arms) {
+      const double2 d = p.cell[(long long)b * cells + v];
+      const double2 cs = rot[(long long)k * p.nfreq];
+      re += a.w * (cs.x * d.x + cs.y * d.y);
+      im += a.w * (cs.x * d.y - cs.y * d.x);
+    }
+    if (a.flags & SRCH_RUN_END) {
+      if (p.coh) p.coh[((long long)h * p.nslot_r + sr) * cells + v] = make_double2(re, im);
+      ++sr;
+      pw += (re * re + im * im);
+      if (a.flags & SRCH_MAP_END) {
+        if (p.pow) p.pow[((long long)h * p.nslot_m + sm) * cells + v] = pw;
+        ++sm;
+      }
+    }
+  }
+  p.racc[sv] = make_double2(re, im);
+  p.macc[sv] = pw;
+}
+
+// (value, linear index): the larger value wins, on equal values the smaller index - the sequential first maximum whatever the order
+// of the combination.  Power is >= 0, so (-1, INT_MAX) loses against every cell.
+__device__ __forceinline__ void search_better(double& bv, int& bi, double v, int i) {
+  if (v > bv || (v == bv && i < bi)) {
+    bv = v;
+    bi = i;
+  }
+}
+
+// A workgroup per finished (hypothesis, map, arm) plane.
+__global__ __launch_bounds__(256) void search_peak_kernel(const SearchArgs p) {
+  __shared__ double wv[4];
+  __shared__ int wi[4];
+  const int h = (int)blockIdx.y;
+  const int s = (int)blockIdx.x / p.arms, arm = (int)blockIdx.x - s * p.arms;
+  if (s >= p.maps_done[h]) return;  // uniform
+  const int plane = p.nfreq * p.ntaps;
+  const double* __restrict__ src = p.pow + (((long long)h * p.nslot_m + s) * p.arms + arm) * plane;
+  const int tid = (int)threadIdx.x;
+  double bv = -1.0;
+  int bi = 0x7fffffff;
+  for (int i = tid; i < plane; i += 256) search_better(bv, bi, src[i], i);
+#pragma unroll
+  for (int sh = 32; sh > 0; sh >>= 1) {
+    const double ov = __shfl_down(bv, sh, 64);
+    const int oi = __shfl_down(bi, sh, 64);
+    search_better(bv, bi, ov, oi);
+  }
+  if ((tid & 63) == 0) {
+    wv[tid >> 6] = bv;
+    wi[tid >> 6] = bi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) search_better(bv, bi, wv[w], wi[w]);
+    gc_ddm_peak r;
+    r.power = bv;
+    r.bin = bi / p.ntaps;
+    r.tap = bi - r.bin * p.ntaps;
+    p.peaks[((long long)h * p.nslot_m + s) * p.arms + arm] = r;
+  }
+}
+
+// Blocks per tile: what one block can cost in every hypothesis at once - its SearchAux, its rotations, and (at most one run and one
+// map end with a block) a finished run if coh is asked for, a finished map with its peaks if maps are - within kSearchTileBytes.
+// At the limits (128 hypotheses, 3 arms x 64 bins x 64 taps, coh and maps) a block costs 37.9 MB: one block always fits.
+int search_tile_blocks(int nhyp, int nfreq, long long cells, int arms, bool want_coh, bool want_maps) {
+  const long long per_block = (long long)nhyp * ((long long)sizeof(SearchAux) + 16LL * nfreq + (want_coh ? 16 * cells : 0) +
+                                                 (want_maps ? 8 * cells + (long long)sizeof(gc_ddm_peak) * arms : 0));
+  return (int)std::max<long long>(1, std::min<long long>(kSearchTileBytes / per_block, 1 << 20));
+}
+
+int ddm_search_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* blocks, int nhyp, const int32_t* block_shift,
+                   const double* weights, int ntaps, const double* tap_offsets, int nfreq, const double* freq_offsets, int nruns,
+                   const int32_t* run_len, int nmaps, const int32_t* map_len, double* coh, double* pow, gc_ddm_peak* peaks) {
+  if (nhyp < 1 || nhyp > GC_DDM_MAX_HYP) {
+    gc_set_error("%s: %d hypotheses (1 .. %d)", fn, nhyp, GC_DDM_MAX_HYP);
+    return GC_E_INVALID;
+  }
+  int arms = 1;
+  int rc = bank_check(fn, ctx, nblocks, blocks, ntaps, tap_offsets, nfreq, freq_offsets, &arms);
+  if (rc) return rc;
+  if (nmaps < 0 || (nblocks > 0 && nruns < 1)) {
+    gc_set_error("%s: %d runs, %d maps for %d blocks", fn, nruns, nmaps, nblocks);
+    return GC_E_INVALID;
+  }
+  std::vector<int> run_start(1, 0), map_start(1, 0);  // blocks of the window before run r, runs before map q
+  for (int r = 0; r < nruns; ++r) {
+    if (run_len[r] < 1 || run_len[r] > nblocks - run_start.back()) {
+      gc_set_error("%s: run %d has %d blocks (1 at least, %d in all)", fn, r, (int)run_len[r], nblocks);
+      return GC_E_INVALID;
+    }
+    run_start.push_back(run_start.back() + run_len[r]);
+  }
+  const int nused = run_start.back();
+  for (int q = 0; q < nmaps; ++q) {
+    if (map_len[q] < 1 || map_len[q] > nruns - map_start.back()) {
+      gc_set_error("%s: map %d has %d runs (1 at least, %d in all)", fn, q, (int)map_len[q], nruns);
+      return GC_E_INVALID;
+    }
+    map_start.push_back(map_start.back() + map_len[q]);
+  }
+  if (nmaps > 0 && map_start.back() != nruns) {
+    gc_set_error("%s: the maps hold %d runs of %d", fn, map_start.back(), nruns);
+    return GC_E_INVALID;
+  }
+  std::vector<int> shift((size_t)nhyp, 0);
+  for (int h = 0; h < nhyp; ++h) {
+    if (block_shift) shift[h] = block_shift[h];
+    if (shift[h] < 0 || shift[h] > nblocks - nused) {
+      gc_set_error("%s: hypothesis %d looks at blocks %d .. %lld of %d", fn, h, shift[h], (long long)shift[h] + nused - 1, nblocks);
+      return GC_E_INVALID;
+    }
+  }
+  for (int h = 0; h < nhyp; ++h)
+    for (int r = 0; r < nruns; ++r) {
+      const int b0 = shift[h] + run_start[r];
+      for (int b = b0 + 1; b < shift[h] + run_start[r + 1]; ++b)
+        if (blocks[b].channel != blocks[b0].channel) {
+          gc_set_error("%s: run %d of hypothesis %d has blocks of channels %d and %d", fn, r, h, blocks[b0].channel, blocks[b].channel);
+          return GC_E_INVALID;
+        }
+    }
+  if (weights)
+    for (long long i = 0; i < (long long)nhyp * nblocks; ++i)
+      if (!std::isfinite(weights[i])) {
+        gc_set_error("%s: the weight of block %d in hypothesis %d is not finite", fn, (int)(i % nblocks), (int)(i / nblocks));
+        return GC_E_INVALID;
+      }
+  if (!coh && !pow && !peaks) {
+    gc_set_error("%s: no output asked for", fn);
+    return GC_E_INVALID;
+  }
+  if ((pow || peaks) && nmaps == 0) {
+    gc_set_error("%s: power maps or peaks asked for without a map", fn);
+    return GC_E_INVALID;
+  }
+  if (nblocks == 0) return GC_OK;
+  if ((rc = bank_upload_grids(fn, ctx, ntaps, tap_offsets, nfreq, freq_offsets))) return rc;
+  const bool want_maps = pow || peaks;
+  const long long cells = (long long)arms * nfreq * ntaps, full = (long long)GC_MAX_ARMS * nfreq * ntaps;
+  const long long max_chunks = bank_max_chunks(2 * cells);
+  const int tile = search_tile_blocks(nhyp, nfreq, cells, arms, coh != nullptr, want_maps);
+  // per position of the window: its run, and where runs and maps begin and end
+  std::vector<int> run_of((size_t)nused), pos_flags((size_t)nused, SRCH_IN);
+  for (int r = 0; r < nruns; ++r) {
+    for (int k = run_start[r]; k < run_start[r + 1]; ++k) run_of[k] = r;
+    pos_flags[run_start[r]] |= SRCH_RUN_START;
+    pos_flags[run_start[r + 1] - 1] |= SRCH_RUN_END;
+  }
+  if (want_maps)  // without an output for them the open map is never stored: no flags, nothing kept
+    for (int q = 0; q < nmaps; ++q) {
+      pos_flags[run_start[map_start[q]]] |= SRCH_MAP_START;
+      pos_flags[run_start[map_start[q + 1]] - 1] |= SRCH_MAP_END;
+    }
+  GcBuf& bout = ctx->bank[gc_context::BANK_OUT];
+  GcBuf& baux = ctx->bank[gc_context::BANK_AUX];
+  GcBuf& brot = ctx->bank[gc_context::BANK_ROT];
+  GcBuf& bdone = ctx->bank[gc_context::BANK_RUNS];
+  GcBuf& bcoh = ctx->bank[gc_context::BANK_COH];
+  GcBuf& bpow = ctx->bank[gc_context::BANK_POW];
+  GcBuf& bracc = ctx->bank[gc_context::BANK_RACC];
+  GcBuf& bmacc = ctx->bank[gc_context::BANK_MACC];
+  GcBuf& bpeak = ctx->bank[gc_context::BANK_PEAKS];
+  // the accumulators a cut run or map goes on from: reserved once, before the walk
+  if (gc_buf_reserve(bracc, sizeof(double2) * (size_t)(nhyp * cells), false) != hipSuccess ||
+      gc_buf_reserve(bmacc, sizeof(double) * (size_t)(nhyp * cells), false) != hipSuccess ||
+      gc_buf_reserve(bdone, sizeof(int32_t) * (size_t)nhyp, false) != hipSuccess) {
+    gc_set_error("%s: device allocation failed (%d hypotheses, %d taps, %d bins)", fn, nhyp, ntaps, nfreq);
+    return GC_E_NOMEM;
+  }
+  GC_HIP(hipMemsetAsync(bracc.p, 0, sizeof(double2) * (size_t)(nhyp * cells), ctx->stream));
+  GC_HIP(hipMemsetAsync(bmacc.p, 0, sizeof(double) * (size_t)(nhyp * cells), ctx->stream));
+  std::vector<int32_t> base, runs_now((size_t)nhyp), maps_now((size_t)nhyp);
+  std::vector<int> runs_done((size_t)nhyp, 0), maps_done((size_t)nhyp, 0);  // finished so far, per hypothesis
+  std::vector<SearchAux> aux;
+  std::vector<double> hcoh, hpow;
+  std::vector<gc_ddm_peak> hpeak;
+  for (int first = 0; first < nblocks;) {
+    const int nb = bank_cut(blocks, nblocks, first, max_chunks, base);
+    if (gc_buf_reserve(bout, sizeof(double2) * (size_t)(nb * cells), false) != hipSuccess)
+      return bank_nomem(fn, true, nb, base.back(), ntaps, nfreq);
+    BankArgs a;
+    if ((rc = bank_chunks(fn, ctx, blocks + first, nb, base, ntaps, nfreq, true, arms, &a))) return rc;
+    a.out = (double*)bout.p;
+    hipLaunchKernelGGL(bank_combine_kernel, dim3((unsigned int)((nb * 2 * cells + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    GC_HIP(hipGetLastError());
+    for (int t0 = 0; t0 < nb; t0 += tile) {
+      const int nt = std::min(tile, nb - t0);
+      aux.assign((size_t)nhyp * nt, SearchAux{0, 0.0, 0, 0});
+      int nslot_r = 0, nslot_m = 0;
+      bool any = false;
+      for (int h = 0; h < nhyp; ++h) {
+        runs_now[h] = maps_now[h] = 0;
+        const int lo = std::max(first + t0, shift[h]), hi = std::min(first + t0 + nt, shift[h] + nused);
+        for (int b = lo; b < hi; ++b) {
+          const int k = b - shift[h];
+          const int f = pos_flags[k];
+          aux[(size_t)h * nt + (b - first - t0)] =
+              SearchAux{blocks[b].first_sample - blocks[shift[h] + run_start[run_of[k]]].first_sample,
+                        weights ? weights[(size_t)h * nblocks + b] : 1.0, f, 0};
+          runs_now[h] += (f & SRCH_RUN_END) != 0;
+          maps_now[h] += (f & SRCH_MAP_END) != 0;
+          any = true;
+        }
+        nslot_r = std::max(nslot_r, (int)runs_now[h]);
+        nslot_m = std::max(nslot_m, (int)maps_now[h]);
+      }
+      if (!any) continue;  // a tile no hypothesis looks at
+      const bool out_coh = coh && nslot_r > 0, out_maps = nslot_m > 0;
+      if (gc_buf_reserve(baux, sizeof(SearchAux) * aux.size(), false) != hipSuccess ||
+          gc_buf_reserve(brot, sizeof(double2) * aux.size() * (size_t)nfreq, false) != hipSuccess ||
+          (out_coh && gc_buf_reserve(bcoh, sizeof(double2) * (size_t)((long long)nhyp * nslot_r * cells), false) != hipSuccess) ||
+          (out_maps && (gc_buf_reserve(bpow, sizeof(double) * (size_t)((long long)nhyp * nslot_m * cells), false) != hipSuccess ||
+                        gc_buf_reserve(bpeak, sizeof(gc_ddm_peak) * (size_t)((long long)nhyp * nslot_m * arms), false) != hipSuccess))) {
+        gc_set_error("%s: device allocation failed (%d hypotheses, %d blocks in a tile, %d taps, %d bins)", fn, nhyp, nt, ntaps, nfreq);
+        return GC_E_NOMEM;
+      }
+      GC_HIP(hipMemcpyAsync(baux.p, aux.data(), sizeof(SearchAux) * aux.size(), hipMemcpyHostToDevice, ctx->stream));
+      SearchArgs s;
+      s.blocks = a.blocks;
+      s.chans = a.chans;
+      s.freqs = a.freqs;
+      s.aux = (const SearchAux*)baux.p;
+      s.cell = (const double2*)bout.p;
+      s.rot = (double2*)brot.p;
+      s.racc = (double2*)bracc.p;
+      s.macc = (double*)bmacc.p;
+      s.coh = out_coh ? (double2*)bcoh.p : nullptr;
+      s.pow = out_maps ? (double*)bpow.p : nullptr;
+      s.maps_done = (const int32_t*)bdone.p;
+      s.peaks = (gc_ddm_peak*)bpeak.p;
+      s.fs = ctx->fs;
+      s.t0 = t0;
+      s.nt = nt;
+      s.ntaps = ntaps;
+      s.nfreq = nfreq;
+      s.arms = arms;
+      s.nhyp = nhyp;
+      s.nslot_r = nslot_r;
+      s.nslot_m = nslot_m;
+      hipLaunchKernelGGL(search_rotation_kernel, dim3((unsigned int)((aux.size() * (size_t)nfreq + 255) / 256)), dim3(256), 0, ctx->stream, s);
+      GC_HIP(hipGetLastError());
+      hipLaunchKernelGGL(search_integrate_kernel, dim3((unsigned int)((cells + 255) / 256), (unsigned int)nhyp), dim3(256), 0, ctx->stream, s);
+      GC_HIP(hipGetLastError());
+      if (out_maps && peaks) {
+        GC_HIP(hipMemcpyAsync(bdone.p, maps_now.data(), sizeof(int32_t) * (size_t)nhyp, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(search_peak_kernel, dim3((unsigned int)(nslot_m * arms), (unsigned int)nhyp), dim3(256), 0, ctx->stream, s);
+        GC_HIP(hipGetLastError());
+        hpeak.resize((size_t)nhyp * nslot_m * arms);
+        GC_HIP(hipMemcpyAsync(hpeak.data(), bpeak.p, sizeof(gc_ddm_peak) * hpeak.size(), hipMemcpyDeviceToHost, ctx->stream));
+      }
+      if (out_coh) {
+        hcoh.resize((size_t)((long long)nhyp * nslot_r * cells * 2));
+        GC_HIP(hipMemcpyAsync(hcoh.data(), bcoh.p, sizeof(double) * hcoh.size(), hipMemcpyDeviceToHost, ctx->stream));
+      }
+      if (out_maps && pow) {
+        hpow.resize((size_t)((long long)nhyp * nslot_m * cells));
+        GC_HIP(hipMemcpyAsync(hpow.data(), bpow.p, sizeof(double) * hpow.size(), hipMemcpyDeviceToHost, ctx->stream));
+      }
+      GC_HIP(hipStreamSynchronize(ctx->stream));
+      // the device rows hold the call's arms only: the others are zero on the host's side
+      for (int h = 0; h < nhyp; ++h) {
+        if (out_coh)
+          for (int k = 0; k < runs_now[h]; ++k) {
+            double* o = coh + ((size_t)h * nruns + runs_done[h] + k) * (size_t)(2 * full);
+            std::memcpy(o, hcoh.data() + ((size_t)h * nslot_r + k) * (size_t)(2 * cells), sizeof(double) * (size_t)(2 * cells));
+            std::memset(o + 2 * cells, 0, sizeof(double) * (size_t)(2 * (full - cells)));
+          }
+        for (int k = 0; k < maps_now[h]; ++k) {
+          const size_t q = (size_t)h * nmaps + maps_done[h] + k;
+          if (pow) {
+            double* o = pow + q * (size_t)full;
+            std::memcpy(o, hpow.data() + ((size_t)h * nslot_m + k) * (size_t)cells, sizeof(double) * (size_t)cells);
+            std::memset(o + cells, 0, sizeof(double) * (size_t)(full - cells));
+          }
+          if (peaks)
+            for (int arm = 0; arm < GC_MAX_ARMS; ++arm)
+              peaks[q * GC_MAX_ARMS + arm] = arm < arms ? hpeak[((size_t)h * nslot_m + k) * arms + arm] : gc_ddm_peak{0.0, 0, 0};
+        }
+        runs_done[h] += runs_now[h];
+        maps_done[h] += maps_now[h];
+      }
+    }
+    first += nb;
+  }
+  return GC_OK;
+}
+
 }  // namespace
+
+extern "C" int gc_correlate_ddm_search(gc_context* ctx, int nblocks, const gc_block* blocks, int nhyp, const int32_t* block_shift,
+                                       const double* block_weights, int ntaps, const double* tap_offsets, int nfreq,
+                                       const double* freq_offsets, int nruns, const int32_t* run_len, int nmaps, const int32_t* map_len,
+                                       double* coh, double* pow, gc_ddm_peak* peaks) {
+  if (!ctx || nblocks < 0 || !tap_offsets || !freq_offsets || (nblocks > 0 && !blocks) || nruns < 0 || (nruns > 0 && !run_len) ||
+      (nmaps > 0 && !map_len)) {
+    gc_set_error("gc_correlate_ddm_search: bad arguments");
+    return GC_E_INVALID;
+  }
+  return ddm_search_run("gc_correlate_ddm_search", ctx, nblocks, blocks, nhyp, block_shift, block_weights, ntaps, tap_offsets, nfreq,
+                        freq_offsets, nruns, run_len, nmaps, map_len, coh, pow, peaks);
+}
 
 extern "C" int gc_correlate_bank(gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, double* out) {
   if (!ctx || nblocks < 0 || !tap_offsets || (nblocks > 0 && (!blocks || !out))) {

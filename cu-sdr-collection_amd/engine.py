@@ -273,6 +273,46 @@ class Engine:
                                                      None if pw is None else pw.ctypes.data_as(dp)))
         return (None if coh is None else coh[..., 0] + 1j * coh[..., 1]), pw
 
+    def correlate_ddm_search(self, blocks, offsets, freqs, run_len, map_len=None, shifts=None, weights=None, coherent=False, power=True,
+                             peaks=True):
+        """gc_correlate_ddm_search: correlate_ddm_integrate under many hypotheses from one pass over the samples, every power map's peak
+        picked on the device.  Hypothesis h looks at the sum(run_len) blocks from block shifts[h] on (None: 0) with the weights
+        weights[h, :] - [nhyp, nblocks], indexed by absolute block number (None: all 1) - and its maps are, bit for bit, those of
+        correlate_ddm_integrate(blocks[shifts[h]:shifts[h] + nused], ..., weights=weights[h, shifts[h]:shifts[h] + nused]).  The number
+        of hypotheses is len(shifts), else weights.shape[0], else 1.  map_len None: one power map of all the runs.
+        Returns (complex128 [nhyp, nruns, GC_MAX_ARMS, nfreq, ntaps] if coherent else None,
+                 float64 [nhyp, nmaps, GC_MAX_ARMS, nfreq, ntaps] if power else None,
+                 structured [nhyp, nmaps, GC_MAX_ARMS] with fields power, bin, tap if peaks else None):
+        a peak is the first maximum of its plane walked bin-major, {0.0, 0, 0} for an arm the channel does not have.  With peaks alone
+        neither maps nor coherent sums leave the device."""
+        n = len(blocks)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        frq = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        runs = np.ascontiguousarray(run_len, dtype=np.int32).reshape(-1)
+        if map_len is None:
+            map_len = [runs.shape[0]] if runs.shape[0] else []
+        maps = np.ascontiguousarray(map_len, dtype=np.int32).reshape(-1)
+        sh = None if shifts is None else np.ascontiguousarray(shifts, dtype=np.int32).reshape(-1)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.ndim != 2 or w.shape[1] != n or (sh is not None and w.shape[0] != sh.shape[0]):
+                raise ValueError("correlate_ddm_search: weights are [nhyp, nblocks]")
+        nhyp = sh.shape[0] if sh is not None else w.shape[0] if w is not None else 1
+        nmaps = maps.shape[0]
+        coh = np.zeros((nhyp, runs.shape[0], L.GC_MAX_ARMS, frq.shape[0], off.shape[0], 2)) if coherent else None
+        pw = np.zeros((nhyp, nmaps, L.GC_MAX_ARMS, frq.shape[0], off.shape[0])) if power else None
+        pk = np.zeros((nhyp, nmaps, L.GC_MAX_ARMS), dtype=L.DDM_PEAK_DTYPE) if peaks else None
+        # without a map there is nothing for pow and peaks to hold: the library is asked for neither
+        L.check(self._lib.gc_correlate_ddm_search(self._ctx, n, blocks, nhyp, None if sh is None else sh.ctypes.data_as(ip),
+                                                  None if w is None else w.ctypes.data_as(dp), off.shape[0], off.ctypes.data_as(dp),
+                                                  frq.shape[0], frq.ctypes.data_as(dp), runs.shape[0], runs.ctypes.data_as(ip), nmaps,
+                                                  maps.ctypes.data_as(ip), None if coh is None else coh.ctypes.data_as(dp),
+                                                  None if pw is None or nmaps == 0 else pw.ctypes.data_as(dp),
+                                                  None if pk is None or nmaps == 0 else pk.ctypes.data_as(C.POINTER(L.gc_ddm_peak))))
+        return (None if coh is None else coh[..., 0] + 1j * coh[..., 1]), pw, pk
+
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition
         (corr_multi.hip), 5 hybrid for channels with a derived six-fold arm (corr_cboc.hip), 6 float64 (corr_f64.hip), -1 mixed

@@ -498,6 +498,69 @@ def integrated_delay_doppler_map(fid: Engine, trackResults_k, channel_k, setting
     return pw[:, :arms]
 
 
+def _search_grid(name, nblocks, run, lead, noncoherent):
+    """run_len and map_len of a search whose runs are `run` epochs long and whose hypotheses need `lead` further epochs: the complete
+    runs every hypothesis has, in one map or in maps of `noncoherent` runs (a trailing incomplete map is dropped)."""
+    if run < 1 or (noncoherent is not None and int(noncoherent) < 1):
+        raise ValueError(f"{name}: the run length and noncoherent count epochs and runs (1 at least)")
+    nruns = max(nblocks - lead, 0) // run
+    if noncoherent is not None:
+        nruns -= nruns % int(noncoherent)
+    if nruns < 1:
+        raise ValueError(f"{name}: {nblocks} evaluated epochs do not hold one complete map of runs of {run} epochs for every hypothesis")
+    return [run] * nruns, [nruns] if noncoherent is None else [int(noncoherent)] * (nruns // int(noncoherent))
+
+
+def _search_winner(peaks):
+    """The first maximum over the hypotheses of the first arm's peak power summed over the maps."""
+    return int(np.argmax(peaks["power"][:, :, 0].sum(axis=1)))
+
+
+def bit_edge_search(fid: Engine, trackResults_k, channel_k, settings, offsets, freqs, period, noncoherent=None, signal: str = "GPS_L1CA",
+                    epochs=None):
+    """Where the data-bit edges fall on a channel whose prompt signs cannot be trusted: integrated_delay_doppler_map()'s power maps
+    without a wipe-off, under the `period` alignments of a grid of runs of `period` consecutive evaluated epochs (20 for GPS L1 C/A).
+    Hypothesis h starts its runs at evaluated epoch h; only the alignment at which no run straddles a bit edge adds every run
+    coherently.  Every hypothesis integrates the same number of runs: the complete runs common to all shifts, in one power map, or in
+    maps of `noncoherent` runs each (a trailing incomplete map is dropped).  One gc_correlate_ddm_search call (include/gnsscorr.h): the
+    epochs are correlated once for all alignments, the peaks are picked on the device and nothing else comes back.
+
+    Returns (peaks, shift): peaks a structured array [period, n_maps, arms] with fields power, bin, tap - the first maximum of every
+    map, bin indexing `freqs` and tap `offsets` -, shift the first maximum over the alignments of the first arm's peak power summed
+    over the maps.  ValueError when the evaluated epochs do not hold one complete map for every alignment.
+    Other arguments, refusals and side effects (the engine's slot 255, the sampling frequency) as correlation_function()."""
+    blocks, arms = _tracked_blocks(fid, trackResults_k, channel_k, settings, signal, epochs)
+    period = int(period)
+    run_len, map_len = _search_grid("bit_edge_search", len(blocks), period, period - 1, noncoherent)
+    _, _, peaks = fid.correlate_ddm_search(blocks, offsets, freqs, run_len, map_len=map_len, shifts=np.arange(period), power=False)
+    peaks = peaks[:, :, :arms]
+    return peaks, _search_winner(peaks)
+
+
+def secondary_code_search(fid: Engine, trackResults_k, channel_k, settings, offsets, freqs, code, noncoherent=None,
+                          signal: str = "GPS_L1CA", epochs=None):
+    """The phase of a known secondary code (`code`: its chips as +1 / -1, one per code period - NH10, NH20, CS25, CS100) on a channel
+    whose prompt signs cannot be trusted: integrated_delay_doppler_map()'s power maps over runs of len(code) evaluated epochs, under
+    the len(code) phases of the pattern.  Hypothesis h weights evaluated epoch n with code[(n + h) % len(code)]; only the true phase
+    wipes every chip and adds the whole run coherently.  One power map of all complete runs, or maps of `noncoherent` runs each.
+    One gc_correlate_ddm_search call (include/gnsscorr.h; at most GC_DDM_MAX_HYP chips per call).
+
+    Returns (peaks, phase): peaks a structured array [len(code), n_maps, arms] as bit_edge_search(), phase the first maximum over
+    the hypotheses of the first arm's peak power summed over the maps.
+    Other arguments, refusals and side effects (the engine's slot 255, the sampling frequency) as correlation_function()."""
+    blocks, arms = _tracked_blocks(fid, trackResults_k, channel_k, settings, signal, epochs)
+    chips = np.asarray(code, dtype=np.float64).reshape(-1)
+    if chips.size < 1 or not np.all(np.abs(chips) == 1.0):
+        raise ValueError("secondary_code_search: the code's chips are +1 / -1")
+    nchip = chips.size
+    run_len, map_len = _search_grid("secondary_code_search", len(blocks), nchip, 0, noncoherent)
+    n = np.arange(len(blocks))
+    weights = chips[(n[None, :] + np.arange(nchip)[:, None]) % nchip]
+    _, _, peaks = fid.correlate_ddm_search(blocks, offsets, freqs, run_len, map_len=map_len, weights=weights, power=False)
+    peaks = peaks[:, :, :arms]
+    return peaks, _search_winner(peaks)
+
+
 def tracking_file(fid: Engine, path: str, channel, settings, window_samples: int, signal: str = "GPS_L1CA", pilot_fields: str | None = None,
                   precision: str | None = None, device_loop: bool = False):
     """tracking(fid, channel, settings) on a record FILE that need not fit the device: at most 2 * window_samples samples are

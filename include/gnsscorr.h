@@ -225,6 +225,40 @@ int gc_correlate_ddm_integrate(gc_context* ctx, int nblocks, const gc_block* blo
                                int nruns, const int32_t* run_len, int nmaps, const int32_t* map_len,
                                double* coh, double* pow);
 
+/* gc_correlate_ddm_integrate under many hypotheses at once, each map's peak picked on the device (csrc/corr_bank.hip): the search
+ * over data-bit edges (shifts of the run grid) or over the phases of a secondary code (weight rows) that integrating an untracked
+ * channel past one code period needs.  The block cells are computed ONCE, whatever nhyp is.
+ * Hypotheses: nused = sum(run_len).  Hypothesis h, 0 <= h < nhyp, looks at the window of nused blocks that starts at block
+ *   block_shift[h] (null: every shift 0); its weights are row h of block_weights, laid out [nhyp][nblocks] and indexed by ABSOLUTE
+ *   block number (null: every weight 1).
+ * Identity: the coherent cells and power maps of hypothesis h are, BIT FOR BIT, what gc_correlate_ddm_integrate returns for
+ *     blocks + block_shift[h],  nblocks = nused,  block_weights + h * nblocks + block_shift[h] (or null),
+ *   the same taps, bins, run_len and map_len - so the rotation reference b0 is the first block of each run OF THAT HYPOTHESIS.
+ * Peaks: peaks[(h * nmaps + q) * GC_MAX_ARMS + arm] is the first maximum of that arm's nfreq x ntaps plane of pow: the cells are
+ *   walked bin-major with the tap fastest, starting from cell (0, 0), and the held cell is replaced only on a strict >.  power is
+ *   that cell's value, bin and tap its indices.  An arm the run's channel does not have is all zeros: its peak is {0.0, 0, 0}.
+ * Outputs: coh[((((h * nruns + r) * GC_MAX_ARMS + arm) * nfreq + m) * ntaps + j) * 2 + {0: re, 1: im}],
+ *   pow[(((h * nmaps + q) * GC_MAX_ARMS + arm) * nfreq + m) * ntaps + j], peaks as above.  Each of the three may be null, at least
+ *   one is given; pow and peaks need nmaps >= 1.  With peaks alone neither the maps nor the coherent sums leave the device.
+ * Independence: a hypothesis's bytes do not depend on which other hypotheses are in the call, on their order, on nhyp, on blocks
+ *   outside its window, or on where the library cuts the list.
+ * Refusals: every refusal of gc_correlate_ddm_integrate, with its status, checked over the WHOLE block list.  GC_E_INVALID also for
+ *   nhyp outside 1 .. GC_DDM_MAX_HYP, a negative shift, block_shift[h] + nused > nblocks, nruns < 1 with blocks present, lengths
+ *   that do not sum (map_len to nruns), two channels inside a run of any hypothesis's window, any non-finite entry of
+ *   block_weights, peaks or pow given with nmaps == 0, no output at all.  nblocks == 0 with nruns == 0 and nmaps == 0 is GC_OK (no
+ *   record needed).  A refused call writes none of its outputs. */
+#define GC_DDM_MAX_HYP 128
+typedef struct gc_ddm_peak {
+  double power;
+  int32_t bin;
+  int32_t tap;
+} gc_ddm_peak;
+int gc_correlate_ddm_search(gc_context* ctx, int nblocks, const gc_block* blocks,
+                            int nhyp, const int32_t* block_shift, const double* block_weights,
+                            int ntaps, const double* tap_offsets, int nfreq, const double* freq_offsets,
+                            int nruns, const int32_t* run_len, int nmaps, const int32_t* map_len,
+                            double* coh, double* pow, gc_ddm_peak* peaks);
+
 /* Replay (batched, open-loop) mode: descriptors stay resident in HBM so that the timed
  * region contains only kernel work (SURVEY.md §7 hard part 1a). */
 int gc_replay_prepare(gc_context* ctx, int64_t nblocks, const gc_block* blocks);

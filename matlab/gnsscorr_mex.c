@@ -27,6 +27,13 @@
  *          bin rotated to the carrier phase at the run's first block, each block times weights(b) ([] = 1: +1 / -1 wipes a data bit);
  *          mapLen(q) consecutive runs are added as power ([] = no power maps, one output).  C: 2 x ntaps x (nfreq*3*nruns), rows re, im
  *          ([] with coherent = 0: the coherent sums stay on the device); P: ntaps x (nfreq*3*nmaps)
+ *   [PK, BIN, TAP, P, C] = gnsscorr_mex('correlate_ddm_search', h, blocks, offsets, freqs, runLen, mapLen[, shifts[, weights]])   % the
+ *          integrated maps under nhyp hypotheses from one pass over the samples (gc_correlate_ddm_search): hypothesis k looks at the
+ *          sum(runLen) blocks from block shifts(k) on (0-based; [] = 0) with the weights weights(:, k) (nblocks x nhyp, one row per
+ *          block of the whole list; [] = 1) and is 'correlate_ddm_integrate' on that window, bit for bit.  nhyp = numel(shifts), else
+ *          columns of weights, else 1.  PK, BIN, TAP: 3 x (nmaps*nhyp), each map's first maximum per arm - its power and its 0-based
+ *          bin and tap (freqs(BIN + 1), offsets(TAP + 1)); P (asked for with a fourth output): ntaps x (nfreq*3*nmaps*nhyp);
+ *          C (a fifth): 2 x ntaps x (nfreq*3*nruns*nhyp).  With three outputs neither maps nor coherent sums leave the device
  *   [trk, epochs, status] = gnsscorr_mex('track', h, params_struct, channels)   % channels: 5 x nch
  *   res  = gnsscorr_mex('acquire_coarse', h, acq_struct, sampledCodes)          % int8 spc x nprn
  *   f    = gnsscorr_mex('acquire_fine_l1ca', h, acq_struct, caCode, codePhase, coarseFreq)
@@ -150,7 +157,8 @@ static gc_channel_init* channel_inits_from(const mxArray* a, int* nch_out) {
 }
 
 /* blocks: 8 x nblocks, rows = channel, first_sample (0-based), blksize, remCodePhase, codePhaseStep, earlyLateSpc, carrFreq,
- * remCarrPhase - the quantities of tracking.m:212-222,249,277 ('correlate', 'correlate_bank', 'correlate_ddm', 'correlate_ddm_integrate') */
+ * remCarrPhase - the quantities of tracking.m:212-222,249,277 ('correlate', 'correlate_bank', 'correlate_ddm', 'correlate_ddm_integrate',
+ * 'correlate_ddm_search') */
 static gc_block* blocks_from(const mxArray* a, int* n_out) {
   if (mxGetM(a) != 8) mexErrMsgIdAndTxt("gnsscorr:usage", "blocks must be 8 x nblocks");
   const double* b = mxGetDoubles(a);
@@ -310,6 +318,47 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxFree(blk);
     if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
     if (rc) fail("gc_correlate_ddm_integrate");
+  } else if (!strcmp(cmd, "correlate_ddm_search")) {
+    /* blocks, offsets, freqs and runLen as for 'correlate_ddm_integrate'; mapLen, shifts: double vectors; weights: nblocks x nhyp
+     * (column k is row k of gc_correlate_ddm_search's block_weights).  The results are the library's `peaks` taken apart into three
+     * arrays (arm, map, hypothesis) and its `pow` and `coh` as they lie in memory, the last dimensions folded. */
+    if (nrhs < 7 || !mxIsDouble(prhs[3]) || !mxIsDouble(prhs[4]) || !mxIsDouble(prhs[5]) || !mxIsDouble(prhs[6]) ||
+        (nrhs > 7 && !mxIsDouble(prhs[7])) || (nrhs > 8 && !mxIsDouble(prhs[8])))
+      mexErrMsgIdAndTxt("gnsscorr:usage", "correlate_ddm_search: h, blocks 8 x nblocks, offsets, freqs, runLen, mapLen[, shifts[, weights]]");
+    if (nlhs < 3) mexErrMsgIdAndTxt("gnsscorr:usage", "correlate_ddm_search: [PK, BIN, TAP[, P[, C]]] = ...");
+    int n = 0;
+    gc_block* blk = blocks_from(prhs[2], &n);
+    const int ntaps = (int)mxGetNumberOfElements(prhs[3]), nfreq = (int)mxGetNumberOfElements(prhs[4]);
+    const int nruns = (int)mxGetNumberOfElements(prhs[5]), nmaps = (int)mxGetNumberOfElements(prhs[6]);
+    const int nsh = nrhs > 7 ? (int)mxGetNumberOfElements(prhs[7]) : 0, nw = nrhs > 8 ? (int)mxGetNumberOfElements(prhs[8]) : 0;
+    const int nhyp = nsh ? nsh : nw ? (int)mxGetN(prhs[8]) : 1;
+    if (nw && ((int)mxGetM(prhs[8]) != n || (int)mxGetN(prhs[8]) != nhyp))
+      mexErrMsgIdAndTxt("gnsscorr:usage", "correlate_ddm_search: weights must be [] or nblocks x nhyp");
+    int32_t* len = (int32_t*)mxCalloc((size_t)(nruns + nmaps + nsh > 0 ? nruns + nmaps + nsh : 1), sizeof *len);
+    for (int r = 0; r < nruns; ++r) len[r] = (int32_t)mxGetDoubles(prhs[5])[r];
+    for (int q = 0; q < nmaps; ++q) len[nruns + q] = (int32_t)mxGetDoubles(prhs[6])[q];
+    for (int k = 0; k < nsh; ++k) len[nruns + nmaps + k] = (int32_t)mxGetDoubles(prhs[7])[k];
+    const size_t npk = (size_t)GC_MAX_ARMS * (size_t)nmaps * (size_t)(nhyp > 0 ? nhyp : 0);
+    gc_ddm_peak* pk = (gc_ddm_peak*)mxCalloc(npk ? npk : 1, sizeof *pk);
+    for (int o = 0; o < 3; ++o) plhs[o] = mxCreateDoubleMatrix(GC_MAX_ARMS, (mwSize)(npk / GC_MAX_ARMS), mxREAL);
+    if (nlhs > 3) plhs[3] = mxCreateDoubleMatrix((mwSize)ntaps, (mwSize)nfreq * GC_MAX_ARMS * (mwSize)nmaps * (mwSize)(nhyp > 0 ? nhyp : 0), mxREAL);
+    if (nlhs > 4) {
+      const mwSize cdims[3] = {2, (mwSize)ntaps, (mwSize)nfreq * GC_MAX_ARMS * (mwSize)nruns * (mwSize)(nhyp > 0 ? nhyp : 0)};
+      plhs[4] = mxCreateNumericArray(3, cdims, mxDOUBLE_CLASS, mxREAL);
+    }
+    int rc = gc_correlate_ddm_search(handle(prhs[1]), n, blk, nhyp, nsh ? len + nruns + nmaps : NULL, nw ? mxGetDoubles(prhs[8]) : NULL, ntaps,
+                                     mxGetDoubles(prhs[3]), nfreq, mxGetDoubles(prhs[4]), nruns, len, nmaps, len + nruns,
+                                     nlhs > 4 ? mxGetDoubles(plhs[4]) : NULL, nlhs > 3 ? mxGetDoubles(plhs[3]) : NULL, pk);
+    for (size_t i = 0; i < npk && !rc; ++i) {
+      mxGetDoubles(plhs[0])[i] = pk[i].power;
+      mxGetDoubles(plhs[1])[i] = (double)pk[i].bin;
+      mxGetDoubles(plhs[2])[i] = (double)pk[i].tap;
+    }
+    mxFree(pk);
+    mxFree(len);
+    mxFree(blk);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
+    if (rc) fail("gc_correlate_ddm_search");
   } else if (!strcmp(cmd, "track") || !strcmp(cmd, "track_device") || !strcmp(cmd, "track_file") || !strcmp(cmd, "track_file_device")) {
     /* [trk, epochs, status] = gnsscorr_mex('track', h, p, chanTable)
        [trk, epochs, status] = gnsscorr_mex('track_file', h, p, chanTable, fileName, windowSamples, dataType, fileType[, 'QI']):
