@@ -33,6 +33,11 @@ constexpr int kFW = 64;  // one wavefront per workgroup
 #ifndef GC_SCHED_GROUP
 #define GC_SCHED_GROUP 4
 #endif
+// A/B (scripts/variants.sh, docs/KNOBS.md): 1 = the replay instantiations' chunk loop as before round 7 - the next chunk's load
+// issued in front of the wait for this chunk's words.
+#ifndef GC_FAST_PARENT_SCHEDULE
+#define GC_FAST_PARENT_SCHEDULE 0
+#endif
 
 // Running sums of sample j to LDS: ds_write_addtid_b32 (address = M0 + offset + 4*lane, no address VGPR) takes 2 LDS
 // cycles per wave-store, half of any other 4-byte store (MI355X_MICROARCH.md, LDS): the stores, not the VALU,
@@ -188,6 +193,10 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
   constexpr int kPfWords = SPL * Fmt<MODE>::bps / 4;
   [[maybe_unused]] unsigned int pf_w[kPfWords];
   [[maybe_unused]] long long pf_off = -1;
+  // Replay: the next chunk's load goes out AFTER the wait for this chunk's words.  Issued in front of it, the compiler's wait for
+  // this chunk's words was s_waitcnt vmcnt(0) - the counter cannot tell the two buffers apart across the loop's back edge - and so
+  // every chunk sat out the whole latency of the load that had just been issued for the next one.
+  constexpr bool kLoadAfterWait = !CL && !DEVLOOP && GC_FAST_PARENT_SCHEDULE == 0;
   for (int bi = (WIDE != 0 && !wave_items) ? wave : 0; bi < nloop; bi += (WIDE != 0 && !wave_items) ? 4 : 1) {
   const long long lb = DEVLOOP ? wq : (grp * p.bpw + bi) * p.stride + cslot;
   if (lb >= p.nblocks) break;
@@ -509,10 +518,21 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
       pf_off = -1;
     }
     if (!fetched) load_k(0, wa);
+    // The words are used from here on.  The "+v" ties place the compiler's wait for them here; the one "memory" clobber behind them is
+    // what keeps load_k below that wait (a load may not move above a statement that could write memory).
+    auto arrived = [&](unsigned int (&w)[NW]) {
+      if constexpr (kLoadAfterWait) {
+#pragma unroll
+        for (int q = 0; q < NW; ++q) asm volatile("" : "+v"(w[q]));
+        asm volatile("" : : : "memory");
+      }
+    };
     for (int k = 0;; k += 2) {
+      arrived(wa);
       if (k + 1 < iters) load_k(k + 1, wb);
       process(wa, k);
       if (k + 1 >= iters) break;
+      arrived(wb);
       if (k + 2 < iters) load_k(k + 2, wa);
       process(wb, k + 1);
       if (k + 2 >= iters) break;
