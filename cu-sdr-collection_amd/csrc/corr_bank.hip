@@ -37,10 +37,9 @@
 //   sums        float32 per chunk and (arm, bin, tap) - lanes by fixed shuffles -, written as float64 partials
 //               [chunk][arm][bin][tap][2] and added over a block's chunks in index order by bank_combine_kernel.  No atomics:
 //               the same input gives the same bits.
-#include <algorithm>
-#include <cmath>
+#include <cstring>
 
-#include "corr_common.h"
+#include "bank_plan.h"
 
 using namespace gcorr;
 
@@ -53,11 +52,9 @@ using namespace gcorr;
 
 namespace {
 
-constexpr int kBankChunk = 1024;  // S: samples per work item
 constexpr int kBankWG = 256;      // threads per workgroup: kBankChunk / kBankWG consecutive samples per thread in the prefix sums
 constexpr int kBankSPT = kBankChunk / kBankWG;
 constexpr int kBankWaves = kBankWG / 64;
-constexpr long long kBankPartialBytes = 256LL << 20;  // partial sums of one sub-batch of blocks at most
 
 template <int MODE>
 __device__ __forceinline__ void bank_load_sample(const uint8_t* __restrict__ base, long long idx, float& a, float& b) {
@@ -113,101 +110,6 @@ int bank_record_mode(const gc_context* ctx) {
   return ctx->if_layout == GC_IQ ? I16_IQ : ctx->if_layout == GC_QI ? I16_QI : I16_REAL;
 }
 
-// What gc_correlate_bank accepts (include/gnsscorr.h), for it and for the functions defined through it (`fn`: the name in the
-// error texts); *arms = the most arms a channel of the list has.
-int bank_validate(const char* fn, const gc_context* ctx, int nblocks, const gc_block* b, int ntaps, const double* off, int* arms) {
-  if (ntaps < 1 || ntaps > GC_BANK_MAX_TAPS) {
-    gc_set_error("%s: %d taps (1 .. %d)", fn, ntaps, GC_BANK_MAX_TAPS);
-    return GC_E_INVALID;
-  }
-  double omax = 0.0;
-  for (int j = 0; j < ntaps; ++j) {
-    if (!std::isfinite(off[j])) {
-      gc_set_error("%s: tap offset %d is not finite", fn, j);
-      return GC_E_INVALID;
-    }
-    omax = std::max(omax, std::fabs(off[j]));
-  }
-  if (nblocks == 0) return GC_OK;  // an empty list is no call sequence error, as in gc_correlate
-  if (ctx->precision != GC_PREC_F32) {
-    gc_set_error("%s: float32 kernels only (gc_set_precision GC_PREC_F32)", fn);
-    return GC_E_UNSUPPORTED;
-  }
-  if (!ctx->d_if) {
-    gc_set_error("no IF buffer loaded");
-    return GC_E_STATE;
-  }
-  if (!(ctx->fs > 0)) {
-    gc_set_error("sampling frequency not set (gc_set_sampling_freq)");
-    return GC_E_STATE;
-  }
-  *arms = 1;
-  bool seen[GC_MAX_CHANNELS] = {false};
-  for (int i = 0; i < nblocks; ++i) {
-    const gc_block& k = b[i];
-    if (k.channel < 0 || k.channel >= GC_MAX_CHANNELS || !ctx->ch[k.channel].configured) {
-      gc_set_error("block %d: channel %d not configured", i, k.channel);
-      return GC_E_STATE;
-    }
-    const HostChannel& c = ctx->ch[k.channel];
-    double max_mult = 1.0;
-    for (int a = 0; a < c.arms; ++a) {
-      if (!c.d_tab[a]) {
-        gc_set_error("block %d: channel %d arm %d has no code table", i, k.channel, a);
-        return GC_E_STATE;
-      }
-      if (k.table_offset[a] != 0) {
-        gc_set_error("block %d: %s reads whole tables periodically (table_offset must be 0)", i, fn);
-        return GC_E_INVALID;
-      }
-      max_mult = std::max(max_mult, c.mult[a]);
-    }
-    if (!seen[k.channel]) {  // per channel: no window, pads that are the period, every offset within one period
-      seen[k.channel] = true;
-      *arms = std::max(*arms, c.arms);
-      for (int a = 0; a < c.arms; ++a) {
-        if (c.window[a] > 0) {
-          gc_set_error("channel %d arm %d: %s does not take a code window (gc_set_code_window)", k.channel, a, fn);
-          return GC_E_UNSUPPORTED;
-        }
-        const std::vector<int8_t>& t = c.h_tab[a];
-        const int n = c.nent[a];
-        if ((int)t.size() != n || n < 3 || t[0] != t[n - 2] || t[n - 1] != t[1]) {
-          gc_set_error("channel %d arm %d: the table's pads are not its period ([c(end) c c(1)])", k.channel, a);
-          return GC_E_INVALID;
-        }
-        if (!(omax * c.index_scale * c.mult[a] < (double)(n - 2))) {
-          gc_set_error("channel %d arm %d: a tap offset of %g chips reaches a code period (%d entries) or more", k.channel, a, omax, n - 2);
-          return GC_E_INVALID;
-        }
-      }
-    }
-    if (k.blksize <= 0 || k.first_sample < 0 || !(k.code_phase_step > 0) || !(k.rem_code_phase > -1.0) ||
-        !std::isfinite(k.rem_code_phase) || !std::isfinite(k.carr_freq) || !std::isfinite(k.rem_carr_phase)) {
-      gc_set_error("block %d: invalid descriptor", i);
-      return GC_E_INVALID;
-    }
-    const double rate = k.code_phase_step * c.index_scale * max_mult;  // table entries per sample of the fastest arm
-    if (rate > 1.0) {
-      gc_set_error("block %d: %g table entries per sample (%s takes at most one)", i, rate, fn);
-      return GC_E_UNSUPPORTED;
-    }
-    if (!(rate >= 1.0 / 65536.0)) {
-      gc_set_error("block %d: %g table entries per sample (below 2^-16)", i, rate);
-      return GC_E_INVALID;
-    }
-    if (!(((double)k.blksize * k.code_phase_step + std::fabs(k.rem_code_phase) + omax) * c.index_scale * max_mult < 2147483000.0)) {
-      gc_set_error("block %d: the ramps' table indices leave int32", i);
-      return GC_E_INVALID;
-    }
-    if ((uint64_t)k.first_sample + (uint64_t)k.blksize > ctx->if_nsamples) {
-      gc_set_error("block %d: samples [%lld, %lld) exceed the IF buffer (%llu samples)", i, (long long)k.first_sample,
-                   (long long)(k.first_sample + k.blksize), (unsigned long long)ctx->if_nsamples);
-      return GC_E_RANGE;  // tracking.m:241-245
-    }
-  }
-  return GC_OK;
-}
 constexpr int kDdmGroup = GC_DDM_GROUP;
 static_assert(kDdmGroup >= 1 && kDdmGroup * (kBankChunk + 1) * 8 + kDdmGroup * kBankWaves * 8 <= 160 * 1024, "a workgroup's LDS");
 
@@ -407,32 +309,6 @@ int bank_launch_chunks(gc_context* ctx, const BankArgs& a, int total_chunks) {
 
 // ---- what gc_correlate_bank / gc_correlate_ddm (bank_run) and gc_correlate_ddm_integrate (ddm_integrate_run) share ------------------
 
-// The argument check of the functions defined through the bank.  freq_offsets == nullptr is the bank itself.
-int bank_check(const char* fn, const gc_context* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* tap_offsets, int nfreq,
-               const double* freq_offsets, int* arms) {
-  if (freq_offsets) {
-    if (nfreq < 1 || nfreq > GC_DDM_MAX_FREQS) {
-      gc_set_error("%s: %d frequency bins (1 .. %d)", fn, nfreq, GC_DDM_MAX_FREQS);
-      return GC_E_INVALID;
-    }
-    for (int m = 0; m < nfreq; ++m)
-      if (!std::isfinite(freq_offsets[m])) {
-        gc_set_error("%s: frequency offset %d is not finite", fn, m);
-        return GC_E_INVALID;
-      }
-  }
-  int rc = bank_validate(fn, ctx, nblocks, blocks, ntaps, tap_offsets, arms);
-  if (rc) return rc;
-  if (freq_offsets)
-    for (int i = 0; i < nblocks; ++i)
-      for (int m = 0; m < nfreq; ++m)
-        if (!std::isfinite(blocks[i].carr_freq + freq_offsets[m])) {  // what the bank answers to that carr_freq
-          gc_set_error("block %d: invalid descriptor (carr_freq + frequency offset %d is not finite)", i, m);
-          return GC_E_INVALID;
-        }
-  return GC_OK;
-}
-
 // The channels, the tap offsets and the frequency offsets on the device.
 int bank_upload_grids(const char* fn, gc_context* ctx, int ntaps, const double* tap_offsets, int nfreq, const double* freq_offsets) {
   GC_HIP(hipSetDevice(ctx->device));
@@ -448,23 +324,6 @@ int bank_upload_grids(const char* fn, gc_context* ctx, int ntaps, const double* 
   GC_HIP(hipMemcpyAsync(btap.p, tap_offsets, sizeof(double) * (size_t)ntaps, hipMemcpyHostToDevice, ctx->stream));
   if (freq_offsets) GC_HIP(hipMemcpyAsync(bfrq.p, freq_offsets, sizeof(double) * (size_t)nfreq, hipMemcpyHostToDevice, ctx->stream));
   return GC_OK;
-}
-
-// Chunks whose partial sums (`row` doubles each) fit the budget of one sub-batch.
-long long bank_max_chunks(long long row) { return std::max<long long>(1, std::min<long long>(kBankPartialBytes / (row * 8), 0x40000000LL)); }
-
-// The sub-batch that begins at block `first`: blocks while their chunks' partial sums fit (one block at least).  base[k] = chunks
-// before its block k; returns the number of blocks.
-int bank_cut(const gc_block* blocks, int nblocks, int first, long long max_chunks, std::vector<int32_t>& base) {
-  base.assign(1, 0);
-  int nb = 0;
-  while (first + nb < nblocks) {
-    const long long c = ((long long)blocks[first + nb].blksize + kBankChunk - 1) / kBankChunk;
-    if (nb > 0 && base.back() + c > max_chunks) break;
-    base.push_back((int32_t)(base.back() + c));
-    ++nb;
-  }
-  return nb;
 }
 
 int bank_nomem(const char* fn, bool ddm, int nb, long long chunks, int ntaps, int nfreq) {
@@ -503,22 +362,37 @@ int bank_chunks(const char* fn, gc_context* ctx, const gc_block* blocks, int nb,
   return ddm ? bank_launch_chunks<kDdmGroup>(ctx, *a, (int)chunks) : bank_launch_chunks<1>(ctx, *a, (int)chunks);
 }
 
-// n device rows of `row` doubles to host rows of `full` >= row doubles; waits for the stream.  The device rows hold the call's arms
-// only: the others are zero on the host's side.
-int bank_fetch(gc_context* ctx, double* dst, const void* src, long long n, long long row, long long full, std::vector<double>& compact) {
-  if (row == full) {
-    GC_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)(n * row), hipMemcpyDeviceToHost, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    return GC_OK;
-  }
-  compact.resize((size_t)(n * row));
-  GC_HIP(hipMemcpyAsync(compact.data(), src, sizeof(double) * compact.size(), hipMemcpyDeviceToHost, ctx->stream));
-  GC_HIP(hipStreamSynchronize(ctx->stream));
+// n compact rows of `row` elements to n rows of `full` >= row elements, the rest of each zero: the device rows hold the call's arms
+// only, the caller's rows GC_MAX_ARMS of them.
+template <typename T>
+void bank_spread(T* dst, const T* src, long long n, long long row, long long full) {
   for (long long b = 0; b < n; ++b) {
-    double* o = dst + (size_t)b * full;
-    std::memcpy(o, compact.data() + (size_t)b * row, sizeof(double) * (size_t)row);
-    std::memset(o + row, 0, sizeof(double) * (size_t)(full - row));
+    std::memcpy(dst + b * full, src + b * row, sizeof(T) * (size_t)row);
+    std::memset(dst + b * full + row, 0, sizeof(T) * (size_t)(full - row));
   }
+}
+
+// n device rows of `row` doubles to host rows of `full` >= row doubles; waits for the stream.
+int bank_fetch(gc_context* ctx, double* dst, const void* src, long long n, long long row, long long full, std::vector<double>& compact) {
+  if (row != full) compact.resize((size_t)(n * row));
+  GC_HIP(hipMemcpyAsync(row == full ? dst : compact.data(), src, sizeof(double) * (size_t)(n * row), hipMemcpyDeviceToHost, ctx->stream));
+  GC_HIP(hipStreamSynchronize(ctx->stream));
+  if (row != full) bank_spread(dst, compact.data(), n, row, full);
+  return GC_OK;
+}
+
+// A sub-batch's cells [block][arm][bin][tap][2] in BANK_OUT: room for them, bank_chunks, and the combine kernel.  *a as bank_chunks
+// leaves it, with `out` set.
+int bank_cells(const char* fn, gc_context* ctx, const gc_block* blocks, int nb, const std::vector<int32_t>& base, int ntaps, int nfreq,
+               bool ddm, int arms, BankArgs* a) {
+  const long long row = (long long)arms * nfreq * ntaps * 2;
+  GcBuf& bout = ctx->bank[gc_context::BANK_OUT];
+  if (gc_buf_reserve(bout, sizeof(double) * (size_t)(nb * row), false) != hipSuccess) return bank_nomem(fn, ddm, nb, base.back(), ntaps, nfreq);
+  const int rc = bank_chunks(fn, ctx, blocks, nb, base, ntaps, nfreq, ddm, arms, a);
+  if (rc) return rc;
+  a->out = (double*)bout.p;
+  hipLaunchKernelGGL(bank_combine_kernel, dim3((unsigned int)((nb * row + 255) / 256)), dim3(256), 0, ctx->stream, *a);
+  GC_HIP(hipGetLastError());
   return GC_OK;
 }
 
@@ -533,21 +407,14 @@ int bank_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* block
   if ((rc = bank_upload_grids(fn, ctx, ntaps, tap_offsets, nfreq, freq_offsets))) return rc;
   const long long row = (long long)arms * nfreq * ntaps * 2;  // doubles per chunk (partials) and per block (results)
   const long long full = (long long)GC_MAX_ARMS * nfreq * ntaps * 2;
-  const long long max_chunks = bank_max_chunks(row);
-  GcBuf& bout = ctx->bank[gc_context::BANK_OUT];
+  const long long max_chunks = bank_max_chunks(row, BankBudget());
   std::vector<int32_t> base;
   std::vector<double> compact;
-  for (int first = 0; first < nblocks;) {
-    const int nb = bank_cut(blocks, nblocks, first, max_chunks, base);
-    if (gc_buf_reserve(bout, sizeof(double) * (size_t)(nb * row), false) != hipSuccess)
-      return bank_nomem(fn, freq_offsets != nullptr, nb, base.back(), ntaps, nfreq);
+  for (int first = 0, nb; first < nblocks; first += nb) {
+    nb = bank_cut(blocks, nblocks, first, max_chunks, base);
     BankArgs a;
-    if ((rc = bank_chunks(fn, ctx, blocks + first, nb, base, ntaps, nfreq, freq_offsets != nullptr, arms, &a))) return rc;
-    a.out = (double*)bout.p;
-    hipLaunchKernelGGL(bank_combine_kernel, dim3((unsigned int)((nb * row + 255) / 256)), dim3(256), 0, ctx->stream, a);
-    GC_HIP(hipGetLastError());
-    if ((rc = bank_fetch(ctx, out + (size_t)first * full, bout.p, nb, row, full, compact))) return rc;
-    first += nb;
+    if ((rc = bank_cells(fn, ctx, blocks + first, nb, base, ntaps, nfreq, freq_offsets != nullptr, arms, &a))) return rc;
+    if ((rc = bank_fetch(ctx, out + (size_t)first * full, a.out, nb, row, full, compact))) return rc;
   }
   return GC_OK;
 }
@@ -559,11 +426,6 @@ int bank_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* block
 // phasor ddm_rotation_kernel left in a scratch array, weights and accumulates in block order.  ddm_power_kernel, a thread per map
 // cell, adds the runs' powers in run order.  A run or map the sub-batch walk cuts goes on from its own float64 accumulators in the
 // next sub-batch: the additions are the same ones in the same order wherever the cut falls.
-
-struct DdmBlockAux {
-  long long dn;  // first_sample - first_sample of the run's first block
-  double w;      // the block's weight
-};
 
 struct DdmArgs {
   const gc_block* blocks;
@@ -583,15 +445,21 @@ struct DdmArgs {
   int carry_map;  // map 0 likewise, from pow[0]
 };
 
+// (cospi(2u), sinpi(2u)) with x = (f * dn) / fs, u = x - rint(x): the rotation of bin f for a block dn samples after the first block
+// of its run.
+__device__ __forceinline__ double2 ddm_phasor(double f, long long dn, double fs) {
+  const double x = __dmul_rn(f, (double)dn) / fs;
+  const double u = x - rint(x);
+  double s, c;
+  sincospi(2.0 * u, &s, &c);
+  return make_double2(c, s);
+}
+
 __global__ void ddm_rotation_kernel(const DdmArgs p) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)p.nblocks * p.nfreq) return;
   const int b = (int)(i / p.nfreq), m = (int)(i - (long long)b * p.nfreq);
-  const double x = __dmul_rn(p.freqs[m], (double)p.aux[b].dn) / p.fs;
-  const double u = x - rint(x);
-  double s, c;
-  sincospi(2.0 * u, &s, &c);
-  p.rot[i] = make_double2(c, s);
+  p.rot[i] = ddm_phasor(p.freqs[m], p.aux[b].dn, p.fs);
 }
 
 __global__ __launch_bounds__(256) void ddm_integrate_kernel(const DdmArgs p) {
@@ -638,171 +506,88 @@ __global__ __launch_bounds__(256) void ddm_power_kernel(const DdmArgs p) {
   p.pow[i] = acc;
 }
 
-// One sub-batch of the integrating walk: its blocks [first, first + nb), the runs r0 .. r0 + nr - 1 that have blocks in it - the
-// first nfin of them end in it -, and the maps q0 .. q0 + nm - 1 those finished runs belong to, the first mfin of which end with them.
-struct DdmStep {
-  int first = 0, nb = 0;
-  int r0 = 0, nr = 0, nfin = 0;
-  int q0 = 0, nm = 0, mfin = 0;
-};
-
-// The step after `s` (s.nb == 0: the first).  run_start / map_start: blocks before run r / runs before map q.
-void ddm_next_step(DdmStep& s, const gc_block* blocks, int nblocks, long long max_chunks, const std::vector<int>& run_start,
-                   const std::vector<int>& map_start, std::vector<int32_t>& base) {
-  s.first += s.nb;
-  s.r0 += s.nfin;
-  s.q0 += s.mfin;
-  s.nb = bank_cut(blocks, nblocks, s.first, max_chunks, base);
-  const int end = s.first + s.nb;
-  int r1 = s.r0;
-  while (run_start[r1 + 1] < end) ++r1;
-  s.nr = r1 - s.r0 + 1;
-  s.nfin = run_start[r1 + 1] == end ? s.nr : s.nr - 1;
-  s.nm = s.mfin = 0;
-  if (map_start.size() > 1 && s.nfin > 0) {
-    const int rend = s.r0 + s.nfin;
-    int q1 = s.q0;
-    while (map_start[q1 + 1] < rend) ++q1;
-    s.nm = q1 - s.q0 + 1;
-    s.mfin = map_start[q1 + 1] == rend ? s.nm : s.nm - 1;
-  }
+// The kernel arguments of a step (bank_plan.h: DdmStep, DdmLaunch) from those bank_chunks returned.
+DdmArgs ddm_args(gc_context* ctx, const BankArgs& a, const DdmStep& s, const DdmLaunch& l) {
+  DdmArgs d;
+  d.blocks = a.blocks;
+  d.chans = a.chans;
+  d.chunk_base = a.chunk_base;
+  d.freqs = a.freqs;
+  d.aux = (const DdmBlockAux*)ctx->bank[gc_context::BANK_AUX].p;
+  d.partial = (const double2*)a.partial;
+  d.rot = (double2*)ctx->bank[gc_context::BANK_ROT].p;
+  d.run_base = (const int32_t*)ctx->bank[gc_context::BANK_RUNS].p;
+  d.coh = (double2*)ctx->bank[gc_context::BANK_COH].p;
+  d.map_base = (const int32_t*)ctx->bank[gc_context::BANK_MAPS].p;
+  d.pow = (double*)ctx->bank[gc_context::BANK_POW].p;
+  d.fs = a.fs;
+  d.nblocks = s.nb;
+  d.ntaps = a.ntaps;
+  d.nfreq = a.nfreq;
+  d.arms = a.arms;
+  d.nruns = s.nr;
+  d.nmaps = s.nm;
+  d.carry_run = l.carry_run;
+  d.carry_map = l.carry_map;
+  return d;
 }
 
+// Check, plan (bank_plan.h), then per sub-batch upload, launch, fetch.
 int ddm_integrate_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* blocks, const double* weights, int ntaps,
                       const double* tap_offsets, int nfreq, const double* freq_offsets, int nruns, const int32_t* run_len, int nmaps,
                       const int32_t* map_len, double* coh, double* pow) {
   int arms = 1;
-  int rc = bank_check(fn, ctx, nblocks, blocks, ntaps, tap_offsets, nfreq, freq_offsets, &arms);
+  BankPartition part;
+  int rc = ddm_integrate_check(fn, ctx, nblocks, blocks, weights, ntaps, tap_offsets, nfreq, freq_offsets, nruns, run_len, nmaps, map_len,
+                               coh != nullptr, pow != nullptr, &arms, &part);
   if (rc) return rc;
-  if (nmaps < 0 || (nblocks > 0 && nruns < 1)) {
-    gc_set_error("%s: %d runs, %d maps for %d blocks", fn, nruns, nmaps, nblocks);
-    return GC_E_INVALID;
-  }
-  std::vector<int> run_start(1, 0), map_start(1, 0);  // blocks before run r, runs before map q
-  for (int r = 0; r < nruns; ++r) {
-    if (run_len[r] < 1 || run_len[r] > nblocks - run_start.back()) {
-      gc_set_error("%s: run %d has %d blocks (1 at least, %d in all)", fn, r, (int)run_len[r], nblocks);
-      return GC_E_INVALID;
-    }
-    run_start.push_back(run_start.back() + run_len[r]);
-  }
-  if (run_start.back() != nblocks) {
-    gc_set_error("%s: the runs hold %d blocks of %d", fn, run_start.back(), nblocks);
-    return GC_E_INVALID;
-  }
-  for (int q = 0; q < nmaps; ++q) {
-    if (map_len[q] < 1 || map_len[q] > nruns - map_start.back()) {
-      gc_set_error("%s: map %d has %d runs (1 at least, %d in all)", fn, q, (int)map_len[q], nruns);
-      return GC_E_INVALID;
-    }
-    map_start.push_back(map_start.back() + map_len[q]);
-  }
-  if (nmaps > 0 && map_start.back() != nruns) {
-    gc_set_error("%s: the maps hold %d runs of %d", fn, map_start.back(), nruns);
-    return GC_E_INVALID;
-  }
-  for (int r = 0; r < nruns; ++r)
-    for (int b = run_start[r] + 1; b < run_start[r + 1]; ++b)
-      if (blocks[b].channel != blocks[run_start[r]].channel) {
-        gc_set_error("%s: run %d has blocks of channels %d and %d", fn, r, blocks[run_start[r]].channel, blocks[b].channel);
-        return GC_E_INVALID;
-      }
-  if (weights)
-    for (int b = 0; b < nblocks; ++b)
-      if (!std::isfinite(weights[b])) {
-        gc_set_error("%s: the weight of block %d is not finite", fn, b);
-        return GC_E_INVALID;
-      }
-  if (nmaps > 0 ? !pow : !coh) {
-    gc_set_error(nmaps > 0 ? "%s: power maps asked for without an output" : "%s: neither coherent sums nor power maps asked for", fn);
-    return GC_E_INVALID;
-  }
   if (nblocks == 0) return GC_OK;
   if ((rc = bank_upload_grids(fn, ctx, ntaps, tap_offsets, nfreq, freq_offsets))) return rc;
   const long long cells = (long long)arms * nfreq * ntaps, full = (long long)GC_MAX_ARMS * nfreq * ntaps;
-  const long long max_chunks = bank_max_chunks(2 * cells);
-  std::vector<int32_t> base, index, mindex;  // chunks before a block, blocks before a run, finished runs before a map: of a sub-batch
-  // The walk once without the device: the most blocks, runs and maps a sub-batch holds.  The accumulators a cut run or map goes on
-  // from live in these buffers, so they must not be reallocated during the walk.
-  int max_nb = 0, max_nr = 0, max_nm = 0;
-  for (DdmStep s; s.first + s.nb < nblocks;) {
-    ddm_next_step(s, blocks, nblocks, max_chunks, run_start, map_start, base);
-    max_nb = std::max(max_nb, s.nb);
-    max_nr = std::max(max_nr, s.nr);
-    max_nm = std::max(max_nm, s.nm);
-  }
+  const long long max_chunks = bank_max_chunks(2 * cells, BankBudget());
+  // The accumulators a cut run or map goes on from live in these buffers, so they are sized for the whole walk before it begins.
+  const DdmSizes z = ddm_walk_sizes(blocks, nblocks, max_chunks, part);
   GcBuf& baux = ctx->bank[gc_context::BANK_AUX];
   GcBuf& brot = ctx->bank[gc_context::BANK_ROT];
   GcBuf& brun = ctx->bank[gc_context::BANK_RUNS];
   GcBuf& bcoh = ctx->bank[gc_context::BANK_COH];
   GcBuf& bmap = ctx->bank[gc_context::BANK_MAPS];
   GcBuf& bpow = ctx->bank[gc_context::BANK_POW];
-  if (gc_buf_reserve(baux, sizeof(DdmBlockAux) * (size_t)max_nb, false) != hipSuccess ||
-      gc_buf_reserve(brot, sizeof(double2) * (size_t)max_nb * (size_t)nfreq, false) != hipSuccess ||
-      gc_buf_reserve(brun, sizeof(int32_t) * (size_t)(max_nr + 1), false) != hipSuccess ||
-      gc_buf_reserve(bcoh, sizeof(double2) * (size_t)(max_nr * cells), false) != hipSuccess ||
-      gc_buf_reserve(bmap, sizeof(int32_t) * (size_t)(max_nm + 1), false) != hipSuccess ||
-      gc_buf_reserve(bpow, sizeof(double) * (size_t)(std::max(max_nm, 1) * cells), false) != hipSuccess) {
-    gc_set_error("%s: device allocation failed (%d blocks, %d runs, %d maps in a sub-batch, %d taps, %d bins)", fn, max_nb, max_nr, max_nm,
-                 ntaps, nfreq);
+  if (gc_buf_reserve(baux, sizeof(DdmBlockAux) * (size_t)z.nb, false) != hipSuccess ||
+      gc_buf_reserve(brot, sizeof(double2) * (size_t)z.nb * (size_t)nfreq, false) != hipSuccess ||
+      gc_buf_reserve(brun, sizeof(int32_t) * (size_t)(z.nr + 1), false) != hipSuccess ||
+      gc_buf_reserve(bcoh, sizeof(double2) * (size_t)(z.nr * cells), false) != hipSuccess ||
+      gc_buf_reserve(bmap, sizeof(int32_t) * (size_t)(z.nm + 1), false) != hipSuccess ||
+      gc_buf_reserve(bpow, sizeof(double) * (size_t)(std::max(z.nm, 1) * cells), false) != hipSuccess) {
+    gc_set_error("%s: device allocation failed (%d blocks, %d runs, %d maps in a sub-batch, %d taps, %d bins)", fn, z.nb, z.nr, z.nm, ntaps,
+                 nfreq);
     return GC_E_NOMEM;
   }
-  std::vector<DdmBlockAux> aux;
+  DdmLaunch l;
   std::vector<double> compact;
-  for (DdmStep s; s.first + s.nb < nblocks;) {
-    ddm_next_step(s, blocks, nblocks, max_chunks, run_start, map_start, base);
+  for (DdmStep s; ddm_next_step(s, blocks, nblocks, max_chunks, part);) {
     BankArgs a;
-    if ((rc = bank_chunks(fn, ctx, blocks + s.first, s.nb, base, ntaps, nfreq, true, arms, &a))) return rc;
-    const int end = s.first + s.nb;
-    aux.resize((size_t)s.nb);
-    index.resize((size_t)s.nr + 1);
-    for (int k = 0; k < s.nr; ++k) {
-      const int b0 = run_start[s.r0 + k], lo = std::max(b0, s.first), hi = std::min(run_start[s.r0 + k + 1], end);
-      index[k] = lo - s.first;
-      index[k + 1] = hi - s.first;
-      for (int b = lo; b < hi; ++b) aux[b - s.first] = DdmBlockAux{blocks[b].first_sample - blocks[b0].first_sample, weights ? weights[b] : 1.0};
-    }
-    GC_HIP(hipMemcpyAsync(baux.p, aux.data(), sizeof(DdmBlockAux) * aux.size(), hipMemcpyHostToDevice, ctx->stream));
-    GC_HIP(hipMemcpyAsync(brun.p, index.data(), sizeof(int32_t) * index.size(), hipMemcpyHostToDevice, ctx->stream));
-    DdmArgs d;
-    d.blocks = a.blocks;
-    d.chans = a.chans;
-    d.chunk_base = a.chunk_base;
-    d.freqs = a.freqs;
-    d.aux = (const DdmBlockAux*)baux.p;
-    d.partial = (const double2*)a.partial;
-    d.rot = (double2*)brot.p;
-    d.run_base = (const int32_t*)brun.p;
-    d.coh = (double2*)bcoh.p;
-    d.map_base = (const int32_t*)bmap.p;
-    d.pow = (double*)bpow.p;
-    d.fs = ctx->fs;
-    d.nblocks = s.nb;
-    d.ntaps = ntaps;
-    d.nfreq = nfreq;
-    d.arms = arms;
-    d.nruns = s.nr;
-    d.nmaps = s.nm;
-    d.carry_run = run_start[s.r0] < s.first;
-    d.carry_map = s.nm > 0 && map_start[s.q0] < s.r0;
+    if ((rc = bank_chunks(fn, ctx, blocks + s.first, s.nb, s.chunk_base, ntaps, nfreq, true, arms, &a))) return rc;
+    ddm_plan_step(s, blocks, weights, part, l);
+    GC_HIP(hipMemcpyAsync(baux.p, l.aux.data(), sizeof(DdmBlockAux) * l.aux.size(), hipMemcpyHostToDevice, ctx->stream));
+    GC_HIP(hipMemcpyAsync(brun.p, l.run_base.data(), sizeof(int32_t) * l.run_base.size(), hipMemcpyHostToDevice, ctx->stream));
+    const DdmArgs d = ddm_args(ctx, a, s, l);
     hipLaunchKernelGGL(ddm_rotation_kernel, dim3((unsigned int)(((long long)s.nb * nfreq + 255) / 256)), dim3(256), 0, ctx->stream, d);
     GC_HIP(hipGetLastError());
     hipLaunchKernelGGL(ddm_integrate_kernel, dim3((unsigned int)((s.nr * cells + 255) / 256)), dim3(256), 0, ctx->stream, d);
     GC_HIP(hipGetLastError());
     if (s.nm > 0) {
-      mindex.resize((size_t)s.nm + 1);
-      for (int k = 0; k <= s.nm; ++k) mindex[k] = std::min(std::max(map_start[s.q0 + k] - s.r0, 0), s.nfin);
-      GC_HIP(hipMemcpyAsync(bmap.p, mindex.data(), sizeof(int32_t) * mindex.size(), hipMemcpyHostToDevice, ctx->stream));
+      GC_HIP(hipMemcpyAsync(bmap.p, l.map_base.data(), sizeof(int32_t) * l.map_base.size(), hipMemcpyHostToDevice, ctx->stream));
       hipLaunchKernelGGL(ddm_power_kernel, dim3((unsigned int)((s.nm * cells + 255) / 256)), dim3(256), 0, ctx->stream, d);
       GC_HIP(hipGetLastError());
       if (s.mfin > 0 && (rc = bank_fetch(ctx, pow + (size_t)s.q0 * full, bpow.p, s.mfin, cells, full, compact))) return rc;
-      if (s.mfin < s.nm && s.nm > 1)  // the map that goes on: to the front
-        GC_HIP(hipMemcpyAsync(bpow.p, (const double*)bpow.p + (size_t)(s.nm - 1) * cells, sizeof(double) * (size_t)cells, hipMemcpyDeviceToDevice,
+      if (l.keep_map)  // the map that goes on: to the front
+        GC_HIP(hipMemcpyAsync(bpow.p, (const double*)bpow.p + (size_t)l.keep_map * cells, sizeof(double) * (size_t)cells, hipMemcpyDeviceToDevice,
                               ctx->stream));
     }
     if (coh && s.nfin > 0 && (rc = bank_fetch(ctx, coh + (size_t)s.r0 * 2 * full, bcoh.p, s.nfin, 2 * cells, 2 * full, compact))) return rc;
-    if (s.nfin < s.nr && s.nr > 1)  // the run that goes on: to the front
-      GC_HIP(hipMemcpyAsync(bcoh.p, (const double2*)bcoh.p + (size_t)(s.nr - 1) * cells, sizeof(double2) * (size_t)cells, hipMemcpyDeviceToDevice,
+    if (l.keep_run)  // the run that goes on: to the front
+      GC_HIP(hipMemcpyAsync(bcoh.p, (const double2*)bcoh.p + (size_t)l.keep_run * cells, sizeof(double2) * (size_t)cells, hipMemcpyDeviceToDevice,
                             ctx->stream));
     GC_HIP(hipStreamSynchronize(ctx->stream));
   }
@@ -819,15 +604,6 @@ int ddm_integrate_run(const char* fn, gc_context* ctx, int nblocks, const gc_blo
 // blocks with its open run (re, im) and open map (p) in registers: ddm_integrate_kernel's and ddm_power_kernel's additions in their
 // order.  The two accumulators are kept per (hypothesis, cell) between tiles and sub-batches, so a cut never shows; a finished run
 // goes into its map at once and is stored only when the caller asked for coh.  search_peak_kernel reduces every finished plane.
-
-enum { SRCH_IN = 1, SRCH_RUN_START = 2, SRCH_RUN_END = 4, SRCH_MAP_START = 8, SRCH_MAP_END = 16 };
-
-struct SearchAux {
-  long long dn;   // first_sample - first_sample of the first block of the run this block belongs to in the hypothesis
-  double w;       // the block's weight in the hypothesis
-  int32_t flags;  // SRCH_*; 0: the block is outside the hypothesis's window
-  int32_t pad_;
-};
 
 struct SearchArgs {
   const gc_block* blocks;  // the sub-batch's
@@ -847,8 +623,6 @@ struct SearchArgs {
   int ntaps, nfreq, arms, nhyp, nslot_r, nslot_m;
 };
 
-constexpr long long kSearchTileBytes = 128LL << 20;  // per-(hypothesis, block) scratch and finished runs / maps of one tile at most
-
 __global__ void search_rotation_kernel(const SearchArgs p) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)p.nhyp * p.nt * p.nfreq) return;
@@ -856,11 +630,7 @@ __global__ void search_rotation_kernel(const SearchArgs p) {
   const int m = (int)(i - hk * p.nfreq);
   const SearchAux a = p.aux[hk];
   if (!(a.flags & SRCH_IN)) return;
-  const double x = __dmul_rn(p.freqs[m], (double)a.dn) / p.fs;
-  const double u = x - rint(x);
-  double s, c;
-  sincospi(2.0 * u, &s, &c);
-  p.rot[i] = make_double2(c, s);
+  p.rot[i] = ddm_phasor(p.freqs[m], a.dn, p.fs);
 }
 
 __global__ __launch_bounds__(256) void search_integrate_kernel(const SearchArgs p) {
@@ -944,228 +714,130 @@ __global__ __launch_bounds__(256) void search_peak_kernel(const SearchArgs p) {
   }
 }
 
-// Blocks per tile: what one block can cost in every hypothesis at once - its SearchAux, its rotations, and (at most one run and one
-// map end with a block) a finished run if coh is asked for, a finished map with its peaks if maps are - within kSearchTileBytes.
-// At the limits (128 hypotheses, 3 arms x 64 bins x 64 taps, coh and maps) a block costs 37.9 MB: one block always fits.
-int search_tile_blocks(int nhyp, int nfreq, long long cells, int arms, bool want_coh, bool want_maps) {
-  const long long per_block = (long long)nhyp * ((long long)sizeof(SearchAux) + 16LL * nfreq + (want_coh ? 16 * cells : 0) +
-                                                 (want_maps ? 8 * cells + (long long)sizeof(gc_ddm_peak) * arms : 0));
-  return (int)std::max<long long>(1, std::min<long long>(kSearchTileBytes / per_block, 1 << 20));
+// What a tile's finished runs, maps and peaks pass through on the host.
+struct SearchStage {
+  std::vector<double> coh, pow;
+  std::vector<gc_ddm_peak> peaks;
+};
+
+// The kernel arguments of the tile [t0, t0 + nt) of a sub-batch (bank_plan.h: SearchWalk) from those bank_cells returned.
+SearchArgs search_args(gc_context* ctx, const BankArgs& a, const SearchWalk& w, int t0, int nt, int nhyp, bool out_coh, bool out_maps) {
+  SearchArgs s;
+  s.blocks = a.blocks;
+  s.chans = a.chans;
+  s.freqs = a.freqs;
+  s.aux = (const SearchAux*)ctx->bank[gc_context::BANK_AUX].p;
+  s.cell = (const double2*)a.out;
+  s.rot = (double2*)ctx->bank[gc_context::BANK_ROT].p;
+  s.racc = (double2*)ctx->bank[gc_context::BANK_RACC].p;
+  s.macc = (double*)ctx->bank[gc_context::BANK_MACC].p;
+  s.coh = out_coh ? (double2*)ctx->bank[gc_context::BANK_COH].p : nullptr;
+  s.pow = out_maps ? (double*)ctx->bank[gc_context::BANK_POW].p : nullptr;
+  s.maps_done = (const int32_t*)ctx->bank[gc_context::BANK_RUNS].p;
+  s.peaks = (gc_ddm_peak*)ctx->bank[gc_context::BANK_PEAKS].p;
+  s.fs = a.fs;
+  s.t0 = t0;
+  s.nt = nt;
+  s.ntaps = a.ntaps;
+  s.nfreq = a.nfreq;
+  s.arms = a.arms;
+  s.nhyp = nhyp;
+  s.nslot_r = w.nslot_r;
+  s.nslot_m = w.nslot_m;
+  return s;
 }
 
-int ddm_search_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* blocks, int nhyp, const int32_t* block_shift,
-                   const double* weights, int ntaps, const double* tap_offsets, int nfreq, const double* freq_offsets, int nruns,
-                   const int32_t* run_len, int nmaps, const int32_t* map_len, double* coh, double* pow, gc_ddm_peak* peaks) {
-  if (nhyp < 1 || nhyp > GC_DDM_MAX_HYP) {
-    gc_set_error("%s: %d hypotheses (1 .. %d)", fn, nhyp, GC_DDM_MAX_HYP);
-    return GC_E_INVALID;
-  }
-  int arms = 1;
-  int rc = bank_check(fn, ctx, nblocks, blocks, ntaps, tap_offsets, nfreq, freq_offsets, &arms);
-  if (rc) return rc;
-  if (nmaps < 0 || (nblocks > 0 && nruns < 1)) {
-    gc_set_error("%s: %d runs, %d maps for %d blocks", fn, nruns, nmaps, nblocks);
-    return GC_E_INVALID;
-  }
-  std::vector<int> run_start(1, 0), map_start(1, 0);  // blocks of the window before run r, runs before map q
-  for (int r = 0; r < nruns; ++r) {
-    if (run_len[r] < 1 || run_len[r] > nblocks - run_start.back()) {
-      gc_set_error("%s: run %d has %d blocks (1 at least, %d in all)", fn, r, (int)run_len[r], nblocks);
-      return GC_E_INVALID;
-    }
-    run_start.push_back(run_start.back() + run_len[r]);
-  }
-  const int nused = run_start.back();
-  for (int q = 0; q < nmaps; ++q) {
-    if (map_len[q] < 1 || map_len[q] > nruns - map_start.back()) {
-      gc_set_error("%s: map %d has %d runs (1 at least, %d in all)", fn, q, (int)map_len[q], nruns);
-      return GC_E_INVALID;
-    }
-    map_start.push_back(map_start.back() + map_len[q]);
-  }
-  if (nmaps > 0 && map_start.back() != nruns) {
-    gc_set_error("%s: the maps hold %d runs of %d", fn, map_start.back(), nruns);
-    return GC_E_INVALID;
-  }
-  std::vector<int> shift((size_t)nhyp, 0);
-  for (int h = 0; h < nhyp; ++h) {
-    if (block_shift) shift[h] = block_shift[h];
-    if (shift[h] < 0 || shift[h] > nblocks - nused) {
-      gc_set_error("%s: hypothesis %d looks at blocks %d .. %lld of %d", fn, h, shift[h], (long long)shift[h] + nused - 1, nblocks);
-      return GC_E_INVALID;
-    }
-  }
-  for (int h = 0; h < nhyp; ++h)
-    for (int r = 0; r < nruns; ++r) {
-      const int b0 = shift[h] + run_start[r];
-      for (int b = b0 + 1; b < shift[h] + run_start[r + 1]; ++b)
-        if (blocks[b].channel != blocks[b0].channel) {
-          gc_set_error("%s: run %d of hypothesis %d has blocks of channels %d and %d", fn, r, h, blocks[b0].channel, blocks[b].channel);
-          return GC_E_INVALID;
-        }
-    }
-  if (weights)
-    for (long long i = 0; i < (long long)nhyp * nblocks; ++i)
-      if (!std::isfinite(weights[i])) {
-        gc_set_error("%s: the weight of block %d in hypothesis %d is not finite", fn, (int)(i % nblocks), (int)(i / nblocks));
-        return GC_E_INVALID;
-      }
-  if (!coh && !pow && !peaks) {
-    gc_set_error("%s: no output asked for", fn);
-    return GC_E_INVALID;
-  }
-  if ((pow || peaks) && nmaps == 0) {
-    gc_set_error("%s: power maps or peaks asked for without a map", fn);
-    return GC_E_INVALID;
-  }
-  if (nblocks == 0) return GC_OK;
-  if ((rc = bank_upload_grids(fn, ctx, ntaps, tap_offsets, nfreq, freq_offsets))) return rc;
-  const bool want_maps = pow || peaks;
+// One planned tile: its SearchAux to the device, the kernels, and the runs and maps that end in it back to their rows of the caller's.
+int search_run_tile(const char* fn, gc_context* ctx, const BankArgs& a, const SearchWalk& w, int t0, int nt, int nhyp, int nruns, int nmaps,
+                    double* coh, double* pow, gc_ddm_peak* peaks, SearchStage& st) {
+  const int arms = a.arms, nfreq = a.nfreq, ntaps = a.ntaps, nslot_r = w.nslot_r, nslot_m = w.nslot_m;
   const long long cells = (long long)arms * nfreq * ntaps, full = (long long)GC_MAX_ARMS * nfreq * ntaps;
-  const long long max_chunks = bank_max_chunks(2 * cells);
-  const int tile = search_tile_blocks(nhyp, nfreq, cells, arms, coh != nullptr, want_maps);
-  // per position of the window: its run, and where runs and maps begin and end
-  std::vector<int> run_of((size_t)nused), pos_flags((size_t)nused, SRCH_IN);
-  for (int r = 0; r < nruns; ++r) {
-    for (int k = run_start[r]; k < run_start[r + 1]; ++k) run_of[k] = r;
-    pos_flags[run_start[r]] |= SRCH_RUN_START;
-    pos_flags[run_start[r + 1] - 1] |= SRCH_RUN_END;
-  }
-  if (want_maps)  // without an output for them the open map is never stored: no flags, nothing kept
-    for (int q = 0; q < nmaps; ++q) {
-      pos_flags[run_start[map_start[q]]] |= SRCH_MAP_START;
-      pos_flags[run_start[map_start[q + 1]] - 1] |= SRCH_MAP_END;
-    }
-  GcBuf& bout = ctx->bank[gc_context::BANK_OUT];
+  const bool out_coh = coh && nslot_r > 0, out_maps = nslot_m > 0;
   GcBuf& baux = ctx->bank[gc_context::BANK_AUX];
-  GcBuf& brot = ctx->bank[gc_context::BANK_ROT];
   GcBuf& bdone = ctx->bank[gc_context::BANK_RUNS];
   GcBuf& bcoh = ctx->bank[gc_context::BANK_COH];
   GcBuf& bpow = ctx->bank[gc_context::BANK_POW];
+  GcBuf& bpeak = ctx->bank[gc_context::BANK_PEAKS];
+  if (gc_buf_reserve(baux, sizeof(SearchAux) * w.aux.size(), false) != hipSuccess ||
+      gc_buf_reserve(ctx->bank[gc_context::BANK_ROT], sizeof(double2) * w.aux.size() * (size_t)nfreq, false) != hipSuccess ||
+      (out_coh && gc_buf_reserve(bcoh, sizeof(double2) * (size_t)((long long)nhyp * nslot_r * cells), false) != hipSuccess) ||
+      (out_maps && (gc_buf_reserve(bpow, sizeof(double) * (size_t)((long long)nhyp * nslot_m * cells), false) != hipSuccess ||
+                    gc_buf_reserve(bpeak, sizeof(gc_ddm_peak) * (size_t)((long long)nhyp * nslot_m * arms), false) != hipSuccess))) {
+    gc_set_error("%s: device allocation failed (%d hypotheses, %d blocks in a tile, %d taps, %d bins)", fn, nhyp, nt, ntaps, nfreq);
+    return GC_E_NOMEM;
+  }
+  GC_HIP(hipMemcpyAsync(baux.p, w.aux.data(), sizeof(SearchAux) * w.aux.size(), hipMemcpyHostToDevice, ctx->stream));
+  const SearchArgs s = search_args(ctx, a, w, t0, nt, nhyp, out_coh, out_maps);
+  hipLaunchKernelGGL(search_rotation_kernel, dim3((unsigned int)((w.aux.size() * (size_t)nfreq + 255) / 256)), dim3(256), 0, ctx->stream, s);
+  GC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(search_integrate_kernel, dim3((unsigned int)((cells + 255) / 256), (unsigned int)nhyp), dim3(256), 0, ctx->stream, s);
+  GC_HIP(hipGetLastError());
+  if (out_maps && peaks) {
+    GC_HIP(hipMemcpyAsync(bdone.p, w.maps_now.data(), sizeof(int32_t) * (size_t)nhyp, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(search_peak_kernel, dim3((unsigned int)(nslot_m * arms), (unsigned int)nhyp), dim3(256), 0, ctx->stream, s);
+    GC_HIP(hipGetLastError());
+    st.peaks.resize((size_t)nhyp * nslot_m * arms);
+    GC_HIP(hipMemcpyAsync(st.peaks.data(), bpeak.p, sizeof(gc_ddm_peak) * st.peaks.size(), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (out_coh) {
+    st.coh.resize((size_t)((long long)nhyp * nslot_r * cells * 2));
+    GC_HIP(hipMemcpyAsync(st.coh.data(), bcoh.p, sizeof(double) * st.coh.size(), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (out_maps && pow) {
+    st.pow.resize((size_t)((long long)nhyp * nslot_m * cells));
+    GC_HIP(hipMemcpyAsync(st.pow.data(), bpow.p, sizeof(double) * st.pow.size(), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  GC_HIP(hipStreamSynchronize(ctx->stream));
+  for (int h = 0; h < nhyp; ++h) {  // slot k of hypothesis h is its run runs_done[h] + k, its map maps_done[h] + k
+    const size_t r = (size_t)h * nruns + w.runs_done[h], q = (size_t)h * nmaps + w.maps_done[h];
+    if (out_coh) bank_spread(coh + r * (size_t)(2 * full), st.coh.data() + (size_t)h * nslot_r * (2 * cells), w.runs_now[h], 2 * cells, 2 * full);
+    if (out_maps && pow) bank_spread(pow + q * (size_t)full, st.pow.data() + (size_t)h * nslot_m * cells, w.maps_now[h], cells, full);
+    if (out_maps && peaks) bank_spread(peaks + q * GC_MAX_ARMS, st.peaks.data() + (size_t)h * nslot_m * arms, w.maps_now[h], arms, GC_MAX_ARMS);
+  }
+  return GC_OK;
+}
+
+// Check, plan (bank_plan.h), then per sub-batch the blocks' cells once and per tile of its blocks upload, launch, fetch.
+int ddm_search_run(const char* fn, gc_context* ctx, int nblocks, const gc_block* blocks, int nhyp, const int32_t* block_shift,
+                   const double* weights, int ntaps, const double* tap_offsets, int nfreq, const double* freq_offsets, int nruns,
+                   const int32_t* run_len, int nmaps, const int32_t* map_len, double* coh, double* pow, gc_ddm_peak* peaks) {
+  int arms = 1;
+  BankPartition part;
+  std::vector<int> shift;
+  int rc = ddm_search_check(fn, ctx, nblocks, blocks, nhyp, block_shift, weights, ntaps, tap_offsets, nfreq, freq_offsets, nruns, run_len, nmaps,
+                            map_len, coh != nullptr, pow != nullptr, peaks != nullptr, &arms, &part, &shift);
+  if (rc) return rc;
+  if (nblocks == 0) return GC_OK;
+  if ((rc = bank_upload_grids(fn, ctx, ntaps, tap_offsets, nfreq, freq_offsets))) return rc;
+  const bool want_maps = pow || peaks;
+  const long long cells = (long long)arms * nfreq * ntaps;
+  const BankBudget budget;
+  const long long max_chunks = bank_max_chunks(2 * cells, budget);
+  const int tile = search_tile_blocks(nhyp, nfreq, cells, arms, coh != nullptr, want_maps, budget);
   GcBuf& bracc = ctx->bank[gc_context::BANK_RACC];
   GcBuf& bmacc = ctx->bank[gc_context::BANK_MACC];
-  GcBuf& bpeak = ctx->bank[gc_context::BANK_PEAKS];
   // the accumulators a cut run or map goes on from: reserved once, before the walk
   if (gc_buf_reserve(bracc, sizeof(double2) * (size_t)(nhyp * cells), false) != hipSuccess ||
       gc_buf_reserve(bmacc, sizeof(double) * (size_t)(nhyp * cells), false) != hipSuccess ||
-      gc_buf_reserve(bdone, sizeof(int32_t) * (size_t)nhyp, false) != hipSuccess) {
+      gc_buf_reserve(ctx->bank[gc_context::BANK_RUNS], sizeof(int32_t) * (size_t)nhyp, false) != hipSuccess) {
     gc_set_error("%s: device allocation failed (%d hypotheses, %d taps, %d bins)", fn, nhyp, ntaps, nfreq);
     return GC_E_NOMEM;
   }
   GC_HIP(hipMemsetAsync(bracc.p, 0, sizeof(double2) * (size_t)(nhyp * cells), ctx->stream));
   GC_HIP(hipMemsetAsync(bmacc.p, 0, sizeof(double) * (size_t)(nhyp * cells), ctx->stream));
-  std::vector<int32_t> base, runs_now((size_t)nhyp), maps_now((size_t)nhyp);
-  std::vector<int> runs_done((size_t)nhyp, 0), maps_done((size_t)nhyp, 0);  // finished so far, per hypothesis
-  std::vector<SearchAux> aux;
-  std::vector<double> hcoh, hpow;
-  std::vector<gc_ddm_peak> hpeak;
-  for (int first = 0; first < nblocks;) {
-    const int nb = bank_cut(blocks, nblocks, first, max_chunks, base);
-    if (gc_buf_reserve(bout, sizeof(double2) * (size_t)(nb * cells), false) != hipSuccess)
-      return bank_nomem(fn, true, nb, base.back(), ntaps, nfreq);
+  SearchWalk w;
+  search_walk_begin(w, part, nhyp, want_maps);
+  SearchStage st;
+  std::vector<int32_t> base;
+  for (int first = 0, nb; first < nblocks; first += nb) {
+    nb = bank_cut(blocks, nblocks, first, max_chunks, base);
     BankArgs a;
-    if ((rc = bank_chunks(fn, ctx, blocks + first, nb, base, ntaps, nfreq, true, arms, &a))) return rc;
-    a.out = (double*)bout.p;
-    hipLaunchKernelGGL(bank_combine_kernel, dim3((unsigned int)((nb * 2 * cells + 255) / 256)), dim3(256), 0, ctx->stream, a);
-    GC_HIP(hipGetLastError());
+    if ((rc = bank_cells(fn, ctx, blocks + first, nb, base, ntaps, nfreq, true, arms, &a))) return rc;
     for (int t0 = 0; t0 < nb; t0 += tile) {
       const int nt = std::min(tile, nb - t0);
-      aux.assign((size_t)nhyp * nt, SearchAux{0, 0.0, 0, 0});
-      int nslot_r = 0, nslot_m = 0;
-      bool any = false;
-      for (int h = 0; h < nhyp; ++h) {
-        runs_now[h] = maps_now[h] = 0;
-        const int lo = std::max(first + t0, shift[h]), hi = std::min(first + t0 + nt, shift[h] + nused);
-        for (int b = lo; b < hi; ++b) {
-          const int k = b - shift[h];
-          const int f = pos_flags[k];
-          aux[(size_t)h * nt + (b - first - t0)] =
-              SearchAux{blocks[b].first_sample - blocks[shift[h] + run_start[run_of[k]]].first_sample,
-                        weights ? weights[(size_t)h * nblocks + b] : 1.0, f, 0};
-          runs_now[h] += (f & SRCH_RUN_END) != 0;
-          maps_now[h] += (f & SRCH_MAP_END) != 0;
-          any = true;
-        }
-        nslot_r = std::max(nslot_r, (int)runs_now[h]);
-        nslot_m = std::max(nslot_m, (int)maps_now[h]);
-      }
-      if (!any) continue;  // a tile no hypothesis looks at
-      const bool out_coh = coh && nslot_r > 0, out_maps = nslot_m > 0;
-      if (gc_buf_reserve(baux, sizeof(SearchAux) * aux.size(), false) != hipSuccess ||
-          gc_buf_reserve(brot, sizeof(double2) * aux.size() * (size_t)nfreq, false) != hipSuccess ||
-          (out_coh && gc_buf_reserve(bcoh, sizeof(double2) * (size_t)((long long)nhyp * nslot_r * cells), false) != hipSuccess) ||
-          (out_maps && (gc_buf_reserve(bpow, sizeof(double) * (size_t)((long long)nhyp * nslot_m * cells), false) != hipSuccess ||
-                        gc_buf_reserve(bpeak, sizeof(gc_ddm_peak) * (size_t)((long long)nhyp * nslot_m * arms), false) != hipSuccess))) {
-        gc_set_error("%s: device allocation failed (%d hypotheses, %d blocks in a tile, %d taps, %d bins)", fn, nhyp, nt, ntaps, nfreq);
-        return GC_E_NOMEM;
-      }
-      GC_HIP(hipMemcpyAsync(baux.p, aux.data(), sizeof(SearchAux) * aux.size(), hipMemcpyHostToDevice, ctx->stream));
-      SearchArgs s;
-      s.blocks = a.blocks;
-      s.chans = a.chans;
-      s.freqs = a.freqs;
-      s.aux = (const SearchAux*)baux.p;
-      s.cell = (const double2*)bout.p;
-      s.rot = (double2*)brot.p;
-      s.racc = (double2*)bracc.p;
-      s.macc = (double*)bmacc.p;
-      s.coh = out_coh ? (double2*)bcoh.p : nullptr;
-      s.pow = out_maps ? (double*)bpow.p : nullptr;
-      s.maps_done = (const int32_t*)bdone.p;
-      s.peaks = (gc_ddm_peak*)bpeak.p;
-      s.fs = ctx->fs;
-      s.t0 = t0;
-      s.nt = nt;
-      s.ntaps = ntaps;
-      s.nfreq = nfreq;
-      s.arms = arms;
-      s.nhyp = nhyp;
-      s.nslot_r = nslot_r;
-      s.nslot_m = nslot_m;
-      hipLaunchKernelGGL(search_rotation_kernel, dim3((unsigned int)((aux.size() * (size_t)nfreq + 255) / 256)), dim3(256), 0, ctx->stream, s);
-      GC_HIP(hipGetLastError());
-      hipLaunchKernelGGL(search_integrate_kernel, dim3((unsigned int)((cells + 255) / 256), (unsigned int)nhyp), dim3(256), 0, ctx->stream, s);
-      GC_HIP(hipGetLastError());
-      if (out_maps && peaks) {
-        GC_HIP(hipMemcpyAsync(bdone.p, maps_now.data(), sizeof(int32_t) * (size_t)nhyp, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(search_peak_kernel, dim3((unsigned int)(nslot_m * arms), (unsigned int)nhyp), dim3(256), 0, ctx->stream, s);
-        GC_HIP(hipGetLastError());
-        hpeak.resize((size_t)nhyp * nslot_m * arms);
-        GC_HIP(hipMemcpyAsync(hpeak.data(), bpeak.p, sizeof(gc_ddm_peak) * hpeak.size(), hipMemcpyDeviceToHost, ctx->stream));
-      }
-      if (out_coh) {
-        hcoh.resize((size_t)((long long)nhyp * nslot_r * cells * 2));
-        GC_HIP(hipMemcpyAsync(hcoh.data(), bcoh.p, sizeof(double) * hcoh.size(), hipMemcpyDeviceToHost, ctx->stream));
-      }
-      if (out_maps && pow) {
-        hpow.resize((size_t)((long long)nhyp * nslot_m * cells));
-        GC_HIP(hipMemcpyAsync(hpow.data(), bpow.p, sizeof(double) * hpow.size(), hipMemcpyDeviceToHost, ctx->stream));
-      }
-      GC_HIP(hipStreamSynchronize(ctx->stream));
-      // the device rows hold the call's arms only: the others are zero on the host's side
-      for (int h = 0; h < nhyp; ++h) {
-        if (out_coh)
-          for (int k = 0; k < runs_now[h]; ++k) {
-            double* o = coh + ((size_t)h * nruns + runs_done[h] + k) * (size_t)(2 * full);
-            std::memcpy(o, hcoh.data() + ((size_t)h * nslot_r + k) * (size_t)(2 * cells), sizeof(double) * (size_t)(2 * cells));
-            std::memset(o + 2 * cells, 0, sizeof(double) * (size_t)(2 * (full - cells)));
-          }
-        for (int k = 0; k < maps_now[h]; ++k) {
-          const size_t q = (size_t)h * nmaps + maps_done[h] + k;
-          if (pow) {
-            double* o = pow + q * (size_t)full;
-            std::memcpy(o, hpow.data() + ((size_t)h * nslot_m + k) * (size_t)cells, sizeof(double) * (size_t)cells);
-            std::memset(o + cells, 0, sizeof(double) * (size_t)(full - cells));
-          }
-          if (peaks)
-            for (int arm = 0; arm < GC_MAX_ARMS; ++arm)
-              peaks[q * GC_MAX_ARMS + arm] = arm < arms ? hpeak[((size_t)h * nslot_m + k) * arms + arm] : gc_ddm_peak{0.0, 0, 0};
-        }
-        runs_done[h] += runs_now[h];
-        maps_done[h] += maps_now[h];
-      }
+      if (!search_plan_tile(w, blocks, nblocks, weights, part, shift, first + t0, nt)) continue;  // a tile no hypothesis looks at
+      if ((rc = search_run_tile(fn, ctx, a, w, t0, nt, nhyp, nruns, nmaps, coh, pow, peaks, st))) return rc;
     }
-    first += nb;
   }
   return GC_OK;
 }

@@ -202,8 +202,10 @@ struct gc_context {
          BANK_AUX, BANK_ROT, BANK_RUNS, BANK_COH, BANK_MAPS, BANK_POW, BANK_RACC, BANK_MACC, BANK_PEAKS, BANK_NBUF };
   // gc_correlate_bank, gc_correlate_ddm: descriptors, tap offsets, chunk index, per-chunk partial sums, results, frequency offsets;
   // gc_correlate_ddm_integrate: per-block sample distance and weight, per-(block, bin) rotations, run index, coherent sums, map index, power maps;
-  // gc_correlate_ddm_search: the same slots per (hypothesis, block) of a tile (BANK_OUT: the blocks' cells, BANK_RUNS: the shifts,
-  // BANK_COH / BANK_POW: finished runs and maps on their way out), every hypothesis's open run and open map, the picked peaks
+  // gc_correlate_ddm_search: the same slots per (hypothesis, block) of a tile (BANK_OUT: the blocks' cells, BANK_RUNS: the maps that
+  // end in the tile per hypothesis, BANK_COH / BANK_POW: finished runs and maps on their way out), every hypothesis's open run and
+  // open map, the picked peaks.  What goes into the index and aux slots, and how large a sub-batch or a tile makes them, is decided
+  // in bank_plan.h (BankBudget, DdmStep / DdmLaunch, SearchWalk); corr_bank.hip reserves, uploads and launches.
   GcBuf bank[BANK_NBUF];
   double* cno_out = nullptr;  // gc_set_cno_output: caller-owned C/N0 buffer of the next tracking calls
   long long cno_cap = 0;

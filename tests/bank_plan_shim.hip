@@ -1,0 +1,177 @@
+// The host plan of the tap bank family (csrc/bank_plan.h) on the CPU: a context that holds channel FACTS only (arms, table length,
+// window, whether the pads are the period - no device memory) for the argument checks, and the sub-batch cut, the integrate walk and
+// the search walk over a descriptor list under budgets the caller chooses, written out as plain integers.  Built by
+// tests/test_bank_plan_cpu.py with the flags of corr_bank.hip; no GPU is touched.
+#include <cstdarg>
+
+#include "../cu-sdr-collection_amd/csrc/bank_plan.h"
+
+void gc_set_error(const char*, ...) {}
+
+namespace {
+struct Out {  // what does not fit is counted, not written: the caller compares the count with its capacity
+  long long* p;
+  long long cap, n;
+  void put(long long v) {
+    if (n < cap) p[n] = v;
+    ++n;
+  }
+};
+BankBudget budget_of(long long partial_bytes, long long tile_bytes) {  // 0: the library's
+  BankBudget b;
+  if (partial_bytes > 0) b.partial_bytes = partial_bytes;
+  if (tile_bytes > 0) b.tile_bytes = tile_bytes;
+  return b;
+}
+}  // namespace
+
+extern "C" {
+
+void* bank_shim_create(int have_record, unsigned long long if_nsamples, double fs) {
+  static uint8_t no_record;
+  gc_context* ctx = new gc_context();
+  ctx->precision = GC_PREC_F32;
+  ctx->d_if = have_record ? &no_record : nullptr;  // never read
+  ctx->if_nsamples = if_nsamples;
+  ctx->fs = fs;
+  return ctx;
+}
+
+void bank_shim_destroy(void* ctx) { delete static_cast<gc_context*>(ctx); }
+
+void bank_shim_set_double(void* ctx, int on) { static_cast<gc_context*>(ctx)->precision = on ? GC_PREC_F64 : GC_PREC_F32; }
+
+// arms tables of nent entries (pads included), ramp multiplier 1, index scale 1; broken_pad: the first pad is not the period's last entry
+void bank_shim_set_channel(void* vctx, int channel, int arms, int nent, int window, int broken_pad) {
+  static int8_t no_table;
+  HostChannel& c = static_cast<gc_context*>(vctx)->ch[channel];
+  c = HostChannel();
+  c.configured = true;
+  c.arms = arms;
+  c.index_scale = 1.0;
+  for (int a = 0; a < arms; ++a) {
+    c.nent[a] = nent;
+    c.mult[a] = 1.0;
+    c.window[a] = window;
+    c.d_tab[a] = &no_table;  // never read
+    c.h_tab[a].assign((size_t)nent, (int8_t)1);
+    if (broken_pad) c.h_tab[a][0] = -1;
+  }
+}
+
+// gc_correlate_bank (freqs == nullptr) and gc_correlate_ddm up to the first device call
+int bank_shim_check(void* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* taps, int nfreq, const double* freqs) {
+  int arms = 1;
+  return bank_check("shim", static_cast<const gc_context*>(ctx), nblocks, blocks, ntaps, taps, nfreq, freqs, &arms);
+}
+
+int bank_shim_check_integrate(void* ctx, int nblocks, const gc_block* blocks, const double* weights, int ntaps, const double* taps, int nfreq,
+                              const double* freqs, int nruns, const int32_t* run_len, int nmaps, const int32_t* map_len, int want_coh,
+                              int want_pow) {
+  int arms = 1;
+  BankPartition p;
+  return ddm_integrate_check("shim", static_cast<const gc_context*>(ctx), nblocks, blocks, weights, ntaps, taps, nfreq, freqs, nruns, run_len,
+                             nmaps, map_len, want_coh != 0, want_pow != 0, &arms, &p);
+}
+
+int bank_shim_check_search(void* ctx, int nblocks, const gc_block* blocks, int nhyp, const int32_t* shifts, const double* weights, int ntaps,
+                           const double* taps, int nfreq, const double* freqs, int nruns, const int32_t* run_len, int nmaps,
+                           const int32_t* map_len, int want_coh, int want_pow, int want_peaks) {
+  int arms = 1;
+  BankPartition p;
+  std::vector<int> shift;
+  return ddm_search_check("shim", static_cast<const gc_context*>(ctx), nblocks, blocks, nhyp, shifts, weights, ntaps, taps, nfreq, freqs, nruns,
+                          run_len, nmaps, map_len, want_coh != 0, want_pow != 0, want_peaks != 0, &arms, &p, &shift);
+}
+
+int bank_shim_tile_blocks(int nhyp, int nfreq, long long cells, int arms, int want_coh, int want_maps, long long tile_bytes) {
+  return search_tile_blocks(nhyp, nfreq, cells, arms, want_coh != 0, want_maps != 0, budget_of(0, tile_bytes));
+}
+
+// bank_run's walk, `row` doubles per chunk: per sub-batch {first, blocks, chunks}.  Returns the integers written (or needed).
+long long bank_shim_cut(int nblocks, const gc_block* blocks, long long row, long long partial_bytes, long long* out, long long cap) {
+  Out o{out, cap, 0};
+  const long long max_chunks = bank_max_chunks(row, budget_of(partial_bytes, 0));
+  std::vector<int32_t> base;
+  for (int first = 0, nb; first < nblocks; first += nb) {
+    nb = bank_cut(blocks, nblocks, first, max_chunks, base);
+    o.put(first);
+    o.put(nb);
+    o.put(base.back());
+  }
+  return o.n;
+}
+
+// ddm_integrate_run's walk with `cells` cells per map: {the partition's status, the pre-walk's nb, nr, nm}, then per step
+// {first, nb, r0, nr, nfin, q0, nm, mfin, carry_run, carry_map, keep_run, keep_map, chunks, run_base[nr + 1], map_base[nm + 1 or
+// none], dn[nb]}; the blocks' weights in list order to wout[nblocks].
+long long bank_shim_integrate(int nblocks, const gc_block* blocks, const double* weights, int nruns, const int32_t* run_len, int nmaps,
+                              const int32_t* map_len, long long cells, long long partial_bytes, long long* out, long long cap, double* wout) {
+  Out o{out, cap, 0};
+  BankPartition p;
+  const int rc = bank_partition("shim", nblocks, nruns, run_len, nmaps, map_len, true, &p);
+  o.put(rc);
+  if (rc) return o.n;
+  const long long max_chunks = bank_max_chunks(2 * cells, budget_of(partial_bytes, 0));
+  const DdmSizes z = ddm_walk_sizes(blocks, nblocks, max_chunks, p);
+  o.put(z.nb);
+  o.put(z.nr);
+  o.put(z.nm);
+  DdmLaunch l;
+  for (DdmStep s; ddm_next_step(s, blocks, nblocks, max_chunks, p);) {
+    ddm_plan_step(s, blocks, weights, p, l);
+    for (int v : {s.first, s.nb, s.r0, s.nr, s.nfin, s.q0, s.nm, s.mfin, l.carry_run, l.carry_map, l.keep_run, l.keep_map, (int)s.chunk_base.back()})
+      o.put(v);
+    if ((int)l.run_base.size() != s.nr + 1 || (int)l.map_base.size() != (s.nm > 0 ? s.nm + 1 : 0) || (int)l.aux.size() != s.nb) return -1;
+    for (int v : l.run_base) o.put(v);
+    for (int v : l.map_base) o.put(v);
+    for (int k = 0; k < s.nb; ++k) {
+      o.put(l.aux[k].dn);
+      wout[s.first + k] = l.aux[k].w;
+    }
+  }
+  return o.n;
+}
+
+// ddm_search_run's walk (sub-batches of bank_cut, tiles of search_tile_blocks): {the partition's status, the tile size}, then per
+// tile {first block of the sub-batch, t0, nt, looked at, nslot_r, nslot_m, per hypothesis {runs_now, maps_now, runs_done, maps_done},
+// per (hypothesis, block of the tile) {dn, flags}}; the weights per (hypothesis, block) to wout[nhyp][nblocks].
+long long bank_shim_search(int nblocks, const gc_block* blocks, const double* weights, int nhyp, const int32_t* shifts, int nruns,
+                           const int32_t* run_len, int nmaps, const int32_t* map_len, int want_coh, int want_maps, int arms, int nfreq, int ntaps,
+                           long long partial_bytes, long long tile_bytes, long long* out, long long cap, double* wout) {
+  Out o{out, cap, 0};
+  BankPartition p;
+  const int rc = bank_partition("shim", nblocks, nruns, run_len, nmaps, map_len, false, &p);
+  o.put(rc);
+  if (rc) return o.n;
+  const std::vector<int> shift(shifts, shifts + nhyp);
+  const BankBudget budget = budget_of(partial_bytes, tile_bytes);
+  const long long cells = (long long)arms * nfreq * ntaps;
+  const long long max_chunks = bank_max_chunks(2 * cells, budget);
+  const int tile = search_tile_blocks(nhyp, nfreq, cells, arms, want_coh != 0, want_maps != 0, budget);
+  o.put(tile);
+  SearchWalk w;
+  search_walk_begin(w, p, nhyp, want_maps != 0);
+  std::vector<int32_t> base;
+  for (int first = 0, nb; first < nblocks; first += nb) {
+    nb = bank_cut(blocks, nblocks, first, max_chunks, base);
+    for (int t0 = 0; t0 < nb; t0 += tile) {
+      const int nt = std::min(tile, nb - t0);
+      const bool any = search_plan_tile(w, blocks, nblocks, weights, p, shift, first + t0, nt);
+      for (int v : {first, t0, nt, (int)any, w.nslot_r, w.nslot_m}) o.put(v);
+      for (int h = 0; h < nhyp; ++h)
+        for (int v : {(int)w.runs_now[h], (int)w.maps_now[h], w.runs_done[h], w.maps_done[h]}) o.put(v);
+      if ((long long)w.aux.size() != (long long)nhyp * nt) return -1;
+      for (int h = 0; h < nhyp; ++h)
+        for (int k = 0; k < nt; ++k) {
+          const SearchAux& a = w.aux[(size_t)h * nt + k];
+          o.put(a.dn);
+          o.put(a.flags);
+          wout[(size_t)h * nblocks + first + t0 + k] = a.w;
+        }
+    }
+  }
+  return o.n;
+}
+
+}  // extern "C"

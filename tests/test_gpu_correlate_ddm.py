@@ -20,7 +20,7 @@ from oracle import gnss_oracle as O
 pytestmark = pytest.mark.gpu
 TOL = 2e-6
 FREQ_POOL = [0.0, 0.37, -0.37, 250.0, -250.0, 500.0, -500.0, 1e3, -1e3, 1e4, -1e4, 4.5e6, -4.5e6]
-PARTIAL_BUDGET = 256 << 20     # the library's budget for one sub-batch's partial sums (csrc/corr_bank.hip kBankPartialBytes)
+PARTIAL_BUDGET = 256 << 20     # the library's budget for one sub-batch's partial sums (csrc/bank_plan.h BankBudget::partial_bytes)
 
 
 def _check(engine, rec, descs, offsets, freqs, tables, r=1.0, arm_mult=None, layout="IQ", label=""):

@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 TOL = 2e-6                     # the DDM tests' correlator-versus-definition figure, of sum |x| per block
 FREQ_POOL = [0.0, 0.37, -0.37, 250.0, -250.0, 500.0, -500.0, 1e3, -1e3, 1e4, -1e4, 4.5e6, -4.5e6]
 SIZES = (1, 2, 63, 64, 65, 1023, 1024, 1025, 2049, 4097)
-PARTIAL_BUDGET = 256 << 20     # the library's budget for one sub-batch's partial sums (csrc/corr_bank.hip kBankPartialBytes)
+PARTIAL_BUDGET = 256 << 20     # the library's budget for one sub-batch's partial sums (csrc/bank_plan.h BankBudget::partial_bytes)
 EPS = 2.0 ** -52
 
 
