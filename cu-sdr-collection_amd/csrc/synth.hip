@@ -233,11 +233,16 @@ __global__ __launch_bounds__(256) void synth2_kernel(void* __restrict__ out, con
 extern "C" int gs_version(void) { return 2; }
 
 // Fills d_out[0 .. 2*nsamples) (device pointer, 16-B aligned) on `device`.  `codes`: host array of
-// ncodes x code_len int8 (+-1).  Returns 0 or a negative hipError.
+// ncodes x code_len int8 (+-1).  Returns 0, -1 for arguments it refuses (nothing is written then: null or misaligned
+// pointers, more than 64 satellites, code_len / bit_periods / ncodes < 1, a code_index outside `codes`), or -2 .. -5 for a
+// HIP failure.
 extern "C" int gs_generate(void* d_out, uint64_t nsamples, int device, double fs, double intermediate_freq,
                            const int8_t* codes, int ncodes, int code_len, int bit_periods, const gs_sat* sats,
                            int nsat, double sigma, uint64_t seed) {
   if (!d_out || !codes || !sats || nsat < 0 || nsat > kMaxSats || ((uintptr_t)d_out & 15)) return -1;
+  if (code_len <= 0 || bit_periods <= 0 || ncodes <= 0) return -1;  // the kernel divides by both
+  for (int i = 0; i < nsat; ++i)
+    if (sats[i].code_index < 0 || sats[i].code_index >= ncodes) return -1;
   if (hipSetDevice(device) != hipSuccess) return -2;
   Params hp;
   for (int i = 0; i < nsat; ++i) hp.sat[i] = sats[i];
@@ -252,7 +257,10 @@ extern "C" int gs_generate(void* d_out, uint64_t nsamples, int device, double fs
   Params* dp = nullptr;
   int8_t* dcodes = nullptr;
   if (hipMalloc((void**)&dp, sizeof(Params)) != hipSuccess) return -3;
-  if (hipMalloc((void**)&dcodes, (size_t)ncodes * code_len) != hipSuccess) return -3;
+  if (hipMalloc((void**)&dcodes, (size_t)ncodes * code_len) != hipSuccess) {
+    (void)hipFree(dp);
+    return -3;
+  }
   int rc = 0;
   if (hipMemcpy(dp, &hp, sizeof(Params), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(dcodes, codes, (size_t)ncodes * code_len, hipMemcpyHostToDevice) != hipSuccess)
@@ -260,6 +268,7 @@ extern "C" int gs_generate(void* d_out, uint64_t nsamples, int device, double fs
   if (!rc) {
     const uint64_t chunks = (nsamples + 7) / 8;
     const unsigned int grid = (unsigned int)((chunks + 255) / 256);
+    (void)hipGetLastError();  // an error another library's call left behind in this thread is not this launch's
     hipLaunchKernelGGL(synth_kernel, dim3(grid), dim3(256), 0, 0, (int8_t*)d_out, dcodes, dp);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = -5;
   }
@@ -268,10 +277,17 @@ extern "C" int gs_generate(void* d_out, uint64_t nsamples, int device, double fs
   return rc;
 }
 
-// Version 2: per-satellite codes / pilots / intermediate frequencies, int8 (out_i16 = 0) or int16 I/Q output.
+// Version 2: per-satellite codes / pilots / intermediate frequencies, int8 (out_i16 = 0) or int16 I/Q output.  Refuses (-1)
+// what gs_generate refuses and a satellite whose code or pilot chips do not lie inside codes[0 .. codes_bytes).
 extern "C" int gs_generate2(void* d_out, uint64_t nsamples, int device, double fs, const int8_t* codes, uint64_t codes_bytes,
                             const gs_sat2* sats, int nsat, double sigma, uint64_t seed, int out_i16) {
   if (!d_out || !codes || !sats || nsat < 0 || nsat > kMaxSats || ((uintptr_t)d_out & 15)) return -1;
+  for (int i = 0; i < nsat; ++i) {
+    const gs_sat2& st = sats[i];
+    if (st.code_len <= 0 || st.bit_periods <= 0) return -1;  // the kernel divides by both
+    if (st.code_offset < 0 || (uint64_t)st.code_offset + (uint64_t)st.code_len > codes_bytes) return -1;
+    if (st.pilot_offset >= 0 && (uint64_t)st.pilot_offset + (uint64_t)st.code_len > codes_bytes) return -1;
+  }
   if (hipSetDevice(device) != hipSuccess) return -2;
   static Params2 hp;
   for (int i = 0; i < nsat; ++i) hp.sat[i] = sats[i];
@@ -284,7 +300,10 @@ extern "C" int gs_generate2(void* d_out, uint64_t nsamples, int device, double f
   Params2* dp = nullptr;
   int8_t* dcodes = nullptr;
   if (hipMalloc((void**)&dp, sizeof(Params2)) != hipSuccess) return -3;
-  if (hipMalloc((void**)&dcodes, (size_t)codes_bytes) != hipSuccess) return -3;
+  if (hipMalloc((void**)&dcodes, (size_t)codes_bytes) != hipSuccess) {
+    (void)hipFree(dp);
+    return -3;
+  }
   int rc = 0;
   if (hipMemcpy(dp, &hp, sizeof(Params2), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(dcodes, codes, (size_t)codes_bytes, hipMemcpyHostToDevice) != hipSuccess)
@@ -292,6 +311,7 @@ extern "C" int gs_generate2(void* d_out, uint64_t nsamples, int device, double f
   if (!rc) {
     const uint64_t chunks = (nsamples + 7) / 8;
     const unsigned int grid = (unsigned int)((chunks + 255) / 256);
+    (void)hipGetLastError();  // as in gs_generate
     hipLaunchKernelGGL(synth2_kernel, dim3(grid), dim3(256), 0, 0, d_out, dcodes, dp);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = -5;
   }

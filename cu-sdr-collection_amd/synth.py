@@ -147,7 +147,9 @@ def generate_if_gpu(engine, sats, n_samples: int, fs: float, intermediate_freq: 
                     code_rate: float, code_len: int, seed: int, sigma: float = 20.0,
                     carrier_ratio: float = 1540.0, bit_periods: int = 20, attached: bool = False) -> None:
     """Allocates the engine's IF buffer (int8 I/Q) and fills it on the GPU.  attached=True: the engine already reads a buffer
-    of n_samples int8 I/Q samples that the caller owns (Engine.attach_if, e.g. a torch tensor about to be broadcast) - fill that."""
+    of n_samples int8 I/Q samples that the caller owns (Engine.attach_if, e.g. a torch tensor about to be broadcast) - fill that;
+    a buffer of another size, sample type or sample order raises ValueError before anything is written.
+    tests/test_gpu_synth.py holds the record to a float64 model (tests/synth_model.py) sample for sample."""
     import ctypes as C
     import os
 
@@ -167,6 +169,9 @@ def generate_if_gpu(engine, sats, n_samples: int, fs: float, intermediate_freq: 
     ptr, n = engine.if_buffer()
     if n != n_samples:
         raise ValueError(f"generate_if_gpu: the engine's buffer holds {n} samples, {n_samples} wanted")
+    from . import _lib as L
+    if engine.if_format() != (L.GC_I8, L.GC_IQ):
+        raise ValueError(f"generate_if_gpu writes int8 I,Q; the engine's buffer has format {engine.if_format()}")
     codes = np.ascontiguousarray(np.stack([np.asarray(code_fn(s.prn), dtype=np.int8) for s in sats]))
     arr = (gs_sat * len(sats))()
     for i, s in enumerate(sats):
@@ -189,7 +194,9 @@ def generate_if_mix_gpu(engine, groups, n_samples: int, fs: float, intermediate_
     """generate_if_mix on the GPU (libgnsssynth.so gs_generate2): allocates the engine's IF buffer (int8 or int16 I/Q)
     and fills it in HBM.  Same signal model; data bits and noise come from a counter-based hash instead of NumPy's
     generator, so the two generators agree in distribution, not sample for sample.  attached=True: fill the buffer the engine
-    already reads (Engine.attach_if on caller-owned memory of the same size and format) instead of allocating one."""
+    already reads (Engine.attach_if on caller-owned memory of the same size and format) instead of allocating one; a buffer
+    whose format is not (dtype, qi_order) raises ValueError before anything is written (an int16 record would overrun an int8
+    buffer of as many samples)."""
     import ctypes as C
     import os
 
@@ -212,6 +219,9 @@ def generate_if_mix_gpu(engine, groups, n_samples: int, fs: float, intermediate_
     ptr, have = engine.if_buffer()
     if have != n_samples:
         raise ValueError(f"generate_if_mix_gpu: the engine's buffer holds {have} samples, {n_samples} wanted")
+    want = (L.GC_I16 if i16 else L.GC_I8, L.GC_QI if qi_order else L.GC_IQ)
+    if engine.if_format() != want:      # an int16 record written into an int8 buffer of as many samples overruns it
+        raise ValueError(f"generate_if_mix_gpu writes format {want}; the engine's buffer has format {engine.if_format()}")
     flat, sats = [], []
     off = 0
     for g in groups:
