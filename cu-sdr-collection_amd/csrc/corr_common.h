@@ -182,17 +182,48 @@ __device__ __forceinline__ void load_words(const uint8_t* __restrict__ base, lon
   }
 }
 
+// A/B (scripts/variants.sh, docs/KNOBS.md): 1 = the block edges as before round 9 - mask_words sample by sample, the row_bcast steps
+// of wave_sum_lane63 as update_dpp + add, and in the replay instantiations of corr_fast.hip the edge test per lane, the channel's
+// constants read per block, the ramp step's high word moved from its scalar in every chunk and the Horner step's accumulators
+// copied back once per pair of chunks.
+#ifndef GC_FAST_PARENT_EDGES
+#define GC_FAST_PARENT_EDGES 0
+#endif
+
 // Zero the samples of an edge chunk that lie outside [0, N): sample j is valid iff 0 <= i0+j < N.
+// The valid samples are one contiguous range [lo, hi) = [max(0, -i0), min(SPL, N - i0)): it is derived once, as a bitmap of
+// the chunk's samples, and every word takes its mask from its own bits of that bitmap - no compare / select per sample.  With a
+// wave-uniform i0 and N (corr_fast.hip, replay) the masks are formed on the scalar unit.
 template <int MODE, int SPL>
-__device__ __forceinline__ void mask_words(unsigned int (&w)[SPL * Fmt<MODE>::bps / 4], int i0, int N) {
+__host__ __device__ __forceinline__ void mask_words(unsigned int (&w)[SPL * Fmt<MODE>::bps / 4], int i0, int N) {
   constexpr int bits = 8 * Fmt<MODE>::bps;
   constexpr int per_word = 32 / bits;
+#if GC_FAST_PARENT_EDGES
 #pragma unroll
   for (int j = 0; j < SPL; ++j) {
     const bool valid = (unsigned int)(i0 + j) < (unsigned int)N;
     const unsigned int m = (bits == 32) ? 0xffffffffu : (((1u << bits) - 1u) << ((j % per_word) * bits));
     if (!valid) w[j / per_word] &= ~m;
   }
+#else
+  static_assert(SPL <= 16 && SPL % per_word == 0, "the bitmap of a chunk's samples is built with 32-bit shifts");
+  // 0 <= lo <= hi <= SPL; lo == hi: no valid sample.  For i0 < N the unsigned difference N - i0 is exact.
+  const int lo = i0 >= 0 ? 0 : (i0 <= -SPL ? SPL : -i0);
+  const unsigned int left = (unsigned int)N - (unsigned int)i0;
+  const int hi_raw = i0 >= N ? 0 : (left >= (unsigned int)SPL ? SPL : (int)left);
+  const int hi = hi_raw > lo ? hi_raw : lo;
+  const unsigned int valid = (1u << hi) - (1u << lo);  // bit j: sample j is valid
+#pragma unroll
+  for (int q = 0; q < SPL / per_word; ++q) {
+    unsigned int m = 0u;
+#pragma unroll
+    for (int s = 0; s < per_word; ++s) {
+      const unsigned int field = (bits == 32) ? 0xffffffffu : (((1u << bits) - 1u) << (s * bits));
+      m |= (0u - ((valid >> (q * per_word + s)) & 1u)) & field;
+    }
+    w[q] &= m;
+  }
+#endif
 }
 
 #define GC_CVT_SDWA(sel)                                                                                  \
@@ -253,8 +284,18 @@ __device__ __forceinline__ float wave_sum_lane63(float v) {
   v += dpp(v, std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});  // row_shr:2
   v += dpp(v, std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});  // row_shr:4
   v += dpp(v, std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});  // row_shr:8
+#if GC_FAST_PARENT_EDGES
   v += dpp(v, std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});  // row_bcast:15
   v += dpp(v, std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});  // row_bcast:31
+#else
+  // The two broadcast steps as one v_add_f32_dpp each (the builtin form compiles to v_mov 0 + v_mov_dpp + v_add): rows 1 and 3 add lane 15
+  // of the row below, then rows 2 and 3 add lane 31.  The rows outside row_mask keep v where the builtin form made v + 0; none of
+  // their lanes is read afterwards on the way to lane 63.  s_nop 1: the two wait states a DPP read wants after the VALU write of
+  // its source (the assembler cannot see into the block).
+  asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
+      : "+v"(v));
+#endif
   return v;
 }
 

@@ -88,6 +88,10 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
   constexpr int NW = SPL * Fmt<MODE>::bps / 4;
   constexpr bool kReal = (MODE == I8_REAL || MODE == I16_REAL);
   constexpr int kShift = (SPL == 16) ? 4 : 3;
+  // Round 9, replay instantiations only (GC_FAST_PARENT_EDGES, corr_common.h): what a block's edges cost for nothing - the channel's
+  // constants once per workgroup, the edge masks on the scalar unit, the ramp step's words kept in registers, the Horner step in
+  // place.  The closed-loop and device-loop instantiations keep their code.
+  constexpr bool kEdges = !CL && !DEVLOOP && GC_FAST_PARENT_EDGES == 0;
 
   long long wg = blockIdx.x;
   if (p.xcd_swizzle && !DEVLOOP) {
@@ -119,13 +123,23 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
   float2* tab2[ARMS];
   unsigned short* tab16[ARMS];
   float* tabf[ARMS];
+  // kEdges: index_scale, mult[0], arms and stage_len[] of the workgroup's ONE channel, read here and not once per block (a dependent
+  // memory round trip behind every descriptor)
+  [[maybe_unused]] double wg_R = 0.0, wg_M = 0.0;
+  [[maybe_unused]] int wg_arms = 0, wg_stage[ARMS];
   {
     const long long lb0 = min(grp * p.bpw * p.stride + cslot, (long long)p.nblocks - 1);
     const gc_block blk0 = DEVLOOP ? p.devloop->chan[lb0].blk : CL ? load_block(p, lb0) : p.blocks[lb0];
     const DevChannel* __restrict__ chn0 = p.chans + blk0.channel;
+    if constexpr (kEdges) {
+      wg_R = chn0->index_scale;
+      wg_M = chn0->mult[0];
+      wg_arms = chn0->arms;
+    }
 #pragma unroll
     for (int a = 0; a < ARMS; ++a) {
       const int aa = (a < chn0->arms) ? a : 0;
+      if constexpr (kEdges) wg_stage[a] = chn0->stage_len[aa];
       tab2[a] = reinterpret_cast<float2*>(smem + 8 * (size_t)chn0->lds_off[aa]);
       tab16[a] = reinterpret_cast<unsigned short*>(smem + 2 * (size_t)chn0->lds_off[aa]);
       tabf[a] = reinterpret_cast<float*>(smem + 4 * (size_t)chn0->lds_off[aa]);
@@ -244,12 +258,20 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
   }
   unsigned long long dl_t0 = 0;
   if constexpr (DEVLOOP) dl_t0 = __builtin_amdgcn_s_memrealtime();
-  const DevChannel* __restrict__ chn = p.chans + blk.channel;
-  const int arms_here = chn->arms;
+  [[maybe_unused]] const DevChannel* __restrict__ chn = p.chans + blk.channel;
+  int arms_here;
+  if constexpr (kEdges) arms_here = wg_arms;
+  else arms_here = chn->arms;
 
   // ---- per-block uniform quantities (see corr_kernel.hip for the reference line citations) --------
-  const double R = chn->index_scale;
-  const double M = chn->mult[0];
+  double R, M;
+  if constexpr (kEdges) {
+    R = wg_R;
+    M = wg_M;
+  } else {
+    R = chn->index_scale;
+    M = chn->mult[0];
+  }
   const double rem = blk.rem_code_phase;
   const double step = blk.code_phase_step;
   const double d = blk.el_spacing;
@@ -338,7 +360,12 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
       ghi[sx] = (unsigned int)(fx[sx].G >> 32);
       kk[sx] = fx[sx].k0;
     }
-    const unsigned int Dlo = (unsigned int)Df, Dhi = (unsigned int)(Df >> 32);
+    const unsigned int Dlo = (unsigned int)Df;
+    unsigned int Dhi = (unsigned int)(Df >> 32);
+    int Di_v = Di;
+    // kEdges: opaque register copies of the ramp step's upper words - the compiler kept Dhi in its scalar and moved it into a vector
+    // register in every chunk
+    if constexpr (kEdges) asm("" : "+v"(Dhi), "+v"(Di_v));
     const uint8_t* __restrict__ bs = base + (long long)CB * (q0 + cbeg);  // uniform
     const unsigned int voff = (unsigned int)lane * CB;
     const unsigned int voff_last = min(voff, (unsigned int)(cend - 1 - cbeg - (iters - 1) * kFW) * CB);
@@ -361,7 +388,25 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
 #pragma unroll
           for (int sx = 0; sx < NS; ++sx) kk[sx] = 0;
         }
-        if ((i0 < 0) | (i0 + SPL > N)) mask_words<MODE, SPL>(w, i0, N);
+        if constexpr (kEdges) {
+          // Chunk c of the block starts at sample SPL * c - r (r = s0 mod SPL): only chunk 0 - lane 0 of the first iteration - can start
+          // before sample 0, and only the block's last chunk - lane tl of the last iteration - can end behind sample N - 1 (the chunks
+          // before it end at or before the one that holds sample N - 1; the idle lanes behind it are zero already).  Both edges are
+          // therefore wave-uniform: the masks are formed on the scalar unit and cost that one lane a v_and per word.
+          if (k == 0) {
+            const int ih = __builtin_amdgcn_readlane(i0, 0);
+            if (ih < 0 && lane == 0) mask_words<MODE, SPL>(w, ih, N);
+          }
+          if (last) {
+            int ce = cend;
+            asm volatile("" : "+s"(ce));  // opaque, as kq: formed here, not kept in a register across the loop
+            const int tl = (ce - 1 - cbeg) & (kFW - 1);
+            const int it = __builtin_amdgcn_readlane(i0, tl);
+            if (it + SPL > N && lane == tl) mask_words<MODE, SPL>(w, it, N);
+          }
+        } else {
+          if ((i0 < 0) | (i0 + SPL > N)) mask_words<MODE, SPL>(w, i0, N);
+        }
       }
 
       // transition positions and the near-tie filter
@@ -436,7 +481,10 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
               kx = max(-1, min(kx, 0x3fffffff));
 #pragma unroll
               for (int ar = 0; ar < ARMS; ++ar) {
-                const int kc = min(kx, chn->stage_len[(ar < arms_here) ? ar : 0] + 1);
+                int slen;
+                if constexpr (kEdges) slen = wg_stage[ar];
+                else slen = chn->stage_len[(ar < arms_here) ? ar : 0];
+                const int kc = min(kx, slen + 1);
                 const float cf = table_entry(ar, kc).x;
                 Ur[ar][x] = fmaf(cf, yr, Ur[ar][x]);
                 Ui[ar][x] = fmaf(cf, yi, Ui[ar][x]);
@@ -490,17 +538,27 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
       for (int ar = 0; ar < ARMS; ++ar)
 #pragma unroll
         for (int x = 0; x < 3; ++x) {
-          const float nr = fmaf(accr[ar][x], rotC, fmaf(-acci[ar][x], rotS, Ur[ar][x]));
-          const float ni = fmaf(accr[ar][x], rotS, fmaf(acci[ar][x], rotC, Ui[ar][x]));
-          accr[ar][x] = nr;
-          acci[ar][x] = ni;
+          if constexpr (kEdges) {
+            // The same four fused multiply-adds in the same order, the two that multiply an accumulator written as v_fma_f32 IN PLACE.
+            // As v_fmac_f32 (result in the addend's register) they left the new accumulators in the registers of U, and the second chunk
+            // of the loop body ended with a v_mov per accumulator to bring them back for the next trip.
+            const float tr = fmaf(-acci[ar][x], rotS, Ur[ar][x]);
+            asm("v_fma_f32 %0, %0, %1, %2" : "+v"(acci[ar][x]) : "s"(rotC), "v"(Ui[ar][x]));
+            acci[ar][x] = fmaf(accr[ar][x], rotS, acci[ar][x]);
+            asm("v_fma_f32 %0, %0, %1, %2" : "+v"(accr[ar][x]) : "s"(rotC), "v"(tr));
+          } else {
+            const float nr = fmaf(accr[ar][x], rotC, fmaf(-acci[ar][x], rotS, Ur[ar][x]));
+            const float ni = fmaf(accr[ar][x], rotS, fmaf(acci[ar][x], rotC, Ui[ar][x]));
+            accr[ar][x] = nr;
+            acci[ar][x] = ni;
+          }
         }
       // next chunk: t += 64*SPL*step*R*M, exactly: the 64-bit fraction's borrow carries into the integer part
 #pragma unroll
       for (int sx = 0; sx < NS; ++sx)
         asm("v_sub_co_u32_e32 %0, vcc, %0, %3\n\tv_subb_co_u32_e32 %1, vcc, %1, %4, vcc\n\tv_addc_co_u32_e32 %2, vcc, %2, %5, vcc"
             : "+v"(glo[sx]), "+v"(ghi[sx]), "+v"(kk[sx])
-            : "v"(Dlo), "v"(Dhi), "v"(Di)
+            : "v"(Dlo), "v"(Dhi), "v"(Di_v)
             : "vcc");
     };
 

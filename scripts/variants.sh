@@ -2,6 +2,7 @@
 # Tuning variants of libgnsscorr.so that differ in ONE translation unit's macros:
 #   scripts/variants.sh corr_fast "PFX:-DGC_FAST_PREFIX=1" ...   -> cu-sdr-collection_amd/lib/libgnsscorr_PFX.so
 #   scripts/variants.sh corr_fast "PAR:-DGC_FAST_PARENT_SCHEDULE=1"   (docs/KNOBS.md: the replay chunk loop as before round 7)
+#   scripts/variants.sh corr_fast "OLD:-DGC_FAST_PARENT_EDGES=1" "NEW:-DGC_FAST_PARENT_EDGES=0"   (the block edges as before round 9)
 set -e
 cd "$(dirname "$0")/../cu-sdr-collection_amd"
 unit="$1"; shift
