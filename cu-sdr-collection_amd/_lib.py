@@ -18,6 +18,8 @@ GC_OUT_STRIDE = 6 * GC_MAX_ARMS
 GC_BANK_MAX_TAPS = 64      # gc_correlate_bank
 GC_DDM_MAX_FREQS = 64      # gc_correlate_ddm
 GC_DDM_MAX_HYP = 128       # gc_correlate_ddm_search
+GC_WIN_RECT, GC_WIN_HAMMING = 0, 1   # gc_probe_window
+GC_PROBE_HIST_BINS = 257   # gc_probe_histogram: hist(x, -128:128)
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -119,6 +121,12 @@ class gc_acq_shift_pick(C.Structure):
 GC_SHIFT_PICK_GLOBAL, GC_SHIFT_PICK_SEQUENTIAL, GC_SHIFT_PICK_SEQUENTIAL_PAIRS = 0, 1, 2
 
 
+class gc_probe_psd_params(C.Structure):
+    """gc_probe_psd: nspans consecutive spans of nsamples samples, Welch segments of nfft samples that overlap by noverlap."""
+    _fields_ = [("first_sample", C.c_int64), ("nsamples", C.c_int64), ("nfft", C.c_int32), ("noverlap", C.c_int32),
+                ("window", C.c_int32), ("nspans", C.c_int32)]
+
+
 class gc_acq_result(C.Structure):
     _fields_ = [("coarse_bin", C.c_int32), ("code_phase", C.c_int32), ("peak", C.c_double),
                 ("peak_metric", C.c_double), ("coarse_freq", C.c_double)]
@@ -214,6 +222,9 @@ SYMBOLS = {
     "gc_debug_acq_surface": (C.c_int, [_P, C.POINTER(gc_acq_params), C.c_int, _P, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32)]),
     "gc_acq_guard_stats": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gc_probe_psd": (C.c_int, [_P, C.POINTER(gc_probe_psd_params), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "gc_probe_histogram": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "gc_debug_probe_tile_segments": (C.c_longlong, [C.c_int]),
 }
 
 _lib = None

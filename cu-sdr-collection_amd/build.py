@@ -40,7 +40,8 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                                   # gc_correlate_ddm_integrate: those maps added over runs of blocks on the device;
                                   # gc_correlate_ddm_search: that integration under many hypotheses, peaks picked on the device
                # the acquisition, one translation unit per part of the search (acq_internal.h is what they share)
-               "acq_fft.hip", "acq_coarse.hip", "acq_shift.hip", "acq_fine.hip", "acq_cond.hip", "acq_guard.hip", "navsync.hip"]
+               "acq_fft.hip", "acq_coarse.hip", "acq_shift.hip", "acq_fine.hip", "acq_cond.hip", "acq_guard.hip", "navsync.hip",
+               "probe.hip"]       # gc_probe_psd, gc_probe_histogram: a record's Welch spectrum (on acq_fft.hip's pass kernels) and level histograms
 
 
 def _tuned(spec: str) -> str:
@@ -54,7 +55,7 @@ LIBS = {
     "libgnsscorr_tuning.so": [_tuned(u) for u in _CORR_UNITS],
     "libgnsssynth.so": ["synth.hip"],
 }
-HEADERS = ["gc_internal.h", "corr_common.h", "launch_plan.h", "bank_plan.h", "devloop.h", "acq_guard.h", "acq_internal.h", os.path.join("..", "..", "include", "gnsscorr.h")]
+HEADERS = ["gc_internal.h", "corr_common.h", "launch_plan.h", "bank_plan.h", "probe_plan.h", "devloop.h", "acq_guard.h", "acq_internal.h", os.path.join("..", "..", "include", "gnsscorr.h")]
 # --offload-compress: the gfx950 code objects inside the fat binary are zstd-compressed (10.1 -> ~1.6 MB; the HIP runtime inflates them
 # when the library is loaded: ~20 ms once per process)
 FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",

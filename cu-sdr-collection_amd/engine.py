@@ -626,6 +626,35 @@ class Engine:
     def preamble_xcorr(self, i_p: np.ndarray, pattern: np.ndarray) -> np.ndarray:
         return self.sync_xcorr(i_p, pattern)
 
+    # ---- the record before acquisition (probeData.m) ----------------------------------------------
+    PROBE_WINDOWS = {"rect": L.GC_WIN_RECT, "hamming": L.GC_WIN_HAMMING}
+
+    def probe_psd(self, first_sample: int, nsamples: int, nfft: int = 32768, noverlap: int = 2048, window="hamming", nspans: int = 1):
+        """gc_probe_psd: pwelch(x, hamming(nfft) | ones, noverlap, nfft, fs, 'twosided') without detrending of `nspans` consecutive spans
+        of `nsamples` samples of the record, samples in file order (include/gnsscorr.h) -> (float64 [nspans, nfft], bin 0 = DC; K segments per span)."""
+        if isinstance(window, str):
+            if window not in self.PROBE_WINDOWS:
+                raise ValueError(f"window must be one of {sorted(self.PROBE_WINDOWS)}, not {window!r}")
+            window = self.PROBE_WINDOWS[window]
+        p = L.gc_probe_psd_params(int(first_sample), int(nsamples), int(nfft), int(noverlap), int(window), int(nspans))
+        out = np.empty((max(int(nspans), 0), max(int(nfft), 0)), dtype=np.float64)
+        k = C.c_int64(0)
+        L.check(self._lib.gc_probe_psd(self._ctx, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(k)))
+        return out, int(k.value)
+
+    def probe_histogram(self, first_sample: int, nsamples: int):
+        """gc_probe_histogram: hist(component, -128:128) of both components in file order (row 1 all zero for a real record) ->
+        (uint64 [2, 257], max(c0^2 + c1^2) as an exact integer)."""
+        counts = np.zeros((2, L.GC_PROBE_HIST_BINS), dtype=np.uint64)
+        m = C.c_int64(0)
+        L.check(self._lib.gc_probe_histogram(self._ctx, int(first_sample), int(nsamples), counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(m)))
+        return counts, int(m.value)
+
+    @staticmethod
+    def debug_probe_tile_segments(nfft: int) -> int:
+        """gc_debug_probe_tile_segments (test hook, host code only): segments of an nfft-point probe_psd the library transforms at a time."""
+        return int(L.load().gc_debug_probe_tile_segments(int(nfft)))
+
     def debug_fft(self, x: np.ndarray, inverse: bool = False) -> np.ndarray:
         """x: complex64 [nbatch, n].  The library's FFT (test hook)."""
         x = np.ascontiguousarray(x, dtype=np.complex64)

@@ -90,6 +90,42 @@ def _acq_params(settings, first_sample: int) -> L.gc_acq_params:
     return p
 
 
+def probeData(fid: Engine, settings, first_sample: int = 0):
+    """probeData.m without the figure: the numbers behind its four plots for the 100 code periods from `first_sample` of the loaded
+    record (probeData.m:66-76), computed on the device (gc_probe_psd, gc_probe_histogram) - samples in file order as :104 takes them.
+      freq, psd      what pwelch(data, 32768, 2048, 32768, fs) returns: fileType 2 the two-sided spectrum over 0 .. fs in Hz (:131);
+                     fileType 1 the one-sided one, called with fs / 1e6 (:128) - nfft/2 + 1 bins over 0 .. fs/2 in MHz, density per MHz
+      nsegments      the Welch segments behind it
+      timeScale, data   timeScale(1:round(samplesPerCode/2)) in seconds and those samples (:90,96-97,106-115; complex for fileType 2)
+      histCenters, histI, histQ   hist(real(data), -128:128), hist(imag(data), -128:128) (:146,155,163; histQ None for fileType 1)
+      dmax           max(abs(data)) + 1 (:148)"""
+    if settings.fileType not in (1, 2):
+        raise ValueError("probeData(): settings.fileType must be 1 (real) or 2 (I/Q)")
+    fs = float(settings.samplingFreq)
+    spc = _round(fs / (settings.codeFreqBasis / settings.codeLength))                  # :66-67
+    n = 100 * spc                                                                      # :76
+    dt, layout = fid.if_format()
+    if (layout == L.GC_REAL) != (settings.fileType == 1):
+        raise ValueError("probeData(): settings.fileType does not match the loaded record's layout")
+    fid.set_sampling_freq(fs)
+    nfft, noverlap = 32768, 2048
+    psd, k = fid.probe_psd(first_sample, n, nfft, noverlap, "hamming")                 # :128-131
+    psd = psd[0]
+    counts, norm2 = fid.probe_histogram(first_sample, n)                               # :146-163
+    half = _round(spc / 2)
+    raw = fid.read_if(first_sample, half, dtype=np.int16 if dt == L.GC_I16 else np.int8, layout=layout).astype(np.float64)
+    if settings.fileType == 1:
+        fsm = fs / 1e6
+        one = psd[:nfft // 2 + 1] * 1e6                                                # density per MHz
+        one[1:nfft // 2] *= 2.0                                                        # one-sided: every bin but DC and Nyquist holds both sides
+        freq, spec, data = np.arange(nfft // 2 + 1) * (fsm / nfft), one, raw
+    else:
+        freq, spec, data = np.arange(nfft) * (fs / nfft), psd, raw[0::2] + 1j * raw[1::2]   # :104
+    return SimpleNamespace(freq=freq, psd=spec, nsegments=k, timeScale=np.arange(half) / fs, data=data,
+                           histCenters=np.arange(-128, 129), histI=counts[0].copy(),
+                           histQ=counts[1].copy() if settings.fileType == 2 else None, dmax=math.sqrt(norm2) + 1.0)
+
+
 def acquisition(engine: Engine, settings, first_sample: int | None = None, n_long: int | None = None):
     """acqResults = acquisition(longSignal, settings) with longSignal = the IF buffer from
     `first_sample` (default settings.skipNumberOfBytes, as postProcessing.m:74-96 reads it).

@@ -709,6 +709,55 @@ int gc_debug_acq_surface(gc_context* ctx, const gc_acq_params* p, int narms, con
  * ties: PRNs of the last search resolved that way; max_dev: largest |float32 peak - float64 peak| / float64 peak over its PRNs. */
 int gc_acq_guard_stats(gc_context* ctx, int32_t* ties, double* max_dev, double* eps);
 
+/* ---- a look at the record before acquisition: probeData.m on the device ---------------------------------------------------------
+ * What every package's init.m runs first (include/probeData.m:76 the stretch of record, :104 the samples, :128-131 pwelch(data,
+ * 32768, 2048, 32768, fs), :146-163 hist(real(data), -128:128), hist(imag(data), -128:128) and dmax): the Welch spectrum and the
+ * level histograms of a stretch of the context's IF record, in any of its six formats.  Both calls are synchronous and run on the
+ * context's stream; they own their buffers (released by gc_destroy) and leave the acquisition's, the conditioned signal's and the
+ * bank's untouched.  New entry points are detected by symbol: GC_API_VERSION is unchanged.
+ *
+ * Samples are taken in FILE order, as probeData.m:104 does in every package: of a two-component record component 0 is the first
+ * value of each pair and component 1 the second, z = c0 + i*c1, whatever the context's layout says (a GC_QI context gives the
+ * bytes of a GC_IQ context on the same buffer); of a real record z = c0 and component 1 is absent.
+ *
+ * gc_probe_psd: pwelch without detrending, two-sided, density scaling, for nspans consecutive spans of nsamples samples each.
+ *   step = nfft - noverlap; K = floor((nsamples - noverlap) / step) segments per span, segment k = samples [k*step, k*step + nfft)
+ *   of the span, what is left over is dropped (*nsegments = K).
+ *   w[n] = 0.54 - 0.46 cos(2 pi n / (nfft - 1)) (GC_WIN_HAMMING: MATLAB's symmetric hamming(nfft)) or 1 (GC_WIN_RECT), applied as
+ *   (float)w[n] * (float)x.
+ *   psd[s][b] = sum_k |FFT(w .* x_k)[b]|^2 / (K * fs * sum_n w[n]^2), b in FFT order (bin 0 = DC), fs from gc_set_sampling_freq,
+ *   sum w^2 in float64.
+ * The transform is the acquisition's float32 transform (nfft = 2^a 3^b 5^c, its second factor at most 2048); |X|^2 is added over
+ * the segments in float64, in segment order, one accumulator per (span, bin), without atomics: the same input gives the same bytes,
+ * and row s of a call with spans is bit for bit the call with nspans = 1 at that span's start - it depends neither on the other
+ * spans nor on where the library cuts the segment list into tiles.  A real record gets the two-sided spectrum too; folding it to
+ * one side (doubling bins 1 .. nfft/2 - 1) is the caller's.
+ *
+ * gc_probe_histogram: counts[c][v + 128] = samples of component c with value v, values below -128 or above +128 (int16 records)
+ * counted in the end bins - hist(x, -128:128); row 1 is all zero for a real record.  *max_norm2 = max(c0^2 + c1^2) as an exact
+ * integer (probeData.m:148 dmax = sqrt(.) + 1 is the caller's).  Integer arithmetic throughout, exact for any range of the record.
+ *
+ * Refusals (nothing is computed, no output is written): GC_E_INVALID for a null ctx / p / psd / counts, first_sample < 0,
+ * nsamples < 1, nspans < 1, nfft < 2, noverlap outside [0, nfft), nsamples < nfft, an unknown window; GC_E_STATE without a record
+ * and, for the spectrum, without a sampling frequency; GC_E_UNSUPPORTED for an nfft the transform has no plan for (a prime factor of
+ * 7 or more, a row longer than 2048); GC_E_RANGE when a span or the range ends beyond the record; GC_E_NOMEM. */
+enum gc_probe_window { GC_WIN_RECT = 0, GC_WIN_HAMMING = 1 };
+typedef struct gc_probe_psd_params {
+  int64_t first_sample;  /* 0-based sample (pair) index of span 0 */
+  int64_t nsamples;      /* samples of EACH span */
+  int32_t nfft;          /* segment = window = transform length */
+  int32_t noverlap;      /* 0 <= noverlap < nfft */
+  int32_t window;        /* gc_probe_window */
+  int32_t nspans;        /* >= 1 consecutive spans: span s starts at first_sample + s*nsamples */
+} gc_probe_psd_params;   /* 32 bytes */
+int gc_probe_psd(gc_context* ctx, const gc_probe_psd_params* p, double* psd /* [nspans][nfft] */, int64_t* nsegments /* may be NULL */);
+#define GC_PROBE_HIST_BINS 257
+int gc_probe_histogram(gc_context* ctx, int64_t first_sample, int64_t nsamples, uint64_t* counts /* [2][GC_PROBE_HIST_BINS] */,
+                       int64_t* max_norm2 /* may be NULL */);
+/* Test hook (host code only, no context): segments of an nfft-point gc_probe_psd the library transforms at a time (a tile of its
+ * segment list); 0 for nfft < 2. */
+long long gc_debug_probe_tile_segments(int nfft);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,11 @@
  *   x    = gnsscorr_mex('read_if', h, firstSample0, n, 'int8'|'int16', valuesPerSample)   % raw record samples back
  *   [name, cus] = gnsscorr_mex('device_info', h)
  *   [ties, maxDev, eps] = gnsscorr_mex('acq_guard_stats', h)                         % float64 guard of the last search (gc_acq_guard_stats)
+ *   [P, K] = gnsscorr_mex('probe_psd', h, firstSample0, nSamples[, nfft[, noverlap[, 'hamming'|'rect'[, nspans]]]])   % probeData.m's
+ *          pwelch(data, 32768, 2048, 32768, fs, 'twosided') (the defaults; no detrending) of nspans consecutive spans of nSamples samples
+ *          of the record, samples in file order (gc_probe_psd): P nfft x nspans, bin 1 = DC; K the Welch segments per span
+ *   [counts, maxNorm2] = gnsscorr_mex('probe_histogram', h, firstSample0, nSamples)   % hist(., -128:128) of both components in file
+ *          order (gc_probe_histogram): counts 257 x 2 uint64 (column 2 all zero for a real record); dmax = sqrt(maxNorm2) + 1
  *   n    = gnsscorr_mex('device_count')                                              % HIP devices visible: one context per device
  *   prev = gnsscorr_mex('set_precision', h, 'double'|'single')                    % float64 correlations for every later correlate /
  *          track call of this context (gc_set_precision), 'single' = the float32 kernels (default); returns the previous setting
@@ -653,6 +658,40 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     plhs[0] = mxCreateDoubleScalar(ties);
     if (nlhs > 1) plhs[1] = mxCreateDoubleScalar(dev);
     if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(eps);
+  } else if (!strcmp(cmd, "probe_psd")) {
+    /* [P, K] = gnsscorr_mex('probe_psd', h, firstSample0, nSamples[, nfft[, noverlap[, window[, nspans]]]]): gc_probe_psd's `psd` as it
+       lies in memory, one column per span */
+    if (nrhs < 4) mexErrMsgIdAndTxt("gnsscorr:usage", "probe_psd: h, firstSample0, nSamples[, nfft[, noverlap[, 'hamming'|'rect'[, nspans]]]]");
+    gc_probe_psd_params p;
+    memset(&p, 0, sizeof p);
+    p.first_sample = (int64_t)mxGetScalar(prhs[2]);
+    p.nsamples = (int64_t)mxGetScalar(prhs[3]);
+    p.nfft = nrhs > 4 ? (int32_t)mxGetScalar(prhs[4]) : 32768;
+    p.noverlap = nrhs > 5 ? (int32_t)mxGetScalar(prhs[5]) : 2048;
+    p.window = GC_WIN_HAMMING;
+    if (nrhs > 6) {
+      char win[16] = "";
+      mxGetString(prhs[6], win, sizeof win);
+      p.window = !strcmp(win, "hamming") ? GC_WIN_HAMMING : !strcmp(win, "rect") ? GC_WIN_RECT : -1;
+      if (p.window < 0) mexErrMsgIdAndTxt("gnsscorr:usage", "probe_psd: window 'hamming' or 'rect', not '%s'", win);
+    }
+    p.nspans = nrhs > 7 ? (int32_t)mxGetScalar(prhs[7]) : 1;
+    int64_t k = 0;
+    plhs[0] = mxCreateDoubleMatrix((mwSize)(p.nfft > 0 ? p.nfft : 0), (mwSize)(p.nspans > 0 ? p.nspans : 0), mxREAL);
+    int rc = gc_probe_psd(handle(prhs[1]), &p, mxGetDoubles(plhs[0]), &k);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
+    if (rc) fail("gc_probe_psd");
+    if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)k);
+  } else if (!strcmp(cmd, "probe_histogram")) {
+    /* [counts, maxNorm2] = gnsscorr_mex('probe_histogram', h, firstSample0, nSamples): gc_probe_histogram's `counts` as it lies in
+       memory, one column per component */
+    if (nrhs < 4) mexErrMsgIdAndTxt("gnsscorr:usage", "probe_histogram: h, firstSample0, nSamples");
+    int64_t m = 0;
+    plhs[0] = mxCreateNumericMatrix(GC_PROBE_HIST_BINS, 2, mxUINT64_CLASS, mxREAL);
+    int rc = gc_probe_histogram(handle(prhs[1]), (int64_t)mxGetScalar(prhs[2]), (int64_t)mxGetScalar(prhs[3]), (uint64_t*)mxGetData(plhs[0]), &m);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
+    if (rc) fail("gc_probe_histogram");
+    if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)m);
   } else if (!strcmp(cmd, "device_count")) {
     int n = 0;
     if (gc_device_count(&n)) fail("gc_device_count");
