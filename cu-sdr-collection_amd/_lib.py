@@ -20,6 +20,8 @@ GC_DDM_MAX_FREQS = 64      # gc_correlate_ddm
 GC_DDM_MAX_HYP = 128       # gc_correlate_ddm_search
 GC_WIN_RECT, GC_WIN_HAMMING = 0, 1   # gc_probe_window
 GC_PROBE_HIST_BINS = 257   # gc_probe_histogram: hist(x, -128:128)
+GC_CANCEL_MAX_CHANNELS = 64   # gc_cancel: distinct channels per call
+GC_CANCEL_SUBTRACT, GC_CANCEL_MODEL = 0, 1   # gc_cancel_mode
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -225,6 +227,7 @@ SYMBOLS = {
     "gc_probe_psd": (C.c_int, [_P, C.POINTER(gc_probe_psd_params), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "gc_probe_histogram": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "gc_debug_probe_tile_segments": (C.c_longlong, [C.c_int]),
+    "gc_cancel": (C.c_int, [_P, _P, C.c_int, C.POINTER(gc_block), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
 }
 
 _lib = None

@@ -41,7 +41,8 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                                   # gc_correlate_ddm_search: that integration under many hypotheses, peaks picked on the device
                # the acquisition, one translation unit per part of the search (acq_internal.h is what they share)
                "acq_fft.hip", "acq_coarse.hip", "acq_shift.hip", "acq_fine.hip", "acq_cond.hip", "acq_guard.hip", "navsync.hip",
-               "probe.hip"]       # gc_probe_psd, gc_probe_histogram: a record's Welch spectrum (on acq_fft.hip's pass kernels) and level histograms
+               "probe.hip",       # gc_probe_psd, gc_probe_histogram: a record's Welch spectrum (on acq_fft.hip's pass kernels) and level histograms
+               "cancel.hip"]      # gc_cancel: tracked components rebuilt in float64 from their descriptors and subtracted from the record
 
 
 def _tuned(spec: str) -> str:
@@ -65,7 +66,7 @@ FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-f
 # header compiled under the default -ffp-contract=fast, so the backend fuses them into v_fma_f64 (one rounding
 # instead of two: wrong table index at exact ties).  These translation units therefore forbid contraction;
 # wanted FMAs are written as fmaf() / fma().
-NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip", "corr_bank.hip"}
+NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip", "corr_bank.hip", "cancel.hip"}
 
 
 def _hipcc() -> str:

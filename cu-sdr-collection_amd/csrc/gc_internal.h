@@ -193,6 +193,7 @@ struct gc_context {
   GcBuf acqbuf[ACQ_NBUF];  // fine-frequency stage: codes, detections, per-code sums; conditioned signal of gc_acq_condition + its scratch
   long long acq_cond_n = 0;  // complex float samples in acqbuf[ACQ_COND_SIG] (gc_acq_params.source = 1 searches them)
   void* probe = nullptr;     // gc_probe_psd / gc_probe_histogram: their own plan, twiddle table, window, rows and accumulators (probe.hip: ProbeState)
+  void* cancel = nullptr;    // gc_cancel: sorted descriptors, channel list, projection partials and amplitudes (cancel.hip: CancelState)
 
   // gc_track_multi: this context's tracking call runs next to other contexts' on the same device.  Its persistent kernels
   // are then launched with a plain launch instead of a cooperative one (gc_launch_persistent below).
@@ -274,6 +275,7 @@ void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const 
 int gc_bytes_per_sample(int dtype, int layout);
 void gc_acq_free(gc_context* ctx);  // acq_coarse.hip
 void gc_probe_free(gc_context* ctx);  // probe.hip
+void gc_cancel_free(gc_context* ctx);  // cancel.hip
 int gc_sync_channels(gc_context* ctx);
 // Launches the correlator for `nblocks` descriptors of scope `s` already on the device: plans (launch_plan.h), fills the
 // kernel arguments from the plan, dispatches on its kernel, combines the partial sums where splits > 1.

@@ -104,6 +104,7 @@ int gc_destroy(gc_context* ctx) {
   for (GcBuf& b : ctx->acqbuf) gc_buf_free(b);
   gc_acq_free(ctx);
   gc_probe_free(ctx);
+  gc_cancel_free(ctx);
   (void)hipEventDestroy(ctx->ev_start);
   (void)hipEventDestroy(ctx->ev_stop);
   (void)hipStreamDestroy(ctx->stream);

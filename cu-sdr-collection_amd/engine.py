@@ -313,6 +313,36 @@ class Engine:
                                                   None if pk is None or nmaps == 0 else pk.ctypes.data_as(C.POINTER(L.gc_ddm_peak))))
         return (None if coh is None else coh[..., 0] + 1j * coh[..., 1]), pw, pk
 
+    CANCEL_MODES = {"subtract": L.GC_CANCEL_SUBTRACT, "model": L.GC_CANCEL_MODEL}
+
+    @classmethod
+    def _cancel_args(cls, nblocks: int, amp, mode):
+        """(gc_cancel_mode, amp_in as float64 [nblocks, GC_MAX_ARMS, 2] or None) of cancel()'s keywords; ValueError for a mode that is
+        neither "subtract" nor "model" and for amplitudes of another shape - before any library call."""
+        if not isinstance(mode, str) or mode not in cls.CANCEL_MODES:
+            raise ValueError(f"mode must be one of {sorted(cls.CANCEL_MODES)}, not {mode!r}")
+        if amp is None:
+            return cls.CANCEL_MODES[mode], None
+        a = np.asarray(amp)
+        if a.shape != (nblocks, L.GC_MAX_ARMS):
+            raise ValueError(f"amp must be complex [nblocks, GC_MAX_ARMS] = [{nblocks}, {L.GC_MAX_ARMS}], not {a.shape}")
+        a = a.astype(np.complex128)
+        return cls.CANCEL_MODES[mode], np.ascontiguousarray(np.stack([a.real, a.imag], axis=-1))
+
+    def cancel(self, blocks, dst: "Engine | None" = None, amp=None, mode: str = "subtract") -> np.ndarray:
+        """gc_cancel: the component every block describes - its prompt replica in float64 with the amplitude `amp[b, arm]`, or (None)
+        the record's own projection on the replica - taken out of this engine's record sample by sample (mode "subtract") or written
+        alone ("model"), into `dst`'s record (same sample count, dtype and layout; alloc_if) or (None) in place.  The blocks may come in
+        any order and from up to GC_CANCEL_MAX_CHANNELS channels; el_spacing is ignored (include/gnsscorr.h).
+        Returns the amplitudes used, complex128 [nblocks, GC_MAX_ARMS], unused arms zero."""
+        n = len(blocks)
+        code, a_in = self._cancel_args(n, amp, mode)
+        out = np.zeros((n, L.GC_MAX_ARMS, 2))
+        dp = C.POINTER(C.c_double)
+        L.check(self._lib.gc_cancel(self._ctx, (self if dst is None else dst)._ctx, n, blocks, None if a_in is None else a_in.ctypes.data_as(dp),
+                                    out.ctypes.data_as(dp), code))
+        return out[..., 0] + 1j * out[..., 1]
+
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition
         (corr_multi.hip), 5 hybrid for channels with a derived six-fold arm (corr_cboc.hip), 6 float64 (corr_f64.hip), -1 mixed

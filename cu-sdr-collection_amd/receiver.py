@@ -419,14 +419,15 @@ def tracking(fid: Engine, channel, settings, signal: str = "GPS_L1CA", device_lo
 BANK_CHANNEL = 255   # the engine's channel slot correlation_function() configures (the last one: tracking() fills from 0)
 
 
-def _tracked_blocks(fid: Engine, trackResults_k, channel_k, settings, signal: str, epochs):
+def _tracked_blocks(fid: Engine, trackResults_k, channel_k, settings, signal: str, epochs, slot: int = BANK_CHANNEL):
     """The descriptors of the blocks a tracked channel's loop cut, from the state tracking.m records per epoch, on the engine's
-    BANK_CHANNEL slot (configured here with the signal's tables; the sampling frequency is set too).  Returns (blocks, arms)."""
+    channel slot `slot` (BANK_CHANNEL unless given; configured here with the signal's tables; the sampling frequency is set too).
+    Returns (blocks, arms)."""
     from . import signals
     spec = signals.SIGNALS[signal]
     sat = getattr(channel_k, spec.id_field, trackResults_k.PRN)                       # as _tracking_prepare: 'K' for GLONASS
     tables = spec.tables(sat, settings)
-    fid.set_channel(BANK_CHANNEL, tables, index_scale=spec.index_scale, arm_mult=spec.arm_mult, windows=spec.windows)
+    fid.set_channel(slot, tables, index_scale=spec.index_scale, arm_mult=spec.arm_mult, windows=spec.windows)
     fid.set_sampling_freq(settings.samplingFreq)
     pos_all = np.asarray(trackResults_k.absoluteSample, dtype=np.float64)
     if epochs is None:
@@ -447,7 +448,7 @@ def _tracked_blocks(fid: Engine, trackResults_k, channel_k, settings, signal: st
             # with pilotTRKflag = 0 the channel has the CM table alone, no window, and the library takes it
             step, rem, length = 2 * step, 2 * rem, 2 * settings.codeLength
             pos = float(np.rint(pos - 1 + rem / step))
-        b.channel = BANK_CHANNEL
+        b.channel = slot
         b.first_sample = int(pos)
         b.rem_code_phase = rem
         b.code_phase_step = step
@@ -473,6 +474,52 @@ def correlation_function(fid: Engine, trackResults_k, channel_k, settings, offse
     there is replaced; tracking() fills slots from 0) and the sampling frequency is set to settings.samplingFreq."""
     blocks, arms = _tracked_blocks(fid, trackResults_k, channel_k, settings, signal, epochs)
     return fid.correlate_bank(blocks, offsets)[:, :arms, :]
+
+
+def cancel_tracked(fid: Engine, trackResults, channel, settings, which=None, signal: str = "GPS_L1CA", epochs=None, dst: Engine | None = None,
+                   mode: str = "subtract", amp=None):
+    """What lies under the signals a tracking run followed: every chosen channel's tracked component rebuilt from the state tracking.m
+    records per epoch (the blocks of correlation_function()) and taken out of the record sample by sample - a reflection next to the
+    peak, a weak satellite under a strong one's cross-correlation floor, the direct signal's leak into a down-looking record.  One
+    gc_cancel call for all channels (include/gnsscorr.h); the bank, the maps, acquisition() and tracking() then run on the residual.
+
+    trackResults, channel: what tracking() returned / was given; the record must be loaded in `fid`.
+    which: indices of the channels to cancel (None: every channel that was tracked, PRN != 0), at most GC_CANCEL_MAX_CHANNELS.
+    epochs: indices of the epochs to cancel, for every chosen channel (None: every epoch a channel completed).
+    dst: the engine whose record receives the result (same sample count, dtype and layout: alloc_if); None works in place.
+    mode: "subtract" leaves the residual, "model" writes the rebuilt components alone.
+    amp: None projects every block on its replica; else one complex array [n_epochs, arms] per chosen channel.
+    Returns (the engine that holds the result, [complex128 [n_epochs, arms] per chosen channel]: the amplitudes used).
+    Side effects on `fid`: the chosen channels' tables go to the engine's last channel slots, counting down from BANK_CHANNEL, one per
+    channel (whatever a caller keeps there is replaced), and the sampling frequency is set to settings.samplingFreq."""
+    Engine._cancel_args(0, None, mode)                                                # ValueError before anything runs
+    if which is None:
+        which = [i for i, tr in enumerate(trackResults) if getattr(tr, "PRN", 0) != 0]
+    which = [int(i) for i in which]
+    if len(which) > L.GC_CANCEL_MAX_CHANNELS:
+        raise ValueError(f"cancel_tracked(): at most {L.GC_CANCEL_MAX_CHANNELS} channels per call, not {len(which)}")
+    if amp is not None:
+        amp = [np.asarray(a) for a in amp]
+        if len(amp) != len(which) or any(a.ndim != 2 or not 1 <= a.shape[1] <= L.GC_MAX_ARMS for a in amp):
+            raise ValueError("cancel_tracked(): amp holds one complex array [n_epochs, arms] per chosen channel")
+    parts = [_tracked_blocks(fid, trackResults[i], channel[i], settings, signal, epochs, slot=BANK_CHANNEL - k) for k, i in enumerate(which)]
+    blocks = fid.make_blocks(sum(len(b) for b, _ in parts))
+    amp_in = None if amp is None else np.zeros((len(blocks), L.GC_MAX_ARMS), dtype=np.complex128)
+    n = 0
+    for k, (b, arms) in enumerate(parts):
+        if amp is not None:
+            if amp[k].shape != (len(b), arms):
+                raise ValueError(f"cancel_tracked(): amp[{k}] must be [{len(b)}, {arms}], not {amp[k].shape}")
+            amp_in[n:n + len(b), :arms] = amp[k]
+        for x in b:
+            blocks[n] = x
+            n += 1
+    used = fid.cancel(blocks, dst=dst, amp=amp_in, mode=mode)
+    out, n = [], 0
+    for b, arms in parts:
+        out.append(used[n:n + len(b), :arms])
+        n += len(b)
+    return (fid if dst is None else dst), out
 
 
 def delay_doppler_map(fid: Engine, trackResults_k, channel_k, settings, offsets, freqs, signal: str = "GPS_L1CA", epochs=None):

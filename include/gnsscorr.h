@@ -758,6 +758,50 @@ int gc_probe_histogram(gc_context* ctx, int64_t first_sample, int64_t nsamples, 
  * segment list); 0 for nfft < 2. */
 long long gc_debug_probe_tile_segments(int nfft);
 
+/* ---- what lies under a tracked signal: the tracked components taken out of a record ------------------------------------------------
+ * gc_cancel rebuilds the component every block descriptor describes - the prompt replica of tracking.m:247-300 with the amplitude the
+ * record itself gives it - and subtracts it sample by sample (csrc/cancel.hip); the bank, the maps, acquisition and tracking then run
+ * on the residual: a reflection under the direct signal's triangle, a weak satellite under a strong one's cross-correlation floor,
+ * the direct signal's leak into a down-looking record.  `src` holds the record, the channels and the sampling frequency; `dst` a
+ * record of the same sample count, dtype and layout on the same device (gc_alloc_if) that receives the result; dst == src (or a
+ * context sharing src's record) works in place and gives the same bytes as out of place.  Synchronous, on src's stream.  New entry
+ * points are detected by symbol: GC_API_VERSION is unchanged.
+ *
+ * Definition, in float64, every operation rounded by itself (no fused multiply-add); the replica is the GC_PREC_F64 correlator's
+ * prompt tap (csrc/corr_f64.hip).  Block b (channel ch of R = index_scale and arms a with m_a = arm_mult; N = blksize,
+ * s0 = first_sample, rem = rem_code_phase, step = code_phase_step) covers the record samples s0 + i, 0 <= i < N:
+ *   carrier   trig_i = ((carr_freq * 2.0) * pi) * (i / fs) + rem_carr_phase,  (sn, cs) = sincos(trig_i)
+ *   code      t_i = element i of the reference's colon (rem*R) : (step*R) : (((N-1)*step + rem)*R) - (rem*R) + i*(step*R) below the
+ *             middle, the end - (N-1-i)*(step*R) above it, the mean of both ends in the middle;
+ *             k = ceil(t_i * m_a) + table_offset[a] clamped to the table, c_a(i) = table_a[k] (code windows, derived arms: the table)
+ *   sample    (re, im) of the record: I/Q as stored, Q/I swapped, real records im = 0
+ *   baseband  ib = cs*re + sn*im,  qb = cs*im - sn*re
+ *   amplitude A[b][a] = amp_in[b][a] where amp_in is given; else the projection A = P / E per component, P = sum_i c_a(i) (ib + j qb)
+ *             a float64 sum in a fixed order (bitwise the same from run to run and whatever else is in the call), E = sum_i c_a(i)^2
+ *             an exact integer, A = 0 where E == 0.  Arms are projected independently; P is taken from src's record as it is when
+ *             the call starts.
+ *   model     m_b(i) = sum over a, from +0.0 in arm order, of c_a(i) * ((A_r*cs - A_i*sn) + j (A_r*sn + A_i*cs)); on GC_REAL records
+ *             2 * Re(.) - a real record holds half of the phasor.  M[n] = the sum of m_b over the blocks that cover sample n, added
+ *             in ascending channel index, starting from +0.0.
+ *   output    into dst's record, same position and format: GC_CANCEL_SUBTRACT clamp(rint(x[n] - M[n])), GC_CANCEL_MODEL
+ *             clamp(rint(M[n])) per component; rint rounds to even, the clamp is the dtype's full range.  A sample no block covers is
+ *             copied (SUBTRACT) or zero (MODEL).
+ * amp_out (may be NULL) receives the amplitudes used, [nblocks][GC_MAX_ARMS][2] = {re, im} in the caller's block order as amp_in,
+ * arms the block's channel does not have zero.
+ * Independence: a sample's output depends on its own input sample and on the blocks that cover it - not on the list's order beyond
+ * the rule above, not on the other blocks of the call.  The same input gives the same bytes.  The context's precision setting is
+ * ignored: float64 always.
+ * Accepted: what gc_correlate asks of a descriptor with el_spacing ignored (taken as 0); the blocks in any order; at most
+ * GC_CANCEL_MAX_CHANNELS distinct channels per call.  GC_E_INVALID for two blocks of one channel that overlap, a dst record that
+ * differs from src's in device, sample count, dtype or layout (or overlaps it without being it), an unknown mode, a non-finite amp_in
+ * of an arm the block's channel has, null src, dst, or blocks with nblocks > 0; GC_E_RANGE / GC_E_STATE as gc_correlate (GC_E_STATE
+ * also for a dst without a record).  A refused call writes nothing.  nblocks == 0 is GC_OK: a plain copy (SUBTRACT) or zeros (MODEL). */
+#define GC_CANCEL_MAX_CHANNELS 64
+enum gc_cancel_mode { GC_CANCEL_SUBTRACT = 0, GC_CANCEL_MODEL = 1 };
+int gc_cancel(gc_context* src, gc_context* dst, int nblocks, const gc_block* blocks,
+              const double* amp_in  /* [nblocks][GC_MAX_ARMS][2] or NULL */,
+              double* amp_out       /* same layout, or NULL */, int mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,10 @@
  *          of the record, samples in file order (gc_probe_psd): P nfft x nspans, bin 1 = DC; K the Welch segments per span
  *   [counts, maxNorm2] = gnsscorr_mex('probe_histogram', h, firstSample0, nSamples)   % hist(., -128:128) of both components in file
  *          order (gc_probe_histogram): counts 257 x 2 uint64 (column 2 all zero for a real record); dmax = sqrt(maxNorm2) + 1
+ *   amp  = gnsscorr_mex('cancel', hSrc, hDst, blocks[, amp[, modelOnly]])             % the component every block describes taken out of
+ *          hSrc's record into hDst's (hDst == hSrc: in place; gc_cancel): blocks as for 'correlate' (earlyLateSpc ignored); amp
+ *          2 x GC_MAX_ARMS x nblocks doubles (re; im), [] = the record's own projection; modelOnly ~= 0 writes the components alone;
+ *          returns the amplitudes used in the same layout
  *   n    = gnsscorr_mex('device_count')                                              % HIP devices visible: one context per device
  *   prev = gnsscorr_mex('set_precision', h, 'double'|'single')                    % float64 correlations for every later correlate /
  *          track call of this context (gc_set_precision), 'single' = the float32 kernels (default); returns the previous setting
@@ -692,6 +696,24 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
     if (rc) fail("gc_probe_histogram");
     if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)m);
+  } else if (!strcmp(cmd, "cancel")) {
+    /* amp = gnsscorr_mex('cancel', hSrc, hDst, blocks[, amp[, modelOnly]]): gc_cancel's amp_out as it lies in memory, (re|im, arm, block) */
+    if (nrhs < 4) mexErrMsgIdAndTxt("gnsscorr:usage", "cancel: hSrc, hDst, blocks 8 x nblocks[, amp[, modelOnly]]");
+    int n = 0;
+    gc_block* blk = blocks_from(prhs[3], &n);
+    const double* amp_in = NULL;
+    if (nrhs > 4 && mxGetNumberOfElements(prhs[4]) > 0) {
+      if (!mxIsDouble(prhs[4]) || mxGetNumberOfElements(prhs[4]) != (size_t)2 * GC_MAX_ARMS * (size_t)n)
+        mexErrMsgIdAndTxt("gnsscorr:usage", "cancel: amp must be 2 x %d x nblocks doubles or []", GC_MAX_ARMS);
+      amp_in = mxGetDoubles(prhs[4]);
+    }
+    const int mode = nrhs > 5 && mxGetScalar(prhs[5]) != 0 ? GC_CANCEL_MODEL : GC_CANCEL_SUBTRACT;
+    const mwSize dims[3] = {2, (mwSize)GC_MAX_ARMS, (mwSize)n};
+    plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+    int rc = gc_cancel(handle(prhs[1]), handle(prhs[2]), n, blk, amp_in, mxGetDoubles(plhs[0]), mode);
+    mxFree(blk);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
+    if (rc) fail("gc_cancel");
   } else if (!strcmp(cmd, "device_count")) {
     int n = 0;
     if (gc_device_count(&n)) fail("gc_device_count");
