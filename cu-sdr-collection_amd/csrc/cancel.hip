@@ -1,7 +1,6 @@
 // cancel.hip — gc_cancel: the tracked components of a record rebuilt from their block descriptors and subtracted sample by sample
-// (include/gnsscorr.h has the definition).  The replica is corr_f64.hip's prompt tap restated: the reference's float64 colon element,
-// ceil(t * arm_mult) + table_offset clamped to the table, trig = (carrFreq * 2 * pi) * (i / fs) + remCarrPhase and float64 sincos of
-// trig itself; every operation rounded by itself (this unit is compiled without contraction, build.py NO_CONTRACT).
+// (include/gnsscorr.h has the definition).  The replica is corr_f64.hip's prompt tap, by the same functions (replica_f64.h): the
+// reference's float64 colon element, its table index, the carrier's angle and float64 sincos of it, every operation rounded by itself.
 //
 // Host: validates everything before anything is written, groups the blocks by channel (ascending channel index: the order the model
 // is added in), sorts each group by first_sample, refuses overlaps inside a group, uploads the sorted descriptors, their starts and
@@ -18,6 +17,7 @@
 #include <cmath>
 
 #include "corr_common.h"
+#include "replica_f64.h"
 
 using namespace gcorr;
 
@@ -42,66 +42,18 @@ struct CancelState {  // grow-only device buffers of the context (released by gc
   GcBuf blocks, starts, chans, prefix, part_p, part_e, amp;
 };
 
-// What a block's samples share: the prompt ramp's ends and step, the carrier's rate and phase (corr_f64.hip f64_accumulate, tap 1)
+// What a block's samples share: corr_f64.hip's prompt tap - the same functions (replica_f64.h)
 struct BlockRamp {
-  double a, b, sp, w, rc;
-  int N;
+  Ramp64 code;
+  Carrier64 carr;
 };
 
 __device__ __forceinline__ BlockRamp block_ramp(const gc_block& blk, double R) {
-  const double kPi = 3.141592653589793;
-  BlockRamp k;
-  k.N = blk.blksize;
-  k.sp = __dmul_rn(blk.code_phase_step, R);
-  k.a = __dmul_rn(blk.rem_code_phase, R);
-  k.b = __dmul_rn(__dadd_rn(__dmul_rn((double)(k.N - 1), blk.code_phase_step), blk.rem_code_phase), R);
-  k.w = __dmul_rn(__dmul_rn(blk.carr_freq, 2.0), kPi);
-  k.rc = blk.rem_carr_phase;
-  return k;
-}
-
-// element i of colon(a, sp, b): from the start below the middle, from the end above it, the mean of both ends in the middle
-__device__ __forceinline__ double ramp_at(const BlockRamp& k, int i) {
-  if (2 * i < k.N - 1) return __dadd_rn(k.a, __dmul_rn((double)i, k.sp));
-  if (2 * i > k.N - 1) return __dadd_rn(k.b, -__dmul_rn((double)(k.N - 1 - i), k.sp));
-  return __dadd_rn(k.a, k.b) / 2.0;
-}
-
-__device__ __forceinline__ void carrier_at(const BlockRamp& k, int i, double fs, double& sn, double& cs) {
-  sincos(__dadd_rn(__dmul_rn(k.w, __ddiv_rn((double)i, fs)), k.rc), &sn, &cs);
+  return {ramp64(blk.rem_code_phase, 0.0, blk.code_phase_step, R, blk.blksize), carrier64(blk.carr_freq, blk.rem_carr_phase)};
 }
 
 __device__ __forceinline__ double code_at(const CancelChan& ch, const gc_block& blk, int arm, double t) {
-  const int k = (int)ceil(__dmul_rn(t, ch.mult[arm])) + blk.table_offset[arm];
-  return (double)ch.tab[arm][min(max(k, 0), ch.last[arm])];
-}
-
-template <int MODE>
-struct Fmt {
-  static constexpr int ES = (MODE == I16_IQ || MODE == I16_QI || MODE == I16_REAL) ? 2 : 1;  // bytes per value
-  static constexpr int NC = (MODE == I8_REAL || MODE == I16_REAL) ? 1 : 2;                   // values per sample
-  static constexpr int BPS = ES * NC;
-  static constexpr int V = 16 / BPS;  // samples per 16 bytes
-  static constexpr bool SWAP = MODE == I8_QI || MODE == I16_QI;
-  static constexpr double LO = ES == 2 ? -32768.0 : -128.0, HI = ES == 2 ? 32767.0 : 127.0;
-};
-
-// One sample of the record as (re, im), corr_f64.hip's load_sample
-template <int MODE>
-__device__ __forceinline__ void load_sample(const uint8_t* __restrict__ base, long long idx, double& re, double& im) {
-  using F = Fmt<MODE>;
-  double c0, c1 = 0.0;
-  if constexpr (F::ES == 1) {
-    const signed char* s = (const signed char*)base + (long long)F::NC * idx;
-    c0 = (double)s[0];
-    if constexpr (F::NC == 2) c1 = (double)s[1];
-  } else {
-    const short* s = (const short*)base + (long long)F::NC * idx;
-    c0 = (double)s[0];
-    if constexpr (F::NC == 2) c1 = (double)s[1];
-  }
-  re = F::SWAP ? c1 : c0;
-  im = F::NC == 1 ? 0.0 : F::SWAP ? c0 : c1;
+  return (double)ch.tab[arm][code_index(t, ch.mult[arm], blk.table_offset[arm], ch.last[arm])];
 }
 
 struct ProjectArgs {
@@ -130,19 +82,18 @@ __global__ __launch_bounds__(kCancelWG) void cancel_project_kernel(const Project
   const gc_block blk = p.blocks[lo];
   const CancelChan ch = p.chans[blk.reserved];
   const BlockRamp k = block_ramp(blk, ch.R);
-  const int i_beg = (int)(g - p.prefix[lo]) * kCancelChunk, i_end = min(k.N, i_beg + kCancelChunk);
+  const int i_beg = (int)(g - p.prefix[lo]) * kCancelChunk, i_end = min(blk.blksize, i_beg + kCancelChunk);
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double acc[2 * GC_MAX_ARMS];
   int e[GC_MAX_ARMS];
 #pragma unroll
   for (int a = 0; a < GC_MAX_ARMS; ++a) acc[2 * a] = acc[2 * a + 1] = 0.0, e[a] = 0;
   for (int i = i_beg + tid; i < i_end; i += kCancelWG) {
-    double re, im, sn, cs;
-    load_sample<MODE>(p.if_base, blk.first_sample + i, re, im);
-    carrier_at(k, i, p.fs, sn, cs);
-    const double ib = __dadd_rn(__dmul_rn(cs, re), __dmul_rn(sn, im));
-    const double qb = __dadd_rn(__dmul_rn(cs, im), -__dmul_rn(sn, re));
-    const double t = ramp_at(k, i);
+    double re, im, sn, cs, ib, qb;
+    record_sample<MODE>(p.if_base, blk.first_sample + i, re, im);
+    k.carr.at(i, p.fs, sn, cs);
+    wipe_off(sn, cs, re, im, ib, qb);
+    const double t = k.code.at(i);
 #pragma unroll
     for (int a = 0; a < GC_MAX_ARMS; ++a)
       if (a < ch.arms) {
@@ -221,11 +172,11 @@ __global__ __launch_bounds__(kCancelWG) void cancel_apply_kernel(const ApplyArgs
     for (int i = (int)threadIdx.x; i < words; i += kCancelWG) s[i] = g[i];
   }
   __syncthreads();
-  const long long nvec = (p.nsamples + F::V - 1) / F::V;
+  const long long nvec = (p.nsamples + F::per16 - 1) / F::per16;
   for (long long v = (long long)blockIdx.x * kCancelWG + threadIdx.x; v < nvec; v += (long long)gridDim.x * kCancelWG) {
-    const long long n0 = v * F::V;
-    const int cnt = (int)min((long long)F::V, p.nsamples - n0);
-    const bool whole = p.vec_ok && cnt == F::V;
+    const long long n0 = v * F::per16;
+    const int cnt = (int)min((long long)F::per16, p.nsamples - n0);
+    const bool whole = p.vec_ok && cnt == F::per16;
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     if (whole) {
       const uint4 q = *(const uint4*)(p.src + v * 16);
@@ -234,16 +185,16 @@ __global__ __launch_bounds__(kCancelWG) void cancel_apply_kernel(const ApplyArgs
       const uint8_t* s = p.src + v * 16;
 #pragma unroll
       for (int k = 0; k < 16; ++k)
-        if (k < cnt * F::BPS) w[k >> 2] |= (uint32_t)s[k] << (8 * (k & 3));
+        if (k < cnt * F::bps) w[k >> 2] |= (uint32_t)s[k] << (8 * (k & 3));
     }
 #pragma unroll 1
     for (int s = 0; s < cnt; ++s) {
       const long long n = n0 + s;
-      const int bit = s * F::BPS * 8, word = bit >> 5, sh = bit & 31;
+      const int bit = s * F::bps * 8, word = bit >> 5, sh = bit & 31;
       const uint32_t raw = pick_word(w, word) >> sh;
-      const int v0 = F::ES == 1 ? (int)(signed char)(raw & 0xffu) : (int)(short)(raw & 0xffffu);
-      const int v1 = F::NC == 1 ? 0 : F::ES == 1 ? (int)(signed char)((raw >> 8) & 0xffu) : (int)(short)(raw >> 16);
-      const double x_re = (double)(F::SWAP ? v1 : v0), x_im = (double)(F::SWAP ? v0 : v1);
+      const int v0 = F::value_bytes == 1 ? (int)(signed char)(raw & 0xffu) : (int)(short)(raw & 0xffffu);
+      const int v1 = F::values == 1 ? 0 : F::value_bytes == 1 ? (int)(signed char)((raw >> 8) & 0xffu) : (int)(short)(raw >> 16);
+      const double x_re = (double)(F::swap ? v1 : v0), x_im = (double)(F::swap ? v0 : v1);
       double m_re = 0.0, m_im = 0.0;
       for (int c = 0; c < p.nchan; ++c) {
         const CancelChan& ch = sch[c];
@@ -266,8 +217,8 @@ __global__ __launch_bounds__(kCancelWG) void cancel_apply_kernel(const ApplyArgs
         const BlockRamp k = block_ramp(blk, ch.R);
         const int i = (int)(n - sj);
         double sn, cs;
-        carrier_at(k, i, p.fs, sn, cs);
-        const double t = ramp_at(k, i);
+        k.carr.at(i, p.fs, sn, cs);
+        const double t = k.code.at(i);
         const double* A = p.amp + (long long)(ch.first + j) * (2 * GC_MAX_ARMS);
         double b_re = 0.0, b_im = 0.0;
 #pragma unroll
@@ -278,19 +229,19 @@ __global__ __launch_bounds__(kCancelWG) void cancel_apply_kernel(const ApplyArgs
             b_re = __dadd_rn(b_re, __dmul_rn(cc, __dadd_rn(__dmul_rn(ar, cs), -__dmul_rn(ai, sn))));
             b_im = __dadd_rn(b_im, __dmul_rn(cc, __dadd_rn(__dmul_rn(ar, sn), __dmul_rn(ai, cs))));
           }
-        if constexpr (F::NC == 1) b_re = __dmul_rn(2.0, b_re);  // a real record holds half of the phasor
+        if constexpr (F::values == 1) b_re = __dmul_rn(2.0, b_re);  // a real record holds half of the phasor
         m_re = __dadd_rn(m_re, b_re);
         m_im = __dadd_rn(m_im, b_im);
       }
       const double y_re = p.mode == GC_CANCEL_MODEL ? m_re : __dadd_rn(x_re, -m_re);
       const double y_im = p.mode == GC_CANCEL_MODEL ? m_im : __dadd_rn(x_im, -m_im);
-      const int o_re = (int)fmin(fmax(rint(y_re), F::LO), F::HI);
-      const int o_im = (int)fmin(fmax(rint(y_im), F::LO), F::HI);
-      const int o0 = F::SWAP ? o_im : o_re, o1 = F::SWAP ? o_re : o_im;
-      constexpr uint32_t vmask = F::ES == 1 ? 0xffu : 0xffffu;
-      constexpr uint32_t smask = F::BPS == 4 ? 0xffffffffu : (1u << (F::BPS * 8 % 32)) - 1u;
+      const int o_re = (int)fmin(fmax(rint(y_re), F::lo), F::hi);
+      const int o_im = (int)fmin(fmax(rint(y_im), F::lo), F::hi);
+      const int o0 = F::swap ? o_im : o_re, o1 = F::swap ? o_re : o_im;
+      constexpr uint32_t vmask = F::value_bytes == 1 ? 0xffu : 0xffffu;
+      constexpr uint32_t smask = F::bps == 4 ? 0xffffffffu : (1u << (F::bps * 8 % 32)) - 1u;
       uint32_t bits = (uint32_t)o0 & vmask;
-      if constexpr (F::NC == 2) bits |= ((uint32_t)o1 & vmask) << (8 * F::ES);
+      if constexpr (F::values == 2) bits |= ((uint32_t)o1 & vmask) << (8 * F::value_bytes);
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         if (q == word) w[q] = (w[q] & ~(smask << sh)) | (bits << sh);
@@ -301,38 +252,21 @@ __global__ __launch_bounds__(kCancelWG) void cancel_apply_kernel(const ApplyArgs
       uint8_t* o = p.dst + v * 16;
 #pragma unroll
       for (int k = 0; k < 16; ++k)
-        if (k < cnt * F::BPS) o[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+        if (k < cnt * F::bps) o[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
     }
   }
 }
 
-int record_mode(const gc_context* ctx) {
-  if (ctx->if_dtype == GC_I8) return ctx->if_layout == GC_IQ ? I8_IQ : ctx->if_layout == GC_QI ? I8_QI : I8_REAL;
-  return ctx->if_layout == GC_IQ ? I16_IQ : ctx->if_layout == GC_QI ? I16_QI : I16_REAL;
-}
-
 void launch_project(gc_context* ctx, long long chunks, const ProjectArgs& a) {
-  const dim3 grid((unsigned int)chunks), block(kCancelWG);
-  switch (record_mode(ctx)) {
-    case I8_IQ: hipLaunchKernelGGL(cancel_project_kernel<I8_IQ>, grid, block, 0, ctx->stream, a); break;
-    case I8_QI: hipLaunchKernelGGL(cancel_project_kernel<I8_QI>, grid, block, 0, ctx->stream, a); break;
-    case I16_IQ: hipLaunchKernelGGL(cancel_project_kernel<I16_IQ>, grid, block, 0, ctx->stream, a); break;
-    case I16_QI: hipLaunchKernelGGL(cancel_project_kernel<I16_QI>, grid, block, 0, ctx->stream, a); break;
-    case I8_REAL: hipLaunchKernelGGL(cancel_project_kernel<I8_REAL>, grid, block, 0, ctx->stream, a); break;
-    default: hipLaunchKernelGGL(cancel_project_kernel<I16_REAL>, grid, block, 0, ctx->stream, a); break;
-  }
+  gc_with_mode(gc_record_mode(ctx), [&](auto m) {
+    hipLaunchKernelGGL(cancel_project_kernel<decltype(m)::value>, dim3((unsigned int)chunks), dim3(kCancelWG), 0, ctx->stream, a);
+  });
 }
 
 void launch_apply(gc_context* ctx, unsigned int wgs, const ApplyArgs& a) {
-  const dim3 grid(wgs), block(kCancelWG);
-  switch (record_mode(ctx)) {
-    case I8_IQ: hipLaunchKernelGGL(cancel_apply_kernel<I8_IQ>, grid, block, 0, ctx->stream, a); break;
-    case I8_QI: hipLaunchKernelGGL(cancel_apply_kernel<I8_QI>, grid, block, 0, ctx->stream, a); break;
-    case I16_IQ: hipLaunchKernelGGL(cancel_apply_kernel<I16_IQ>, grid, block, 0, ctx->stream, a); break;
-    case I16_QI: hipLaunchKernelGGL(cancel_apply_kernel<I16_QI>, grid, block, 0, ctx->stream, a); break;
-    case I8_REAL: hipLaunchKernelGGL(cancel_apply_kernel<I8_REAL>, grid, block, 0, ctx->stream, a); break;
-    default: hipLaunchKernelGGL(cancel_apply_kernel<I16_REAL>, grid, block, 0, ctx->stream, a); break;
-  }
+  gc_with_mode(gc_record_mode(ctx), [&](auto m) {
+    hipLaunchKernelGGL(cancel_apply_kernel<decltype(m)::value>, dim3(wgs), dim3(kCancelWG), 0, ctx->stream, a);
+  });
 }
 
 // What gc_correlate asks of a descriptor (launch_plan.h gc_scope_from_blocks) with el_spacing taken as 0

@@ -40,6 +40,7 @@
 #include <cstring>
 
 #include "bank_plan.h"
+#include "replica_f64.h"
 
 using namespace gcorr;
 
@@ -56,59 +57,22 @@ constexpr int kBankWG = 256;      // threads per workgroup: kBankChunk / kBankWG
 constexpr int kBankSPT = kBankChunk / kBankWG;
 constexpr int kBankWaves = kBankWG / 64;
 
-template <int MODE>
-__device__ __forceinline__ void bank_load_sample(const uint8_t* __restrict__ base, long long idx, float& a, float& b) {
-  float x0, x1;
-  if constexpr (MODE == I8_IQ || MODE == I8_QI) {
-    const unsigned int w = *(const unsigned short*)(base + 2 * idx);  // one 16-bit load per sample
-    x0 = (float)(signed char)(w & 0xffu);
-    x1 = (float)(signed char)(w >> 8);
-  } else if constexpr (MODE == I16_IQ || MODE == I16_QI) {
-    const short* s = (const short*)base + 2 * idx;
-    x0 = (float)s[0];
-    x1 = (float)s[1];
-  } else if constexpr (MODE == I8_REAL) {
-    x0 = (float)((const signed char*)base)[idx];
-    x1 = 0.0f;
-  } else {
-    x0 = (float)((const short*)base)[idx];
-    x1 = 0.0f;
-  }
-  a = Fmt<MODE>::swap ? x1 : x0;
-  b = Fmt<MODE>::swap ? x0 : x1;
-}
-
-// One (arm, tap) ramp of a block: the reference's colon element i and its table index.
+// One (arm, tap) ramp of a block: the reference's colon element i and its table index (replica_f64.h).
 struct BankRamp {
-  double a, b, sp, m;
-  int N;
-  __device__ __forceinline__ int index(int i) const {
-    const int back = N - 1 - i;
-    double t;
-    if (i < back)
-      t = __dadd_rn(a, __dmul_rn((double)i, sp));
-    else if (i > back)
-      t = __dadd_rn(b, -__dmul_rn((double)back, sp));
-    else
-      t = __dadd_rn(a, b) / 2.0;
-    return (int)ceil(__dmul_rn(t, m));
-  }
+  Ramp64 r;
+  double m;
+  __device__ __forceinline__ int index(int i) const { return code_step(r.at(i), m); }
   // e(k): the smallest sample of the chunk [i0, i_last] whose index is >= k, for index(i0) < k <= index(i_last) - it lies in
   // (i0, i_last].  A candidate from a float64 division, corrected with the element rule itself: down while sample e - 1 already
   // has index >= k, up while sample e has index < k.
   __device__ __forceinline__ int boundary(int k, int i0, int i_last) const {
-    const double x = ((double)(k - 1) / m - a) / sp;
+    const double x = ((double)(k - 1) / m - r.a) / r.sp;
     int e = (int)fmin(fmax(floor(x) + 1.0, (double)(i0 + 1)), (double)i_last);
     while (e > i0 + 1 && index(e - 1) >= k) --e;
     while (e < i_last && index(e) < k) ++e;
     return e;
   }
 };
-
-int bank_record_mode(const gc_context* ctx) {
-  if (ctx->if_dtype == GC_I8) return ctx->if_layout == GC_IQ ? I8_IQ : ctx->if_layout == GC_QI ? I8_QI : I8_REAL;
-  return ctx->if_layout == GC_IQ ? I16_IQ : ctx->if_layout == GC_QI ? I16_QI : I16_REAL;
-}
 
 constexpr int kDdmGroup = GC_DDM_GROUP;
 static_assert(kDdmGroup >= 1 && kDdmGroup * (kBankChunk + 1) * 8 + kDdmGroup * kBankWaves * 8 <= 160 * 1024, "a workgroup's LDS");
@@ -161,7 +125,7 @@ __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
     const int li = kBankSPT * tid + q;
     xa[q] = 0.0f;
     xb[q] = 0.0f;
-    if (li < n) bank_load_sample<MODE>(p.if_base, blk.first_sample + i0 + li, xa[q], xb[q]);
+    if (li < n) record_sample<MODE>(p.if_base, blk.first_sample + i0 + li, xa[q], xb[q]);
   }
   const double ph0 = blk.rem_carr_phase * 0.15915494309189535;
   float2 s[G][kBankSPT];
@@ -220,18 +184,11 @@ __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
   // ---- phase B: a wavefront per (arm, tap) pair, a lane per table entry the chunk crosses; every boundary once for the group ----
   const int arms = chn->arms;
   const double R = chn->index_scale, rem = blk.rem_code_phase, step = blk.code_phase_step;
-  const double nm1s = __dmul_rn((double)(N - 1), step);
   const int i_last = i0 + n - 1;
   double* __restrict__ prow = p.partial + (long long)item * p.arms * p.nfreq * p.ntaps * 2;
   for (int pair = wave; pair < arms * p.ntaps; pair += kBankWaves) {
     const int arm = pair / p.ntaps, j = pair - arm * p.ntaps;
-    const double o = p.offsets[j];
-    BankRamp rp;
-    rp.a = __dmul_rn(__dadd_rn(rem, o), R);
-    rp.b = __dmul_rn(__dadd_rn(__dadd_rn(nm1s, rem), o), R);
-    rp.sp = __dmul_rn(step, R);
-    rp.m = chn->mult[arm];
-    rp.N = N;
+    const BankRamp rp = {ramp64(rem, p.offsets[j], step, R, N), chn->mult[arm]};
     const int8_t* __restrict__ tab = chn->tab[arm];
     const int L = chn->nent[arm] - 2;  // the code's period in entries
     const int k_lo = rp.index(i0), k_hi = rp.index(i_last);
@@ -295,14 +252,9 @@ __global__ void bank_combine_kernel(const BankArgs p) {
 template <int G>
 int bank_launch_chunks(gc_context* ctx, const BankArgs& a, int total_chunks) {
   const dim3 grid((unsigned int)total_chunks, (unsigned int)((a.nfreq + G - 1) / G)), block(kBankWG);
-  switch (bank_record_mode(ctx)) {
-    case I8_IQ: hipLaunchKernelGGL((bank_chunk_kernel<I8_IQ, G>), grid, block, 0, ctx->stream, a); break;
-    case I8_QI: hipLaunchKernelGGL((bank_chunk_kernel<I8_QI, G>), grid, block, 0, ctx->stream, a); break;
-    case I16_IQ: hipLaunchKernelGGL((bank_chunk_kernel<I16_IQ, G>), grid, block, 0, ctx->stream, a); break;
-    case I16_QI: hipLaunchKernelGGL((bank_chunk_kernel<I16_QI, G>), grid, block, 0, ctx->stream, a); break;
-    case I8_REAL: hipLaunchKernelGGL((bank_chunk_kernel<I8_REAL, G>), grid, block, 0, ctx->stream, a); break;
-    default: hipLaunchKernelGGL((bank_chunk_kernel<I16_REAL, G>), grid, block, 0, ctx->stream, a); break;
-  }
+  gc_with_mode(gc_record_mode(ctx), [&](auto m) {
+    hipLaunchKernelGGL((bank_chunk_kernel<decltype(m)::value, G>), grid, block, 0, ctx->stream, a);
+  });
   GC_HIP(hipGetLastError());
   return GC_OK;
 }

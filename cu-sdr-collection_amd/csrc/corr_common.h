@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "gc_internal.h"
+#include "record_fmt.h"
 
 // NOTE: the correlator translation units are compiled with -ffp-contract=off (build.py explains why): write
 // wanted FMAs as fmaf() / fma().
@@ -11,8 +12,6 @@ namespace gcorr {
 
 constexpr int kWG = 256;
 constexpr int kSPL = 8;  // samples per lane-chunk
-
-enum Mode { I8_IQ = 0, I8_QI, I16_IQ, I16_QI, I8_REAL, I16_REAL };
 
 constexpr int kInlineBlocks = 16;
 constexpr int kGuard = 16;  // zero entries on both sides of the generic kernel's staged f16 tables
@@ -158,12 +157,6 @@ __device__ __forceinline__ void load_chunk(const uint8_t* __restrict__ base, lon
     }
   }
 }
-
-template <int MODE>
-struct Fmt {
-  static constexpr int bps = (MODE == I8_IQ || MODE == I8_QI || MODE == I16_REAL) ? 2 : (MODE == I8_REAL) ? 1 : 4;
-  static constexpr bool swap = (MODE == I8_QI || MODE == I16_QI);
-};
 
 template <int MODE, int SPL>
 __device__ __forceinline__ void load_words(const uint8_t* __restrict__ base, long long q,

@@ -470,6 +470,7 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
             for (int x = 0; x < 3; ++x) {
               const double ax = (x == 0) ? aE : (x == 1) ? aP : aL;
               const double bx = (x == 0) ? bE : (x == 1) ? bP : bL;
+              // replica_f64.h colon_at / code_step define this rule; restated here: this kernel's registers are tuned around these lines
               double t;
               if (2 * i < Nq - 1)
                 t = __dadd_rn(ax, __dmul_rn((double)i, sp));
@@ -796,19 +797,10 @@ void launch_variant(gc_context* ctx, const KArgs& a, const InlineBlocks& ib, dim
 
 template <int ARMS, int SPL>
 int launch_fast_mode(gc_context* ctx, const KArgs& a, const InlineBlocks& ib, dim3 grid, size_t smem) {
-  int mode;
-  if (ctx->if_dtype == GC_I8)
-    mode = ctx->if_layout == GC_IQ ? I8_IQ : ctx->if_layout == GC_QI ? I8_QI : I8_REAL;
-  else
-    mode = ctx->if_layout == GC_IQ ? I16_IQ : ctx->if_layout == GC_QI ? I16_QI : I16_REAL;
-  switch (mode) {
-    case I8_IQ: launch_variant<ARMS, I8_IQ, SPL>(ctx, a, ib, grid, smem); break;
-    case I8_QI: launch_variant<ARMS, I8_QI, SPL>(ctx, a, ib, grid, smem); break;
-    case I16_IQ: launch_variant<ARMS, I16_IQ, 8>(ctx, a, ib, grid, smem); break;
-    case I16_QI: launch_variant<ARMS, I16_QI, 8>(ctx, a, ib, grid, smem); break;
-    case I8_REAL: launch_variant<ARMS, I8_REAL, 8>(ctx, a, ib, grid, smem); break;
-    default: launch_variant<ARMS, I16_REAL, 8>(ctx, a, ib, grid, smem); break;
-  }
+  gc_with_mode(gc_record_mode(ctx), [&](auto m) {  // 16-sample chunks exist for int8 I/Q and Q/I records only
+    constexpr int MODE = decltype(m)::value;
+    launch_variant<ARMS, MODE, (MODE == I8_IQ || MODE == I8_QI) ? SPL : 8>(ctx, a, ib, grid, smem);
+  });
   GC_HIP(hipGetLastError());
   return GC_OK;
 }

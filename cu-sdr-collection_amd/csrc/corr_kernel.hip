@@ -2,6 +2,7 @@
 // for channels with mixed ramp multipliers, and the partial-sum combiner.  The two production kernels live in
 // corr_fast.hip (low chipping rates: at most one table transition per lane-chunk) and corr_lane.hip (any rate).
 #include "launch_plan.h"
+#include "replica_f64.h"
 
 using namespace gcorr;
 
@@ -23,11 +24,7 @@ __global__ __launch_bounds__(kWG) void corr_epl_mixed_kernel(const KArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const double R = chn->index_scale, rem = blk.rem_code_phase, step = blk.code_phase_step, d = blk.el_spacing;
   const int N = blk.blksize;
-  const double sp = step * R;
-  const double a3[3] = {(rem - d) * R, rem * R, (rem + d) * R};
-  const double nm1s = __dmul_rn((double)(N - 1), step);
-  const double b3[3] = {__dmul_rn(__dadd_rn(__dadd_rn(nm1s, rem), -d), R), __dmul_rn(__dadd_rn(nm1s, rem), R),
-                        __dmul_rn(__dadd_rn(__dadd_rn(nm1s, rem), d), R)};
+  const Ramp64 ramp[3] = {ramp64(rem, -d, step, R, N), ramp64(rem, 0.0, step, R, N), ramp64(rem, d, step, R, N)};  // early, prompt, late
   const double tau = blk.carr_freq / p.fs;
   const double ph0 = blk.rem_carr_phase * 0.15915494309189535;
   const int per = (N + p.splits - 1) / p.splits;
@@ -35,44 +32,18 @@ __global__ __launch_bounds__(kWG) void corr_epl_mixed_kernel(const KArgs p) {
   float acc[GC_OUT_STRIDE];
 #pragma unroll
   for (int v = 0; v < GC_OUT_STRIDE; ++v) acc[v] = 0.f;
-  constexpr int bps = (MODE == I8_IQ || MODE == I8_QI || MODE == I16_REAL) ? 2 : (MODE == I8_REAL) ? 1 : 4;
   for (int i = i_beg + tid; i < i_end; i += kWG) {
-    const uint8_t* s = p.if_base + (size_t)(blk.first_sample + i) * bps;
     float a, b;
-    if (MODE == I8_IQ || MODE == I8_QI) {
-      a = (float)(signed char)s[0];
-      b = (float)(signed char)s[1];
-    } else if (MODE == I16_IQ || MODE == I16_QI) {
-      a = (float)((const short*)s)[0];
-      b = (float)((const short*)s)[1];
-    } else if (MODE == I8_REAL) {
-      a = (float)(signed char)s[0];
-      b = 0.f;
-    } else {
-      a = (float)((const short*)s)[0];
-      b = 0.f;
-    }
-    if (MODE == I8_QI || MODE == I16_QI) {
-      const float t = a;
-      a = b;
-      b = t;
-    }
+    record_sample<MODE>(p.if_base, blk.first_sample + i, a, b);
     const double ph = ph0 + (double)i * tau;
     float sn, cs;
     sincospif(2.0f * (float)(ph - floor(ph)), &sn, &cs);
     const float xr = a * cs + b * sn, xi = b * cs - a * sn;
 #pragma unroll
     for (int x = 0; x < 3; ++x) {
-      double t;
-      if (2 * i < N - 1)
-        t = __dadd_rn(a3[x], __dmul_rn((double)i, sp));
-      else if (2 * i > N - 1)
-        t = __dadd_rn(b3[x], -__dmul_rn((double)(N - 1 - i), sp));
-      else
-        t = __dadd_rn(a3[x], b3[x]) / 2.0;
+      const double t = ramp[x].at(i);
       for (int ar = 0; ar < arms; ++ar) {
-        const int k = (int)ceil(__dmul_rn(t, chn->mult[ar])) + blk.table_offset[ar];
-        const float c = (float)chn->tab[ar][min(max(k, 0), chn->nent[ar] - 1)];
+        const float c = (float)chn->tab[ar][code_index(t, chn->mult[ar], blk.table_offset[ar], chn->nent[ar] - 1)];
         acc[ar * 6 + 2 * x] = fmaf(c, xr, acc[ar * 6 + 2 * x]);
         acc[ar * 6 + 2 * x + 1] = fmaf(c, xi, acc[ar * 6 + 2 * x + 1]);
       }
@@ -154,19 +125,9 @@ int gc_launch_correlator(gc_context* ctx, const LaunchScope& s, const gc_block* 
     case 0: rc = gc_launch_correlator_lane(ctx, a, ib, s, plan); break;
     case -1: {  // mixed ramp multipliers: exact per-sample kernel
       const dim3 grid(plan.grid);
-      int mode;
-      if (ctx->if_dtype == GC_I8)
-        mode = ctx->if_layout == GC_IQ ? I8_IQ : ctx->if_layout == GC_QI ? I8_QI : I8_REAL;
-      else
-        mode = ctx->if_layout == GC_IQ ? I16_IQ : ctx->if_layout == GC_QI ? I16_QI : I16_REAL;
-      switch (mode) {
-        case I8_IQ: hipLaunchKernelGGL((corr_epl_mixed_kernel<I8_IQ>), grid, dim3(kWG), 0, ctx->stream, a); break;
-        case I8_QI: hipLaunchKernelGGL((corr_epl_mixed_kernel<I8_QI>), grid, dim3(kWG), 0, ctx->stream, a); break;
-        case I16_IQ: hipLaunchKernelGGL((corr_epl_mixed_kernel<I16_IQ>), grid, dim3(kWG), 0, ctx->stream, a); break;
-        case I16_QI: hipLaunchKernelGGL((corr_epl_mixed_kernel<I16_QI>), grid, dim3(kWG), 0, ctx->stream, a); break;
-        case I8_REAL: hipLaunchKernelGGL((corr_epl_mixed_kernel<I8_REAL>), grid, dim3(kWG), 0, ctx->stream, a); break;
-        default: hipLaunchKernelGGL((corr_epl_mixed_kernel<I16_REAL>), grid, dim3(kWG), 0, ctx->stream, a); break;
-      }
+      gc_with_mode(gc_record_mode(ctx), [&](auto m) {
+        hipLaunchKernelGGL((corr_epl_mixed_kernel<decltype(m)::value>), grid, dim3(kWG), 0, ctx->stream, a);
+      });
       rc = (hipGetLastError() == hipSuccess) ? GC_OK : GC_E_HIP;
       break;
     }

@@ -885,21 +885,11 @@ void launch_tab(gc_context* ctx, const KArgs& a, const InlineBlocks& ib, dim3 gr
   }
 }
 
-int record_mode(const gc_context* ctx) {
-  if (ctx->if_dtype == GC_I8) return ctx->if_layout == GC_IQ ? I8_IQ : ctx->if_layout == GC_QI ? I8_QI : I8_REAL;
-  return ctx->if_layout == GC_IQ ? I16_IQ : ctx->if_layout == GC_QI ? I16_QI : I16_REAL;
-}
-
 template <int ARMS>
 int launch_mode(gc_context* ctx, const KArgs& a, const InlineBlocks& ib, dim3 grid, size_t smem, int tabkind) {
-  switch (record_mode(ctx)) {
-    case I8_IQ: launch_tab<ARMS, I8_IQ>(ctx, a, ib, grid, smem, tabkind); break;
-    case I8_QI: launch_tab<ARMS, I8_QI>(ctx, a, ib, grid, smem, tabkind); break;
-    case I16_IQ: launch_tab<ARMS, I16_IQ>(ctx, a, ib, grid, smem, tabkind); break;
-    case I16_QI: launch_tab<ARMS, I16_QI>(ctx, a, ib, grid, smem, tabkind); break;
-    case I8_REAL: launch_tab<ARMS, I8_REAL>(ctx, a, ib, grid, smem, tabkind); break;
-    default: launch_tab<ARMS, I16_REAL>(ctx, a, ib, grid, smem, tabkind); break;
-  }
+  gc_with_mode(gc_record_mode(ctx), [&](auto m) {
+    launch_tab<ARMS, decltype(m)::value>(ctx, a, ib, grid, smem, tabkind);
+  });
   GC_HIP(hipGetLastError());
   return GC_OK;
 }
@@ -924,14 +914,9 @@ int launch_devloop_arms(gc_context* ctx, KArgs& a, const InlineBlocks& ib, dim3 
   if (half)
     return launch_persistent_fn(ctx, qi ? (const void*)corr_epl_lane_kernel<ARMS, I8_QI, false, 2, true> : (const void*)corr_epl_lane_kernel<ARMS, I8_IQ, false, 2, true>,
                                 a, ib, g, smem, waves);
-  switch (record_mode(ctx)) {
-    case I8_IQ: return launch_lane_devloop<ARMS, I8_IQ>(ctx, a, ib, g, smem, share_el, waves);
-    case I8_QI: return launch_lane_devloop<ARMS, I8_QI>(ctx, a, ib, g, smem, share_el, waves);
-    case I16_IQ: return launch_lane_devloop<ARMS, I16_IQ>(ctx, a, ib, g, smem, share_el, waves);
-    case I16_QI: return launch_lane_devloop<ARMS, I16_QI>(ctx, a, ib, g, smem, share_el, waves);
-    case I8_REAL: return launch_lane_devloop<ARMS, I8_REAL>(ctx, a, ib, g, smem, share_el, waves);
-    default: return launch_lane_devloop<ARMS, I16_REAL>(ctx, a, ib, g, smem, share_el, waves);
-  }
+  return gc_with_mode(gc_record_mode(ctx), [&](auto m) {
+    return launch_lane_devloop<ARMS, decltype(m)::value>(ctx, a, ib, g, smem, share_el, waves);
+  });
 }
 
 }  // namespace

@@ -282,6 +282,7 @@ __global__ __launch_bounds__(NWV* kMW) void corr_epl_multi_kernel(const KArgs p)
             for (int x = 0; x < 3; ++x) {
               const double ax = (x == 0) ? aE : (x == 1) ? aP : aL;
               const double bx = (x == 0) ? bE : (x == 1) ? bP : bL;
+              // replica_f64.h colon_at / code_step define this rule; restated here: this kernel's registers are tuned around these lines
               double t;
               if (2 * i < Nq - 1)
                 t = __dadd_rn(ax, __dmul_rn((double)i, sp));

@@ -18,6 +18,7 @@
 // the records, tests/loop_closure_shim.hip from a CPU test that replays the reference's recorded sums through it.
 #pragma once
 #include "gc_internal.h"
+#include "replica_f64.h"  // kPi
 
 namespace gcorr {
 
@@ -225,7 +226,6 @@ struct DevLoopPre {
 
 __host__ __device__ inline DevLoopPre devloop_pre(const DevLoopArgs* __restrict__ dl, const DevLoopChan& st, const gc_block& b, double R) {
   const gc_track_params& p = dl->prm;
-  const double kPi = 3.141592653589793;
   const int n = b.blksize;
   const double step = b.code_phase_step;
   DevLoopPre r;
@@ -243,7 +243,6 @@ __host__ __device__ inline int devloop_post(const DevLoopArgs* __restrict__ dl, 
   // rec(field, value) takes the epoch's record: straight to device memory (lane kernel) or into registers, to be stored by
   // devloop_commit AFTER the next descriptor is on its way (fast kernel)
   const gc_track_params& p = dl->prm;
-  const double kPi = 3.141592653589793;
   const int n = b.blksize;
   const double i_e = sums[0], q_e = sums[1], i_p = sums[2], q_p = sums[3], i_l = sums[4], q_l = sums[5];
   // do_cno: in an all-gather team every member runs this closure, ONE of them (not the one that writes the records) keeps the
