@@ -22,6 +22,7 @@ GC_WIN_RECT, GC_WIN_HAMMING = 0, 1   # gc_probe_window
 GC_PROBE_HIST_BINS = 257   # gc_probe_histogram: hist(x, -128:128)
 GC_CANCEL_MAX_CHANNELS = 64   # gc_cancel: distinct channels per call
 GC_CANCEL_SUBTRACT, GC_CANCEL_MODEL = 0, 1   # gc_cancel_mode
+GC_EXCISE_MAX_GUARD = 4096   # gc_excise_pulses: longest guard in front of and behind a hot sample
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -129,6 +130,21 @@ class gc_probe_psd_params(C.Structure):
                 ("window", C.c_int32), ("nspans", C.c_int32)]
 
 
+class gc_excise_pulse_params(C.Structure):
+    """gc_excise_pulses: sample n of the range is hot iff c0^2 + c1^2 > threshold2; a hot sample h blanks [h - before, h + after]."""
+    _fields_ = [("first_sample", C.c_int64), ("nsamples", C.c_int64), ("threshold2", C.c_int64), ("before", C.c_int32), ("after", C.c_int32)]
+
+
+class gc_excise_pulse_stats(C.Structure):
+    """gc_excise_pulses: hot samples, blanked samples (hot ones included), maximal runs of blanked samples, the longest run."""
+    _fields_ = [("hot", C.c_int64), ("blanked", C.c_int64), ("runs", C.c_int64), ("longest", C.c_int64)]
+
+
+class gc_excise_bins_params(C.Structure):
+    """gc_excise_bins: the range and the transform length (even, >= 4, 2^a 3^b 5^c with a plan); reserved is 0."""
+    _fields_ = [("first_sample", C.c_int64), ("nsamples", C.c_int64), ("nfft", C.c_int32), ("reserved", C.c_int32)]
+
+
 class gc_acq_result(C.Structure):
     _fields_ = [("coarse_bin", C.c_int32), ("code_phase", C.c_int32), ("peak", C.c_double),
                 ("peak_metric", C.c_double), ("coarse_freq", C.c_double)]
@@ -228,6 +244,9 @@ SYMBOLS = {
     "gc_probe_histogram": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "gc_debug_probe_tile_segments": (C.c_longlong, [C.c_int]),
     "gc_cancel": (C.c_int, [_P, _P, C.c_int, C.POINTER(gc_block), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
+    "gc_excise_pulses": (C.c_int, [_P, _P, C.POINTER(gc_excise_pulse_params), C.POINTER(gc_excise_pulse_stats)]),
+    "gc_excise_bins": (C.c_int, [_P, _P, C.POINTER(gc_excise_bins_params), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "gc_debug_excise_tile_segments": (C.c_longlong, [C.c_int]),
 }
 
 _lib = None

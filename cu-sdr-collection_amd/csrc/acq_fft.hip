@@ -1579,6 +1579,36 @@ int forward(gc_context* ctx, AcqScratch* s, PassArgs base, int pre, long long nb
   a.out_batch_stride = pl.n;
   return launch_pass(ctx, a, nbatch);
 }
+
+int transform_rows(gc_context* ctx, const Plan& pl, const float2* tw, float2* a_rows, float2* b_rows, long long nbatch, int inverse) {
+  PassArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.n = pl.n;
+  a.tw = tw;
+  a.inverse = inverse;
+  fill_sub(a, pl.p1);
+  a.nvec = pl.n2;
+  a.estride = pl.n2;
+  a.vstride = 1;
+  a.cols = choose_cols(a.len, a.estride);
+  a.pre = PRE_NONE;
+  a.post = POST_TWIDDLE;
+  a.in = a_rows;
+  a.in_batch_stride = pl.n;
+  a.out = b_rows;
+  a.out_batch_stride = pl.n;
+  int rc = launch_pass(ctx, a, nbatch);
+  if (rc) return rc;
+  fill_sub(a, pl.p2);
+  a.nvec = pl.n1;
+  a.estride = 1;
+  a.vstride = pl.n2;
+  a.cols = choose_cols(a.len, a.estride);
+  a.post = POST_STORE;
+  a.in = b_rows;
+  a.out = a_rows;
+  return launch_pass(ctx, a, nbatch);
+}
 }  // namespace gcacq
 
 // Test hook: forward FFT of `nbatch` host sequences of length n (complex64) with the library's

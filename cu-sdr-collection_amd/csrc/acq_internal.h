@@ -318,6 +318,10 @@ int launch_pass(gc_context* ctx, PassArgs& a, long long nbatch_groups, bool* use
 int handover_block(const Plan& pl);
 void fill_sub(PassArgs& a, const SubPlan& sp);
 int choose_cols(int L, int estride = 1);
+// Transform of `nbatch` rows of a (natural order, pl.n values each) in place, b the intermediate, with the twiddle table tw of pl.n
+// entries; the result in storage order [k1][k2] (natural index k1 + n1 k2).  The two launches of gc_debug_fft: columns with
+// PRE_NONE / POST_TWIDDLE, rows with PRE_NONE / POST_STORE; inverse = 1 is the unnormalised inverse.  Shared by probe.hip and excise.hip.
+int transform_rows(gc_context* ctx, const Plan& pl, const float2* tw, float2* a_rows, float2* b_rows, long long nbatch, int inverse);
 // Forward transform of `nbatch` sequences produced by `pre` into `dst` (layout [k1][k2])
 int forward(gc_context* ctx, AcqScratch* s, PassArgs base, int pre, long long nbatch, float2* dst);
 // GC_ACQ_FUSED (tuning build): the whole inverse side of a 36 000- / 24 000-point search in one launch; false: no fused kernel for this plan

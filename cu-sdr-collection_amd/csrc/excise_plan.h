@@ -1,0 +1,163 @@
+// excise_plan.h — what the drivers of the excision (excise.hip: gc_excise_pulses, gc_excise_bins) decide on the host, from integers:
+// the argument checks; how the blanker's range is laid over the hot-sample bitmap and cut into the tiles its kernels take one workgroup
+// each; the segment count of the spectral excision and the cut of its segment list into tiles whose rows fit a byte budget.  Nothing
+// here calls HIP, allocates on the device or launches; tests/excise_plan_shim.hip runs all of it without a device.  From the two
+// contexts the checks read d_if, device, if_nsamples, if_dtype and if_layout.  The one refusal that is not decided here is the
+// transform planner's (make_plan, acq_fft.hip: GC_E_UNSUPPORTED).
+#pragma once
+#include <cstdint>
+
+#include "gc_internal.h"
+
+constexpr int kExciseTile = 16384;                          // samples of the bitmap per workgroup of the mark and the blank kernel
+constexpr int kExciseTileWords = kExciseTile / 64;          // 64 samples per bitmap word
+constexpr int kExciseHalo = GC_EXCISE_MAX_GUARD / 64;       // zero words in front of the first tile and behind the last: the longest guard
+static_assert(GC_EXCISE_MAX_GUARD % 64 == 0 && kExciseTile % 64 == 0, "whole bitmap words");
+
+// Bit b of the bitmap is record sample base + b; base is a multiple of 64 at or below first_sample, so every 16 bytes of the record
+// (4, 8 or 16 samples) lie in one word and a tile begins on a 16-byte boundary of the record.  Bits of samples outside the range, and
+// beyond the record, are zero: only the samples of the range are examined.
+struct ExcisePulsePlan {
+  long long base = 0;    // record sample of bit 0
+  long long ntiles = 0;  // tiles that cover [base, first_sample + nsamples)
+  long long words = 0;   // of the bitmap: kExciseHalo + ntiles * kExciseTileWords + kExciseHalo + 1 (the blank kernel's last prefix count reads one word past the halo)
+  int bps = 0;           // bytes per sample
+};
+
+inline int excise_bytes_per_sample(const gc_context* c) { return (c->if_dtype == GC_I16 ? 2 : 1) * (c->if_layout == GC_REAL ? 1 : 2); }
+
+// What gc_cancel asks of its two records, in its order: GC_E_STATE without a record, GC_E_INVALID for a destination that differs from
+// the source in device, sample count, dtype or layout, or overlaps it without being it
+inline int excise_check_records(const char* fn, const gc_context* src, const gc_context* dst) {
+  if (!src->d_if || !dst->d_if) {
+    gc_set_error("%s: no IF record loaded", fn);
+    return GC_E_STATE;
+  }
+  if (dst->device != src->device || dst->if_nsamples != src->if_nsamples || dst->if_dtype != src->if_dtype || dst->if_layout != src->if_layout) {
+    gc_set_error("%s: the destination record differs from the source's in device, sample count, dtype or layout", fn);
+    return GC_E_INVALID;
+  }
+  const uint64_t bytes = src->if_nsamples * (uint64_t)excise_bytes_per_sample(src);
+  if (dst->d_if != src->d_if && dst->d_if < src->d_if + bytes && src->d_if < dst->d_if + bytes) {
+    gc_set_error("%s: the destination record overlaps the source without being the same record", fn);
+    return GC_E_INVALID;
+  }
+  return GC_OK;
+}
+
+// the range [first_sample, first_sample + nsamples) against the record: GC_E_RANGE
+inline int excise_check_range(const char* fn, const gc_context* src, long long first_sample, long long nsamples) {
+  const unsigned long long have = src->if_nsamples, first = (unsigned long long)first_sample;
+  if (first > have || have - first < (unsigned long long)nsamples) {
+    gc_set_error("%s: %lld samples from %lld end beyond the record (%llu samples)", fn, nsamples, first_sample, have);
+    return GC_E_RANGE;
+  }
+  return GC_OK;
+}
+
+inline ExcisePulsePlan excise_pulse_plan(long long first_sample, long long nsamples, int bps) {
+  ExcisePulsePlan pl;
+  const long long end = first_sample + nsamples;
+  pl.bps = bps;
+  pl.base = first_sample / 64 * 64;
+  pl.ntiles = (end - pl.base + kExciseTile - 1) / kExciseTile;
+  pl.words = pl.ntiles * kExciseTileWords + 2 * kExciseHalo + 1;
+  return pl;
+}
+
+// gc_excise_pulses' checks (include/gnsscorr.h), arguments before state before range; then the plan
+inline int excise_check_pulses(const gc_context* src, const gc_context* dst, const gc_excise_pulse_params* p, ExcisePulsePlan* pl) {
+  if (!src || !dst || !p) {
+    gc_set_error("gc_excise_pulses: null argument");
+    return GC_E_INVALID;
+  }
+  if (p->first_sample < 0 || p->nsamples < 1 || p->threshold2 < 0 || p->before < 0 || p->before > GC_EXCISE_MAX_GUARD || p->after < 0 ||
+      p->after > GC_EXCISE_MAX_GUARD) {
+    gc_set_error("gc_excise_pulses: bad arguments (first_sample %lld, nsamples %lld, threshold2 %lld, before %d, after %d)", (long long)p->first_sample,
+                 (long long)p->nsamples, (long long)p->threshold2, p->before, p->after);
+    return GC_E_INVALID;
+  }
+  int rc = excise_check_records("gc_excise_pulses", src, dst);
+  if (rc) return rc;
+  rc = excise_check_range("gc_excise_pulses", src, (long long)p->first_sample, (long long)p->nsamples);
+  if (rc) return rc;
+  *pl = excise_pulse_plan((long long)p->first_sample, (long long)p->nsamples, excise_bytes_per_sample(src));
+  return GC_OK;
+}
+
+// ---- gc_excise_bins: segments of nfft samples that overlap by half, cut into tiles whose rows fit a byte budget ------------------------
+// What one tile's rows may take: two buffers of float2 rows (the transform's passes go from one to the other and back), as the
+// probe's.  The library always passes the default and has no switch for it; the CPU tests pass budgets of a few segments.
+struct ExciseBudget {
+  long long tile_bytes = 128LL << 20;
+};
+
+struct ExciseBinsPlan {
+  long long H = 0;     // nfft / 2: the hop, and the samples a segment pair finishes
+  long long K = 0;     // segments: ceil(nsamples / H) + 1; segment k covers the range-relative samples [(k - 1) H, (k + 1) H)
+  long long tile = 0;  // segments per tile at most
+  long long nsamples = 0;
+};
+
+// A tile [g0, g0 + n) of the segment list finishes the range samples [m0, m1): those whose two segments it holds, counting the
+// second half of segment g0 - 1 that the tile before it left behind (carried: g0 > 0).  The tile's last segment is the next carry.
+struct ExciseTile {
+  long long g0 = 0, n = 0;    // first segment, segments (0: before the first tile)
+  long long carried = -1;     // the segment whose second half the tile reads from the carry buffer (-1: none)
+  long long m0 = 0, m1 = 0;   // range samples the tile writes (empty: m0 >= m1)
+};
+
+inline long long excise_tile_segments(int nfft, const ExciseBudget& b) {
+  const long long row = 2LL * (long long)nfft * (long long)sizeof(float2);
+  const long long t = b.tile_bytes / row;
+  return t > 1 ? t : 1;
+}
+
+inline long long excise_segments(long long nsamples, int nfft) {
+  const long long H = nfft / 2;
+  return (nsamples + H - 1) / H + 1;
+}
+
+inline bool excise_next_tile(const ExciseBinsPlan& pl, ExciseTile& t) {
+  t.g0 += t.n;
+  t.n = pl.tile < pl.K - t.g0 ? pl.tile : pl.K - t.g0;
+  if (t.n <= 0) return false;
+  t.carried = t.g0 > 0 ? t.g0 - 1 : -1;
+  t.m0 = (t.g0 > 0 ? t.g0 - 1 : 0) * pl.H;
+  t.m1 = (t.g0 + t.n - 1) * pl.H;
+  if (t.m1 > pl.nsamples) t.m1 = pl.nsamples;
+  return true;
+}
+
+// gc_excise_bins' arguments (include/gnsscorr.h): GC_E_INVALID.  The transform planner's refusal (make_plan: GC_E_UNSUPPORTED) is
+// asked by the driver between this and excise_check_bins_state.
+inline int excise_check_bins(const gc_context* src, const gc_context* dst, const gc_excise_bins_params* p, const float* gain) {
+  if (!src || !dst || !p || !gain) {
+    gc_set_error("gc_excise_bins: null argument");
+    return GC_E_INVALID;
+  }
+  if (p->first_sample < 0 || p->nsamples < 1 || p->nfft < 4 || (p->nfft & 1) || p->reserved != 0) {
+    gc_set_error("gc_excise_bins: bad arguments (first_sample %lld, nsamples %lld, nfft %d, reserved %d)", (long long)p->first_sample,
+                 (long long)p->nsamples, p->nfft, p->reserved);
+    return GC_E_INVALID;
+  }
+  for (int b = 0; b < p->nfft; ++b)
+    if (!(gain[b] - gain[b] == 0.0f)) {  // neither NaN nor an infinity
+      gc_set_error("gc_excise_bins: gain[%d] is not finite", b);
+      return GC_E_INVALID;
+    }
+  return GC_OK;
+}
+
+// ... and what the contexts must hold for them: GC_E_STATE, GC_E_INVALID (a destination that does not match), GC_E_RANGE; then the plan
+inline int excise_check_bins_state(const gc_context* src, const gc_context* dst, const gc_excise_bins_params* p, const ExciseBudget& b, ExciseBinsPlan* pl) {
+  int rc = excise_check_records("gc_excise_bins", src, dst);
+  if (rc) return rc;
+  rc = excise_check_range("gc_excise_bins", src, (long long)p->first_sample, (long long)p->nsamples);
+  if (rc) return rc;
+  pl->H = p->nfft / 2;
+  pl->K = excise_segments((long long)p->nsamples, p->nfft);
+  pl->tile = excise_tile_segments(p->nfft, b);
+  pl->nsamples = (long long)p->nsamples;
+  return GC_OK;
+}

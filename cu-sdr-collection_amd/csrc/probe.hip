@@ -192,37 +192,9 @@ int probe_prepare(gc_context* ctx, ProbeState* s, const Plan& pl, int kind) {
   return GC_OK;
 }
 
-// Forward transform of `nbatch` rows of a (natural order, n values each) in place, b the intermediate; the result in storage order
-// [k1][k2].  The two launches of gc_debug_fft: columns with PRE_NONE / POST_TWIDDLE, rows with PRE_NONE / POST_STORE.
+// Forward transform of `nbatch` rows of a in place, b the intermediate; the result in storage order [k1][k2] (acq_fft.hip transform_rows)
 int probe_transform(gc_context* ctx, const ProbeState* s, float2* a_rows, float2* b_rows, long long nbatch) {
-  const Plan& pl = s->plan;
-  PassArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.n = pl.n;
-  a.tw = (const float2*)s->tw.p;
-  a.inverse = 0;
-  fill_sub(a, pl.p1);
-  a.nvec = pl.n2;
-  a.estride = pl.n2;
-  a.vstride = 1;
-  a.cols = choose_cols(a.len, a.estride);
-  a.pre = PRE_NONE;
-  a.post = POST_TWIDDLE;
-  a.in = a_rows;
-  a.in_batch_stride = pl.n;
-  a.out = b_rows;
-  a.out_batch_stride = pl.n;
-  int rc = launch_pass(ctx, a, nbatch);
-  if (rc) return rc;
-  fill_sub(a, pl.p2);
-  a.nvec = pl.n1;
-  a.estride = 1;
-  a.vstride = pl.n2;
-  a.cols = choose_cols(a.len, a.estride);
-  a.post = POST_STORE;
-  a.in = b_rows;
-  a.out = a_rows;
-  return launch_pass(ctx, a, nbatch);
+  return transform_rows(ctx, s->plan, (const float2*)s->tw.p, a_rows, b_rows, nbatch, 0);
 }
 
 template <bool I16, int NC>

@@ -5,6 +5,7 @@ import contextlib
 import ctypes as C
 import math
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -342,6 +343,56 @@ class Engine:
         L.check(self._lib.gc_cancel(self._ctx, (self if dst is None else dst)._ctx, n, blocks, None if a_in is None else a_in.ctypes.data_as(dp),
                                     out.ctypes.data_as(dp), code))
         return out[..., 0] + 1j * out[..., 1]
+
+    @staticmethod
+    def _excise_pulse_args(first_sample, nsamples, threshold2, before, after):
+        """gc_excise_pulse_params of excise_pulses()'s arguments; ValueError for a value that is not a whole number or does not fit
+        its field - before any library call (what the library refuses is the library's to refuse)."""
+        vals = []
+        for name, v, bits in (("first_sample", first_sample, 64), ("nsamples", nsamples, 64), ("threshold2", threshold2, 64),
+                              ("before", before, 32), ("after", after, 32)):
+            if isinstance(v, (bool, str, bytes)) or v is None or v != int(v) or not -(1 << (bits - 1)) <= int(v) < 1 << (bits - 1):
+                raise ValueError(f"excise_pulses(): {name} must be a whole number of {bits} bits, not {v!r}")
+            vals.append(int(v))
+        return L.gc_excise_pulse_params(*vals)
+
+    def excise_pulses(self, first_sample: int, nsamples: int, threshold2: int, before: int = 0, after: int = 0, dst: "Engine | None" = None):
+        """gc_excise_pulses: of the samples [first_sample, first_sample + nsamples) of this engine's record, those with
+        c0^2 + c1^2 > threshold2 (file order, exact integers) and `before` samples in front of and `after` behind each of them
+        (0 .. GC_EXCISE_MAX_GUARD, cut at the range's ends) written as zero, into `dst`'s record (same sample count, dtype and layout;
+        alloc_if) or (None) in place.  Returns SimpleNamespace(hot, blanked, runs, longest) (include/gnsscorr.h)."""
+        p = self._excise_pulse_args(first_sample, nsamples, threshold2, before, after)
+        st = L.gc_excise_pulse_stats()
+        L.check(self._lib.gc_excise_pulses(self._ctx, (self if dst is None else dst)._ctx, C.byref(p), C.byref(st)))
+        return SimpleNamespace(hot=int(st.hot), blanked=int(st.blanked), runs=int(st.runs), longest=int(st.longest))
+
+    @staticmethod
+    def _excise_gain(gain) -> np.ndarray:
+        """excise_bins()'s gain as contiguous float32 [nfft]; ValueError for anything but one real value per bin of an even transform
+        of at least 4 points - before any library call."""
+        g = np.asarray(gain)
+        if g.ndim != 1 or g.shape[0] < 4 or g.shape[0] % 2 or not (np.issubdtype(g.dtype, np.floating) or np.issubdtype(g.dtype, np.integer)):
+            raise ValueError(f"excise_bins(): gain must be one real value per bin of an even transform length >= 4, not {g.dtype} {g.shape}")
+        return np.ascontiguousarray(g, dtype=np.float32)
+
+    def excise_bins(self, first_sample: int, nsamples: int, gain, dst: "Engine | None" = None, values: bool = False):
+        """gc_excise_bins: the samples [first_sample, first_sample + nsamples) of this engine's record through a gain per frequency bin
+        - gain[b] is bin b of probe_psd with nfft = len(gain), bin 0 = DC, file order - by weighted overlap-add on the library's
+        float32 transform (sine window, half-overlapping segments, zeros outside the range; all ones is the identity), rounded and
+        clamped into `dst`'s record (same sample count, dtype and layout; alloc_if) or (None) in place.  values=True returns the
+        complex64 [nsamples] values before rounding, else None (include/gnsscorr.h)."""
+        g = self._excise_gain(gain)
+        p = L.gc_excise_bins_params(int(first_sample), int(nsamples), g.shape[0], 0)
+        out = np.zeros((max(int(nsamples), 0), 2), dtype=np.float32) if values else None
+        fp = C.POINTER(C.c_float)
+        L.check(self._lib.gc_excise_bins(self._ctx, (self if dst is None else dst)._ctx, C.byref(p), g.ctypes.data_as(fp),
+                                         None if out is None else out.ctypes.data_as(fp)))
+        return None if out is None else out.view(np.complex64)[:, 0]
+
+    @staticmethod
+    def debug_excise_tile_segments(nfft: int) -> int:
+        """gc_debug_excise_tile_segments (test hook, host code only): segments of an nfft-point excise_bins the library transforms at a time."""
+        return int(L.load().gc_debug_excise_tile_segments(int(nfft)))
 
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition

@@ -476,6 +476,72 @@ def correlation_function(fid: Engine, trackResults_k, channel_k, settings, offse
     return fid.correlate_bank(blocks, offsets)[:, :arms, :]
 
 
+def excise_pulse_threshold(counts, pulse_sigmas: float, ncomponents: int):
+    """(threshold2, sigma) of excise_interference()'s pulse rule from gc_probe_histogram's counts: sigma = 1.4826 x the median of |c0|
+    (row 0: the first value of each pair), threshold2 = (pulse_sigmas sigma)^2 ncomponents.  A median in an end bin (|c0| >= 128:
+    an int16 record whose levels the histogram does not resolve) raises ValueError."""
+    row = np.asarray(counts)[0].astype(np.int64)
+    mag = row[128:].copy()                                                              # |v| = 0 .. 128
+    mag[1:] += row[127::-1]
+    total = int(mag.sum())
+    if total == 0:
+        raise ValueError("excise_interference(): the histogram is empty")
+    cum = np.cumsum(mag)
+    lo, hi = int(np.searchsorted(cum, (total + 1) // 2)), int(np.searchsorted(cum, total // 2 + 1))   # the middle sample(s)
+    if hi >= 128:
+        raise ValueError("excise_interference(): the median level lies in the histogram's end bin (|c0| >= 128): give threshold2 to Engine.excise_pulses yourself")
+    sigma = 1.4826 * 0.5 * (lo + hi)
+    return int((float(pulse_sigmas) * sigma) ** 2 * ncomponents), sigma
+
+
+def excise_bin_gain(psd, bin_factor: float, widen: int = 1) -> np.ndarray:
+    """excise_interference()'s gain rule from one row of gc_probe_psd: 0 on the bins above bin_factor x the median bin and on `widen`
+    neighbours each side of them (around the ends: bin nfft - 1 is next to bin 0), 1 elsewhere."""
+    p = np.asarray(psd, dtype=np.float64).reshape(-1)
+    hot = p > float(bin_factor) * float(np.median(p))
+    out = hot.copy()
+    for k in range(1, int(widen) + 1):
+        out |= np.roll(hot, k) | np.roll(hot, -k)
+    return np.where(out, 0.0, 1.0).astype(np.float32)
+
+
+def excise_interference(fid: Engine, settings, first_sample: int = 0, nsamples: int | None = None, pulse_sigmas: float | None = None,
+                        guard_us=(4.0, 4.0), bin_factor: float | None = None, nfft: int = 4096, widen: int = 1, dst: Engine | None = None):
+    """Interference the receiver does not know taken out of [first_sample, first_sample + nsamples) of the loaded record (None: to its
+    end) before acquisition(): pulses first (pulse_sigmas not None: gc_excise_pulses), then carriers (bin_factor not None:
+    gc_excise_bins), from what the probe shows.  Into `dst`'s record (same sample count, dtype and layout) or (None) in place.
+      pulses   threshold2 from gc_probe_histogram of the range (excise_pulse_threshold); guard_us = (before, after) in microseconds
+               at settings.samplingFreq, at most GC_EXCISE_MAX_GUARD samples.
+      bins     gain from gc_probe_psd of the range AFTER blanking - Hamming window, nfft, noverlap = nfft / 2 - by excise_bin_gain.
+    Returns SimpleNamespace(holder, threshold2, sigma, before, after, stats, gain, psd_before, psd_after): the engine that holds the
+    cleaned record, what the pulse stage used and counted (None where it did not run), the gain and the spectra in front of and
+    behind the bin stage (None where it did not run)."""
+    if pulse_sigmas is None and bin_factor is None:
+        raise ValueError("excise_interference(): give pulse_sigmas, bin_factor or both")
+    fs = float(settings.samplingFreq)
+    first_sample = int(first_sample)
+    n = int(fid.if_buffer()[1]) - first_sample if nsamples is None else int(nsamples)
+    dt, layout = fid.if_format()
+    res = SimpleNamespace(holder=fid, threshold2=None, sigma=None, before=None, after=None, stats=None, gain=None, psd_before=None, psd_after=None)
+    if pulse_sigmas is not None:
+        counts, _ = fid.probe_histogram(first_sample, n)
+        res.threshold2, res.sigma = excise_pulse_threshold(counts, pulse_sigmas, 1 if layout == L.GC_REAL else 2)
+        res.before, res.after = (min(L.GC_EXCISE_MAX_GUARD, _round(float(g) * 1e-6 * fs)) for g in guard_us)
+        res.stats = fid.excise_pulses(first_sample, n, res.threshold2, res.before, res.after, dst=dst)
+        if dst is not None:
+            res.holder = dst
+    if bin_factor is not None:
+        src = res.holder                                                                # after blanking: in place on what holds it
+        src.set_sampling_freq(fs)
+        res.psd_before = src.probe_psd(first_sample, n, nfft, nfft // 2, "hamming")[0][0]
+        res.gain = excise_bin_gain(res.psd_before, bin_factor, widen)
+        src.excise_bins(first_sample, n, res.gain, dst=dst if (dst is not None and src is fid) else None)
+        if dst is not None:
+            res.holder = dst
+            dst.set_sampling_freq(fs)
+        res.psd_after = res.holder.probe_psd(first_sample, n, nfft, nfft // 2, "hamming")[0][0]
+    return res
+
 def cancel_tracked(fid: Engine, trackResults, channel, settings, which=None, signal: str = "GPS_L1CA", epochs=None, dst: Engine | None = None,
                    mode: str = "subtract", amp=None):
     """What lies under the signals a tracking run followed: every chosen channel's tracked component rebuilt from the state tracking.m

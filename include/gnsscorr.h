@@ -802,6 +802,83 @@ int gc_cancel(gc_context* src, gc_context* dst, int nblocks, const gc_block* blo
               const double* amp_in  /* [nblocks][GC_MAX_ARMS][2] or NULL */,
               double* amp_out       /* same layout, or NULL */, int mode);
 
+/* ---- interference the receiver does not know: pulses blanked in a record ---------------------------------------------------------
+ * What gc_probe_histogram shows far out of the level histogram - DME / TACAN pulse pairs in the band of GPS L5, Galileo E5a / E5b
+ * and BDS B2a, radar, bursts of a neighbouring service - is blanked where the record lives (csrc/excise.hip); acquisition, tracking,
+ * the bank and the maps then run on the cleaned record.  The records are gc_cancel's: `src` holds the record, `dst` is a context on
+ * the same device whose record has the same sample count, dtype and layout (gc_alloc_if); dst == src, or a context sharing src's
+ * record, works in place and gives the bytes of the out-of-place call.  Synchronous, on src's stream.  The call owns its buffers
+ * (released by gc_destroy) and touches none of the acquisition's, the conditioned signal's, the bank's or the probe's.  New entry
+ * points are detected by symbol: GC_API_VERSION is unchanged.
+ *
+ * Samples are taken in FILE order, as the probe takes them: c0 is the first value of each pair and c1 the second, whatever the
+ * context calls its layout; a real record has c0 only.
+ *
+ * Definition, in exact 64-bit integers (an int16 pair (-32768, -32768) has norm 2^31).  Only the samples of the range
+ * [first_sample, first_sample + nsamples) are examined.  Sample h of the range is hot iff c0^2 + c1^2 > threshold2 (real records:
+ * c0^2).  A hot sample h blanks [h - before, h + after], cut at the range's ends: sample n of the range is blanked - every one of
+ * its components written as 0 - iff a hot sample lies in [n - after, n + before] within the range.  Every other sample of the
+ * range keeps its bytes; the samples of the record outside the range are copied when out of place and untouched when in place.
+ * stats (may be NULL): hot samples, blanked samples (the hot ones included), maximal runs of consecutive blanked samples and the
+ * longest run.  The same input gives the same bytes and the same statistics.
+ *
+ * Refusals (a refused call writes nothing: not dst, not stats): GC_E_INVALID for a null src / dst / p, first_sample < 0,
+ * nsamples < 1, threshold2 < 0, before or after outside [0, GC_EXCISE_MAX_GUARD], a dst record that differs from src's in device,
+ * sample count, dtype or layout, or overlaps it without being it; GC_E_STATE for a src or dst without a record; GC_E_RANGE when the
+ * range ends beyond the record; GC_E_NOMEM. */
+#define GC_EXCISE_MAX_GUARD 4096
+typedef struct gc_excise_pulse_params {
+  int64_t first_sample;  /* 0-based sample (pair) index of the range */
+  int64_t nsamples;      /* samples of the range, >= 1 */
+  int64_t threshold2;    /* sample n is hot iff c0^2 + c1^2 > threshold2 */
+  int32_t before, after; /* samples blanked in front of and behind a hot sample, 0 .. GC_EXCISE_MAX_GUARD */
+} gc_excise_pulse_params;  /* 32 bytes */
+typedef struct gc_excise_pulse_stats {
+  int64_t hot;      /* hot samples */
+  int64_t blanked;  /* samples blanked, hot samples included */
+  int64_t runs;     /* maximal runs of blanked samples */
+  int64_t longest;  /* longest run */
+} gc_excise_pulse_stats;   /* 32 bytes */
+int gc_excise_pulses(gc_context* src, gc_context* dst, const gc_excise_pulse_params* p, gc_excise_pulse_stats* stats /* may be NULL */);
+
+/* ---- ... and carriers notched: a gain per frequency bin by weighted overlap-add on the library's own transform -----------------------
+ * What gc_probe_psd shows standing over the noise - a CW spur, a narrow-band carrier - is taken out of a range of the record by a
+ * gain per bin of an nfft-point transform: bin b of `gain` is bin b of gc_probe_psd (bin 0 = DC, samples in file order z = c0 + i c1,
+ * z = c0 for a real record).  The records, the in-place rule, the stream and the buffers are gc_excise_pulses'.
+ *
+ * Definition.  H = nfft / 2; w[n] = (float) sin(pi (n + 0.5) / nfft), the sine in float64; s[n] = (float)((double)w[n] / nfft).
+ * w^2 of the two halves adds to 1: a gain of all ones is the identity.  K = ceil(nsamples / H) + 1 segments; segment k covers the
+ * range-relative samples [(k-1) H, (k+1) H), samples outside [0, nsamples) count as zero (zero padding: the record's samples next
+ * to the range are not read).  All arithmetic is float32, every operation rounded by itself:
+ *   a_k[n] = w[n] * (float)x           X_k = the library's forward transform of a_k (the acquisition's, as gc_probe_psd)
+ *   Y_k[b] = gain[b] * X_k[b]          per component
+ *   v_k    = the library's unnormalised inverse transform of Y_k
+ *   c_k[n] = s[n] * v_k[n]
+ *   y[m]   = c_k0[H + m mod H] + c_(k0+1)[m mod H],  k0 = floor(m / H), for range sample m
+ * The output is clamp(rint(y)) per component (rint rounds to even, the clamp is the dtype's full range); on real records the
+ * imaginary part of y is dropped.  values (may be NULL; host memory, [nsamples][2] = {re, im}) receives y[m] exactly as it was
+ * rounded, the imaginary part of a real record's included.  Samples of the record outside the range are copied when out of place
+ * and untouched when in place.
+ * Guarantees: the same input gives the same bytes.  A sample's output depends on its two segments only - not on where the library
+ * cuts the segment list into tiles (gc_debug_excise_tile_segments).  In place equals out of place: where a tile ends, the last
+ * segment's contributions are carried, its samples are not read again after they were written.
+ *
+ * Refusals (a refused call writes nothing: not dst, not values): GC_E_INVALID for a null src / dst / p / gain, first_sample < 0,
+ * nsamples < 1, nfft < 4 or odd, reserved != 0, a gain that is not finite, a dst mismatch as above; GC_E_UNSUPPORTED for an nfft
+ * the transform has no plan for (a prime factor of 7 or more, a row longer than 2048); GC_E_STATE, GC_E_RANGE, GC_E_NOMEM as above. */
+typedef struct gc_excise_bins_params {
+  int64_t first_sample;  /* 0-based sample (pair) index of the range */
+  int64_t nsamples;      /* samples of the range, >= 1 */
+  int32_t nfft;          /* even, >= 4, 2^a 3^b 5^c with a plan */
+  int32_t reserved;      /* 0 */
+} gc_excise_bins_params;   /* 24 bytes */
+int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_bins_params* p,
+                   const float* gain  /* [nfft] */,
+                   float* values      /* [nsamples][2] or NULL */);
+/* Test hook (host code only, no context): segments of an nfft-point gc_excise_bins the library transforms at a time (a tile of its
+ * segment list); 0 for nfft < 4. */
+long long gc_debug_excise_tile_segments(int nfft);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,12 @@
  *          hSrc's record into hDst's (hDst == hSrc: in place; gc_cancel): blocks as for 'correlate' (earlyLateSpc ignored); amp
  *          2 x GC_MAX_ARMS x nblocks doubles (re; im), [] = the record's own projection; modelOnly ~= 0 writes the components alone;
  *          returns the amplitudes used in the same layout
+ *   st   = gnsscorr_mex('excise_pulses', hSrc, hDst, firstSample0, nSamples, threshold2[, before[, after]])   % of the range's samples
+ *          those with c0^2 + c1^2 > threshold2 (file order) and `before` / `after` samples around each written as zero, from hSrc's
+ *          record into hDst's (hDst == hSrc: in place; gc_excise_pulses); st = [hot blanked runs longest]
+ *   v    = gnsscorr_mex('excise_bins', hSrc, hDst, firstSample0, nSamples, gain)      % the range through a gain per frequency bin (gain(b)
+ *          is bin b of 'probe_psd' with nfft = numel(gain), bin 1 = DC) by weighted overlap-add, from hSrc's record into hDst's (hDst ==
+ *          hSrc: in place; gc_excise_bins); v (only when asked for) 2 x nSamples single: the values before rounding (re; im)
  *   n    = gnsscorr_mex('device_count')                                              % HIP devices visible: one context per device
  *   prev = gnsscorr_mex('set_precision', h, 'double'|'single')                    % float64 correlations for every later correlate /
  *          track call of this context (gc_set_precision), 'single' = the float32 kernels (default); returns the previous setting
@@ -714,6 +720,57 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxFree(blk);
     if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error()); /* tracking.m:241-245 */
     if (rc) fail("gc_cancel");
+  } else if (!strcmp(cmd, "excise_pulses")) {
+    /* stats = gnsscorr_mex('excise_pulses', hSrc, hDst, firstSample0, nSamples, threshold2[, before[, after]]): [hot blanked runs longest] */
+    if (nrhs < 6) mexErrMsgIdAndTxt("gnsscorr:usage", "excise_pulses: hSrc, hDst, firstSample0, nSamples, threshold2[, before[, after]]");
+    for (int i = 3; i < nrhs && i < 8; ++i) {
+      const double v = mxGetScalar(prhs[i]);
+      if (!(v >= -9007199254740992.0 && v <= 9007199254740992.0) || v != (double)(int64_t)v || (i > 5 && (v < -2147483648.0 || v > 2147483647.0)))
+        mexErrMsgIdAndTxt("gnsscorr:usage", "excise_pulses: argument %d must be a whole number that fits its field", i + 1);
+    }
+    gc_excise_pulse_params p;
+    p.first_sample = (int64_t)mxGetScalar(prhs[3]);
+    p.nsamples = (int64_t)mxGetScalar(prhs[4]);
+    p.threshold2 = (int64_t)mxGetScalar(prhs[5]);
+    p.before = nrhs > 6 ? (int32_t)mxGetScalar(prhs[6]) : 0;
+    p.after = nrhs > 7 ? (int32_t)mxGetScalar(prhs[7]) : 0;
+    gc_excise_pulse_stats st;
+    int rc = gc_excise_pulses(handle(prhs[1]), handle(prhs[2]), &p, &st);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
+    if (rc) fail("gc_excise_pulses");
+    plhs[0] = mxCreateDoubleMatrix(1, 4, mxREAL);
+    double* o = mxGetDoubles(plhs[0]);
+    o[0] = (double)st.hot, o[1] = (double)st.blanked, o[2] = (double)st.runs, o[3] = (double)st.longest;
+  } else if (!strcmp(cmd, "excise_bins")) {
+    /* values = gnsscorr_mex('excise_bins', hSrc, hDst, firstSample0, nSamples, gain): gc_excise_bins; values 2 x nSamples single (re; im)
+     * when an output is asked for */
+    if (nrhs < 6) mexErrMsgIdAndTxt("gnsscorr:usage", "excise_bins: hSrc, hDst, firstSample0, nSamples, gain (one real value per bin)");
+    const size_t nfft = mxGetNumberOfElements(prhs[5]);
+    const double first = mxGetScalar(prhs[3]), count = mxGetScalar(prhs[4]);
+#ifndef GNSSCORR_TEST_MEX_H /* (the test-only mex.h builds no complex arrays and has no mxIsComplex) */
+    if (mxIsComplex(prhs[5])) mexErrMsgIdAndTxt("gnsscorr:usage", "excise_bins: gain must be real");
+#endif
+    if (!(mxIsDouble(prhs[5]) || mxIsSingle(prhs[5])) || nfft < 4 || nfft > 2147483647u)
+      mexErrMsgIdAndTxt("gnsscorr:usage", "excise_bins: gain must be real double or single, one value per bin of an even transform length >= 4");
+    if (!(first >= -9007199254740992.0 && first <= 9007199254740992.0) || first != (double)(int64_t)first ||
+        !(count >= -9007199254740992.0 && count <= 9007199254740992.0) || count != (double)(int64_t)count)
+      mexErrMsgIdAndTxt("gnsscorr:usage", "excise_bins: firstSample0 and nSamples must be whole numbers");
+    float* g = (float*)mxMalloc(nfft * sizeof(float));
+    for (size_t i = 0; i < nfft; ++i) g[i] = mxIsDouble(prhs[5]) ? (float)mxGetDoubles(prhs[5])[i] : ((const float*)mxGetData(prhs[5]))[i];
+    gc_excise_bins_params p;
+    p.first_sample = (int64_t)first;
+    p.nsamples = (int64_t)count;
+    p.nfft = (int32_t)nfft;
+    p.reserved = 0;
+    float* values = NULL;
+    if (nlhs > 0) {
+      plhs[0] = mxCreateNumericMatrix(2, (mwSize)(count > 0 && count < 4e15 ? count : 0), mxSINGLE_CLASS, mxREAL);
+      if (count > 0) values = (float*)mxGetData(plhs[0]);
+    }
+    int rc = gc_excise_bins(handle(prhs[1]), handle(prhs[2]), &p, g, values);
+    mxFree(g);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
+    if (rc) fail("gc_excise_bins");
   } else if (!strcmp(cmd, "device_count")) {
     int n = 0;
     if (gc_device_count(&n)) fail("gc_device_count");
