@@ -23,6 +23,7 @@ GC_PROBE_HIST_BINS = 257   # gc_probe_histogram: hist(x, -128:128)
 GC_CANCEL_MAX_CHANNELS = 64   # gc_cancel: distinct channels per call
 GC_CANCEL_SUBTRACT, GC_CANCEL_MODEL = 0, 1   # gc_cancel_mode
 GC_EXCISE_MAX_GUARD = 4096   # gc_excise_pulses: longest guard in front of and behind a hot sample
+GC_DDC_MAX_TAPS, GC_DDC_MAX_DECIM = 2048, 64   # gc_downconvert: longest filter, largest decimation
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -145,6 +146,17 @@ class gc_excise_bins_params(C.Structure):
     _fields_ = [("first_sample", C.c_int64), ("nsamples", C.c_int64), ("nfft", C.c_int32), ("reserved", C.c_int32)]
 
 
+class gc_ddc_params(C.Structure):
+    """gc_downconvert: output m is filtered at record sample first_sample + m * decim and written to sample dst_first + m of dst."""
+    _fields_ = [("first_sample", C.c_int64), ("noutputs", C.c_int64), ("dst_first", C.c_int64), ("decim", C.c_int32), ("ntaps", C.c_int32),
+                ("carr_freq", C.c_double), ("carr_phase", C.c_double)]
+
+
+class gc_ddc_result(C.Structure):
+    """gc_downconvert: the NCO's two integers (turns * 2^64), clipped components, the sum of squares of what was stored, the NCO's frequency."""
+    _fields_ = [("phase_step", C.c_uint64), ("phase0", C.c_uint64), ("clipped", C.c_int64), ("sum_sq", C.c_uint64), ("carr_freq", C.c_double)]
+
+
 class gc_acq_result(C.Structure):
     _fields_ = [("coarse_bin", C.c_int32), ("code_phase", C.c_int32), ("peak", C.c_double),
                 ("peak_metric", C.c_double), ("coarse_freq", C.c_double)]
@@ -247,6 +259,8 @@ SYMBOLS = {
     "gc_excise_pulses": (C.c_int, [_P, _P, C.POINTER(gc_excise_pulse_params), C.POINTER(gc_excise_pulse_stats)]),
     "gc_excise_bins": (C.c_int, [_P, _P, C.POINTER(gc_excise_bins_params), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gc_debug_excise_tile_segments": (C.c_longlong, [C.c_int]),
+    "gc_downconvert": (C.c_int, [_P, _P, C.POINTER(gc_ddc_params), C.POINTER(C.c_double), C.POINTER(gc_ddc_result)]),
+    "gc_debug_ddc_tile_outputs": (C.c_longlong, [C.c_int, C.c_int]),
 }
 
 _lib = None

@@ -43,8 +43,9 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                "acq_fft.hip", "acq_coarse.hip", "acq_shift.hip", "acq_fine.hip", "acq_cond.hip", "acq_guard.hip", "navsync.hip",
                "probe.hip",       # gc_probe_psd, gc_probe_histogram: a record's Welch spectrum (on acq_fft.hip's pass kernels) and level histograms
                "cancel.hip",      # gc_cancel: tracked components rebuilt in float64 from their descriptors and subtracted from the record
-               "excise.hip"]      # gc_excise_pulses: samples over a level, and a guard around them, blanked in the record (integers throughout);
+               "excise.hip",      # gc_excise_pulses: samples over a level, and a guard around them, blanked in the record (integers throughout);
                                   # gc_excise_bins: a gain per frequency bin by weighted overlap-add on acq_fft.hip's pass kernels
+               "ddc.hip"]         # gc_downconvert: complex FIR, decimation, a 64-bit NCO and requantisation into a second record, float64
 
 
 def _tuned(spec: str) -> str:
@@ -58,7 +59,7 @@ LIBS = {
     "libgnsscorr_tuning.so": [_tuned(u) for u in _CORR_UNITS],
     "libgnsssynth.so": ["synth.hip"],
 }
-HEADERS = ["gc_internal.h", "corr_common.h", "record_fmt.h", "replica_f64.h", "launch_plan.h", "bank_plan.h", "probe_plan.h", "excise_plan.h", "devloop.h", "acq_guard.h", "acq_internal.h", os.path.join("..", "..", "include", "gnsscorr.h")]
+HEADERS = ["gc_internal.h", "corr_common.h", "record_fmt.h", "replica_f64.h", "launch_plan.h", "bank_plan.h", "probe_plan.h", "excise_plan.h", "ddc_plan.h", "devloop.h", "acq_guard.h", "acq_internal.h", os.path.join("..", "..", "include", "gnsscorr.h")]
 # --offload-compress: the gfx950 code objects inside the fat binary are zstd-compressed (10.1 -> ~1.6 MB; the HIP runtime inflates them
 # when the library is loaded: ~20 ms once per process)
 FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
@@ -69,7 +70,8 @@ FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-f
 # instead of two: wrong table index at exact ties).  These translation units therefore forbid contraction;
 # wanted FMAs are written as fmaf() / fma().
 NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip", "corr_bank.hip", "cancel.hip",
-               "excise.hip"}   # excise.hip: y = s v + s v' is two products and a sum, each rounded by itself
+               "excise.hip",   # excise.hip: y = s v + s v' is two products and a sum, each rounded by itself
+               "ddc.hip"}      # ddc.hip: a tap is four products, a difference and three sums, each rounded by itself
 
 
 def _hipcc() -> str:

@@ -196,6 +196,7 @@ struct gc_context {
   void* cancel = nullptr;    // gc_cancel: sorted descriptors, channel list, projection partials and amplitudes (cancel.hip: CancelState)
   void* excise = nullptr;    // gc_excise_pulses: the hot-sample bitmap, the tiles' run summaries, the statistics; gc_excise_bins: its plan, twiddle
                              // table, window, gain, rows, carry and values (excise.hip: ExciseState)
+  void* ddc = nullptr;       // gc_downconvert: the taps and the two result counters on the device (ddc.hip: DdcState)
 
   // gc_track_multi: this context's tracking call runs next to other contexts' on the same device.  Its persistent kernels
   // are then launched with a plain launch instead of a cooperative one (gc_launch_persistent below).
@@ -279,6 +280,7 @@ void gc_acq_free(gc_context* ctx);  // acq_coarse.hip
 void gc_probe_free(gc_context* ctx);  // probe.hip
 void gc_cancel_free(gc_context* ctx);  // cancel.hip
 void gc_excise_free(gc_context* ctx);  // excise.hip
+void gc_ddc_free(gc_context* ctx);  // ddc.hip
 int gc_sync_channels(gc_context* ctx);
 // Launches the correlator for `nblocks` descriptors of scope `s` already on the device: plans (launch_plan.h), fills the
 // kernel arguments from the plan, dispatches on its kernel, combines the partial sums where splits > 1.

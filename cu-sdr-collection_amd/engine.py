@@ -194,6 +194,7 @@ class Engine:
 
     def set_sampling_freq(self, fs: float):
         L.check(self._lib.gc_set_sampling_freq(self._ctx, float(fs)))
+        self.sampling_freq = float(fs)   # what the context holds (receiver.downconvert_band designs its filter for it)
 
     # ---- code tables ---------------------------------------------------------------------
     def set_channel(self, channel: int, tables, index_scale: float = 1.0, arm_mult=None, windows=None):
@@ -393,6 +394,55 @@ class Engine:
     def debug_excise_tile_segments(nfft: int) -> int:
         """gc_debug_excise_tile_segments (test hook, host code only): segments of an nfft-point excise_bins the library transforms at a time."""
         return int(L.load().gc_debug_excise_tile_segments(int(nfft)))
+
+    @staticmethod
+    def _ddc_taps(taps) -> np.ndarray:
+        """downconvert()'s taps as contiguous float64 [T, 2] = (re, im); ValueError for anything but a [T] real or complex array or a
+        [T][2] real one with 1 <= T <= GC_DDC_MAX_TAPS - before any library call."""
+        g = np.asarray(taps)
+        numeric = np.issubdtype(g.dtype, np.floating) or np.issubdtype(g.dtype, np.integer)
+        if g.ndim == 1 and (numeric or np.issubdtype(g.dtype, np.complexfloating)):
+            g = g.astype(np.complex128)
+            g = np.stack([g.real, g.imag], axis=-1)
+        elif not (g.ndim == 2 and g.shape[1] == 2 and numeric):
+            raise ValueError(f"downconvert(): taps must be [T] complex or [T][2] real, not {g.dtype} {g.shape}")
+        if not 1 <= g.shape[0] <= L.GC_DDC_MAX_TAPS:
+            raise ValueError(f"downconvert(): 1 .. {L.GC_DDC_MAX_TAPS} taps, not {g.shape[0]}")
+        return np.ascontiguousarray(g, dtype=np.float64)
+
+    @staticmethod
+    def _ddc_whole(name, v, bits):
+        if isinstance(v, (bool, str, bytes)) or v is None or v != int(v) or not -(1 << (bits - 1)) <= int(v) < 1 << (bits - 1):
+            raise ValueError(f"downconvert(): {name} must be a whole number of {bits} bits, not {v!r}")
+        return int(v)
+
+    def downconvert(self, dst: "Engine", taps, decim: int, carr_freq: float = 0.0, carr_phase: float = 0.0, first_sample: int = 0,
+                    noutputs: int | None = None, dst_first: int = 0):
+        """gc_downconvert: this engine's record through the complex FIR `taps` ([T] complex or [T][2] real), every decim-th output -
+        output m sits at record sample first_sample + m * decim - rotated by an NCO of carr_freq Hz (phase carr_phase at record sample
+        0) and rounded into sample dst_first + m of `dst`'s record (another engine on the same device; any sample count, dtype and
+        layout).  noutputs=None: every output that still has a record sample under it, up to dst's capacity.
+        Returns SimpleNamespace(phase_step, phase0, clipped, sum_sq, carr_freq, noutputs) (include/gnsscorr.h)."""
+        g = self._ddc_taps(taps)
+        d = self._ddc_whole("decim", decim, 32)
+        first = self._ddc_whole("first_sample", first_sample, 64)
+        dfirst = self._ddc_whole("dst_first", dst_first, 64)
+        if noutputs is None:
+            _, have = self.if_buffer()
+            _, room = dst.if_buffer()
+            nout = min((int(have) + g.shape[0] - 2 - first) // max(d, 1) + 1, int(room) - dfirst)
+        else:
+            nout = self._ddc_whole("noutputs", noutputs, 64)
+        p = L.gc_ddc_params(first, nout, dfirst, d, g.shape[0], float(carr_freq), float(carr_phase))
+        r = L.gc_ddc_result()
+        L.check(self._lib.gc_downconvert(self._ctx, dst._ctx, C.byref(p), g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)))
+        return SimpleNamespace(phase_step=int(r.phase_step), phase0=int(r.phase0), clipped=int(r.clipped), sum_sq=int(r.sum_sq),
+                               carr_freq=float(r.carr_freq), noutputs=nout)
+
+    @staticmethod
+    def debug_ddc_tile_outputs(decim: int, ntaps: int) -> int:
+        """gc_debug_ddc_tile_outputs (test hook, host code only): outputs a workgroup of downconvert() takes; 0 for a refused (decim, ntaps)."""
+        return int(L.load().gc_debug_ddc_tile_outputs(int(decim), int(ntaps)))
 
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition

@@ -542,6 +542,78 @@ def excise_interference(fid: Engine, settings, first_sample: int = 0, nsamples: 
         res.psd_after = res.holder.probe_psd(first_sample, n, nfft, nfft // 2, "hamming")[0][0]
     return res
 
+
+def ddc_nco_step(freq: float, fs: float) -> int:
+    """gc_downconvert's phase_step for `freq` at `fs` as a signed Python integer: ldexp(freq / fs, 64) rounded to the nearest integer,
+    ties to even (what llrint gives the library)."""
+    from fractions import Fraction
+    return int(round(Fraction(math.ldexp(float(freq) / float(fs), 64))))
+
+
+def ddc_nco_freq(step: int, fs: float) -> float:
+    """The frequency an NCO of phase_step `step` (signed) runs at: gc_ddc_result.carr_freq."""
+    return math.ldexp(float(int(step)), -64) * float(fs)
+
+
+def ddc_band_taps(fs: float, center_freq: float, bandwidth: float, ntaps: int, window="hamming"):
+    """(g, f_used, h) of downconvert_band(): h = scipy.signal.firwin(ntaps, bandwidth / 2, fs=fs) low-pass of gain 1 at DC,
+    g[k] = h[k] exp(+j 2 pi f_used k / fs) the same filter around f_used, the frequency gc_downconvert's NCO runs at for center_freq."""
+    from scipy.signal import firwin
+    h = np.asarray(firwin(int(ntaps), float(bandwidth) / 2.0, window=window, fs=float(fs)), dtype=np.float64) if ntaps > 1 else np.ones(1)
+    f_used = ddc_nco_freq(ddc_nco_step(center_freq, fs), fs)
+    return ddc_modulate(h, f_used, fs), f_used, h
+
+
+def ddc_modulate(h, f_used: float, fs: float) -> np.ndarray:
+    """g[k] = h[k] exp(+j 2 pi f_used k / fs), operation by operation as matlab/gnsscorr_downconvert.m writes it."""
+    h = np.asarray(h, dtype=np.float64).reshape(-1)
+    ang = 2.0 * np.pi * f_used * np.arange(h.shape[0], dtype=np.float64) / float(fs)
+    return h * np.cos(ang) + 1j * (h * np.sin(ang))
+
+
+def downconvert_band(engine: Engine, dst: Engine, center_freq: float, bandwidth: float, decim: int, ntaps: int | None = None,
+                     target_rms: float | None = None, window="hamming", h=None):
+    """The band of `bandwidth` Hz around center_freq of `engine`'s record as a record at samplingFreq / decim in `dst` (another engine
+    on the same device with a record from alloc_if; any dtype and layout): one gc_downconvert with a windowed-sinc low-pass moved to
+    the band, the NCO taking the band's centre to DC.  engine's sampling frequency must be set (set_sampling_freq / load_if(fs=)).
+      ntaps       None: the odd number 8 decim + 1 (at most GC_DDC_MAX_TAPS - 1).
+      h           a real low-pass of the caller's to use instead of the designed one (bandwidth, ntaps and window are then ignored):
+                  what matlab/gnsscorr_downconvert.m does with fir1's.
+      target_rms  None: gain 1.  Else the rms a stored component should have: the call runs on the first min(noutputs, 65536)
+                  outputs, the taps are scaled by target_rms / the rms sum_sq gives, and the whole range runs with them.
+    first_sample = (ntaps - 1) // 2, so that output m lines up with input sample m * decim.
+    Returns (result of Engine.downconvert, SimpleNamespace(samplingFreq = fs / decim, IF = center_freq - f_used: what the NCO's
+    quantised frequency leaves of the centre, f_used, gain, delay: the filter's residual delay in INPUT samples (0 for odd ntaps, 0.5
+    for even), decim)) - code phases found on dst map back as sample * decim + delay.  dst's sampling frequency is set."""
+    fs = getattr(engine, "sampling_freq", None)
+    if fs is None:
+        raise ValueError("downconvert_band(): set the engine's sampling frequency first")
+    d = int(decim)
+    if d != decim or not 1 <= d <= L.GC_DDC_MAX_DECIM:
+        raise ValueError(f"downconvert_band(): decim must be a whole number in 1 .. {L.GC_DDC_MAX_DECIM}, not {decim!r}")
+    if h is None:
+        T = min(8 * d + 1, L.GC_DDC_MAX_TAPS - 1) if ntaps is None else int(ntaps)
+        g, f_used, _ = ddc_band_taps(fs, center_freq, bandwidth, T, window)
+    else:
+        f_used = ddc_nco_freq(ddc_nco_step(center_freq, fs), fs)
+        g = ddc_modulate(h, f_used, fs)
+        T = g.shape[0]
+    first = (T - 1) // 2
+    gain = 1.0
+    comps = 1 if dst.if_format()[1] == L.GC_REAL else 2
+    if target_rms is not None:
+        full = min((int(engine.if_buffer()[1]) + T - 2 - first) // d + 1, int(dst.if_buffer()[1]))
+        trial = engine.downconvert(dst, g, d, carr_freq=center_freq, first_sample=first, noutputs=min(full, 65536))
+        rms = math.sqrt(trial.sum_sq / (comps * trial.noutputs))
+        if not rms > 0.0:
+            raise ValueError("downconvert_band(): the band holds nothing to scale (every stored component of the trial is zero)")
+        gain = float(target_rms) / rms
+    res = engine.downconvert(dst, gain * g, d, carr_freq=center_freq, first_sample=first)
+    dst.set_sampling_freq(fs / d)
+    return res, SimpleNamespace(samplingFreq=fs / d, IF=float(center_freq) - f_used, f_used=f_used, gain=gain,
+                                delay=(T - 1) / 2.0 - first, decim=d)
+
+
 def cancel_tracked(fid: Engine, trackResults, channel, settings, which=None, signal: str = "GPS_L1CA", epochs=None, dst: Engine | None = None,
                    mode: str = "subtract", amp=None):
     """What lies under the signals a tracking run followed: every chosen channel's tracked component rebuilt from the state tracking.m

@@ -879,6 +879,67 @@ int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_bins_params
  * segment list); 0 for nfft < 4. */
 long long gc_debug_excise_tile_segments(int nfft);
 
+/* ---- a band of a record as a record at a lower rate: the digital down-converter -----------------------------------------------------
+ * gc_downconvert filters a record with a complex FIR, keeps every D-th output, rotates it by a numerically controlled oscillator and
+ * requantises it into a SECOND record (csrc/ddc.hip): a 50 Msps L5 file, one FDMA carrier of a GLONASS record, the C/A main lobe of
+ * an 18 Msps file become records that every correlator here reads at D times fewer samples.  `src` holds the record (its own, or one
+ * shared through gc_share_if) and the sampling frequency; `dst` is another context on the same device with a record from gc_alloc_if
+ * or gc_attach_if - any sample count, dtype and layout.  Synchronous, on src's stream.  The call owns its buffers (released by
+ * gc_destroy) and touches none of the acquisition's, the probe's, the bank's or the excision's.  New entry points are detected by
+ * symbol: GC_API_VERSION is unchanged.
+ *
+ * Definition, in float64, every operation rounded by itself (no fused multiply-add).  fs = src's gc_set_sampling_freq,
+ * D = decim, T = ntaps, g[k] = (gr[k], gi[k]) = taps[k].
+ *   input     x[n] = (re, im) of record sample n: I/Q as stored, Q/I swapped, real records im = 0; x[n] = 0 for n < 0 and for
+ *             n >= the record's sample count
+ *   position  n_m = first_sample + m * D for output m, 0 <= m < noutputs
+ *   filter    a_r = a_i = +0.0; for k = 0 .. T-1 in ascending order, with x = x[n_m - k]:
+ *               pr = gr[k]*xr - gi[k]*xi,  pi = gr[k]*xi + gi[k]*xr,  a_r = a_r + pr,  a_i = a_i + pi
+ *   NCO       exact integers modulo 2^64, addressed by the absolute record index:
+ *               phase_step = (uint64)(int64) llrint(ldexp(carr_freq / fs, 64))
+ *               phase0: q = carr_phase / 6.283185307179586, r = q - rint(q), X = ldexp(r, 64); 2^63 where X = +-2^63, else
+ *                       (uint64)(int64) llrint(X)
+ *               ph_m = phase0 + phase_step * (uint64) n_m
+ *               ang = (double)(int64) ph_m * (6.283185307179586 * 2^-64), in [-pi, pi]: no large-argument reduction, and the phase
+ *                     of a sample does not depend on where a call starts;  (sn, cs) = sincos(ang)
+ *   rotation  yr = cs*a_r + sn*a_i,  yi = cs*a_i - sn*a_r
+ *   store     into dst's record at sample dst_first + m, in dst's own format: clamp(rint(.)) per component (rint rounds to even, the
+ *             clamp is the dtype's full range); (yr, yi) for GC_IQ, (yi, yr) for GC_QI, yr alone for GC_REAL.
+ *   result    clipped and sum_sq count what was stored (yi of a real dst is not counted).
+ * The taps carry any gain; the library applies none.
+ * Guarantees: dst's bytes outside [dst_first, dst_first + noutputs) are untouched.  The same input gives the same bytes and
+ * statistics.  An output depends on its own T input samples and on n_m only - not on the tile it falls in (gc_debug_ddc_tile_outputs),
+ * not on the call it belongs to: two calls on [n_0, n_0 + a D) and from n_0 + a D on, with dst_first moved by a, write the bytes of
+ * the single call.
+ *
+ * Refusals (a refused call writes nothing: not dst, not res): GC_E_INVALID for a null src / dst / p / taps, first_sample or
+ * dst_first < 0, noutputs < 1, decim outside [1, GC_DDC_MAX_DECIM], ntaps outside [1, GC_DDC_MAX_TAPS], a tap, carr_freq or carr_phase
+ * that is not finite, |carr_freq| >= fs / 2, a dst on another device, a dst record that is src's or overlaps it; GC_E_STATE for a src
+ * or dst without a record and a src without a sampling frequency; GC_E_RANGE when dst_first + noutputs exceeds dst's record, and when
+ * the last output has no record sample under it (n_last - (T-1) >= src's sample count); GC_E_NOMEM. */
+#define GC_DDC_MAX_TAPS  2048
+#define GC_DDC_MAX_DECIM 64
+typedef struct gc_ddc_params {
+  int64_t first_sample;  /* record index n_0 of output 0's newest input sample, >= 0 */
+  int64_t noutputs;      /* >= 1 */
+  int64_t dst_first;     /* output m is written to sample dst_first + m of dst's record, >= 0 */
+  int32_t decim;         /* D, 1 .. GC_DDC_MAX_DECIM */
+  int32_t ntaps;         /* T, 1 .. GC_DDC_MAX_TAPS */
+  double  carr_freq;     /* Hz, |carr_freq| < fs / 2 (fs = src's gc_set_sampling_freq) */
+  double  carr_phase;    /* radians, the NCO's phase at record sample 0 */
+} gc_ddc_params;         /* 48 bytes */
+typedef struct gc_ddc_result {
+  uint64_t phase_step;   /* NCO increment per INPUT sample, turns * 2^64 */
+  uint64_t phase0;       /* NCO phase at record sample 0, turns * 2^64 */
+  int64_t  clipped;      /* stored components whose rint(y) lay outside dst's integer range */
+  uint64_t sum_sq;       /* exact sum of the squares of the stored components */
+  double   carr_freq;    /* the frequency the NCO runs at: (int64) phase_step * 2^-64 * fs */
+} gc_ddc_result;         /* 40 bytes */
+int gc_downconvert(gc_context* src, gc_context* dst, const gc_ddc_params* p,
+                   const double* taps /* [ntaps][2] = {re, im} */, gc_ddc_result* res /* may be NULL */);
+/* Test hook (host code only, no context): outputs a workgroup of the kernel takes (a tile); 0 for a decim or ntaps out of range. */
+long long gc_debug_ddc_tile_outputs(int decim, int ntaps);
+
 #ifdef __cplusplus
 }
 #endif
