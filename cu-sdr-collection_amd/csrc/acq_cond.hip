@@ -232,6 +232,8 @@ extern "C" int gc_acq_conditioned(gc_context* ctx, int64_t first, int64_t n, flo
     return GC_E_RANGE;
   }
   GC_HIP(hipSetDevice(ctx->device));
+  // gc_acq_signal_from_record leaves its kernel in flight on ctx->stream, which is non-blocking: a plain hipMemcpy does not wait for it
+  GC_HIP(hipStreamSynchronize(ctx->stream));
   GC_HIP(hipMemcpy(dst, (const float2*)ctx->acqbuf[gc_context::ACQ_COND_SIG].p + first, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
   return GC_OK;
 }

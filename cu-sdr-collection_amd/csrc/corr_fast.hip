@@ -420,6 +420,13 @@ __global__ __launch_bounds__(WIDE != 0 ? 256 : kFW) void corr_epl_fast_kernel(co
         for (int sx = 0; sx < NS; ++sx) {
           const float u = gh[sx] * uk;
           suspect |= fabsf(u - rintf(u)) < kTieTol;
+          // ... and a ramp that is a hair ABOVE a table edge at the chunk's first sample: the next transition is a whole entry away
+          // (u = 1 / step, no integer), yet the reference's rounded a + i*d may sit exactly ON that edge and still read the entry
+          // below.  Seen where the 64-bit ramp reaches the chunk by its exact per-iteration steps (k > 0) and where the reference
+          // counts backwards from the block's end: t = 341 at sample 6000 of a block with rem = 0.  ~ghi = samples since the edge / uk.
+          float gb;
+          asm("v_cvt_f32_u32_e32 %0, %1" : "=v"(gb) : "v"(~ghi[sx]));
+          suspect |= gb * uk < kTieTol;
         }
         exact |= __any(suspect) != 0;
       }

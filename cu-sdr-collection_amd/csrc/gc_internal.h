@@ -185,6 +185,7 @@ struct gc_context {
   bool force_generic = false;
   int last_kernel = -2;  // gc_debug_last_kernel
   int last_track_mode = -1;  // gc_debug_last_track_mode: 0 launch per epoch, 1 persistent host-fed kernel, 2 device loop
+  int last_track_team = 0;   // gc_debug_last_track_team: workgroups per block of that call (team members / splits per launch)
   int precision = GC_PREC_F32;  // gc_set_precision: GC_PREC_F64 routes gc_correlate and the tracking loops to corr_f64.hip
 
   // acquisition scratch (acq_coarse.hip: AcqScratch)

@@ -669,6 +669,7 @@ void gc_mark_tie_free(const gc_context* ctx, gc_block* b, int64_t n, double eps_
 extern "C" int gc_build_flags(void) { return GC_TUNING ? GC_BUILD_TUNING : 0; }
 extern "C" int gc_debug_last_kernel(const gc_context* ctx) { return ctx ? ctx->last_kernel : -2; }
 extern "C" int gc_debug_last_track_mode(const gc_context* ctx) { return ctx ? ctx->last_track_mode : -1; }
+extern "C" int gc_debug_last_track_team(const gc_context* ctx) { return ctx ? ctx->last_track_team : 0; }
 
 namespace {
 template <int K>

@@ -295,6 +295,7 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
   // single-arm R = 1 channels on the transition-mask kernel with one-wave workgroups, any record format (GPS L1 C/A, BDS B1I,
   // GLONASS); everything else keeps launching.
   ctx->last_track_mode = 0;
+  ctx->last_track_team = ctx->precision == GC_PREC_F64 ? 1 : splits;  // gc_debug_last_track_team; a persistent kernel's team below
   bool persist = poll && !any_mixed && max_arms == 1 && fast_nominal > 0 && gc_fast_table_mode(scope) == 0 && p->pilot_combine == 0 &&
                  p->table_phase_count == 0 && n_epochs > 0 &&
                  !(GC_TUNE_ENV("GC_TRACK_PERSIST") && std::atoi(GC_TUNE_ENV("GC_TRACK_PERSIST")) == 0);
@@ -435,6 +436,7 @@ int gc_track_window(gc_context* ctx, const gc_track_params* p, int nch, const gc
       continue;
     }
     ctx->last_track_mode = e == hipSuccess ? 1 : 0;
+    if (e == hipSuccess) ctx->last_track_team = psplits_dev;
     if (e == hipSuccess && GC_TUNE_ENV("GC_TRACK_DEBUG"))
       std::fprintf(stderr, "gc_track: persistent kernel: %d channels x %d members (%s kernel)\n", nch, psplits_dev, persist_lane ? "lane" : "fast");
     if (e == hipSuccess) ctx->last_kernel = persist_lane ? 0 : 1;  // gc_debug_last_kernel: lane / fast kernel (persistent instantiation)
@@ -928,6 +930,8 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
   if (rc == GC_E_NOFIT) rc = GC_E_UNSUPPORTED;  // one member per channel and still no room: the caller falls back to gc_track
   if (rc == GC_OK) {
     ctx->last_track_mode = 2;
+    ctx->last_track_team = f64 ? 1 : splits;
+    ctx->last_kernel = f64 ? 6 : use_fast ? 1 : 0;  // gc_debug_last_kernel: the device loop's float64 / fast / lane instantiation
     const auto t_l = std::chrono::steady_clock::now();
     e = hipStreamSynchronize(ctx->stream);
     const auto t_k = std::chrono::steady_clock::now();

@@ -454,6 +454,10 @@ class Engine:
         """gc_debug_last_track_mode: 0 a launch per epoch, 1 persistent host-fed kernel, 2 device loop."""
         return int(self._lib.gc_debug_last_track_mode(self._ctx))
 
+    def last_track_team(self) -> int:
+        """gc_debug_last_track_team: workgroups per block of the last tracking call (team members, or splits of a launch per epoch)."""
+        return int(self._lib.gc_debug_last_track_team(self._ctx))
+
     def debug_wave_transpose_sum(self, values: np.ndarray) -> np.ndarray:
         """gc_debug_wave_transpose_sum: values [k, 64] float32 -> the k wave sums as the lane kernel's flush forms them."""
         v = np.ascontiguousarray(values, dtype=np.float32)

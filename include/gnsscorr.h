@@ -670,7 +670,7 @@ long long gc_debug_first_sample_near_edge(double a, double step, long long n, do
  * BOC(1,1) - which lets the lane kernel derive that arm instead of staging its table; 0 otherwise. */
 int gc_debug_tables_derivable(const int8_t* t1, int n1, const int8_t* t6, int n6);
 
-/* Test hook: which correlator kernel the last gc_correlate / gc_replay_launch / gc_track launch used:
+/* Test hook: which correlator kernel the last gc_correlate / gc_replay_launch / gc_track / gc_track_device launch used:
  * 0 lane kernel (any chipping rate), 1 fast kernel with one-wave workgroups (float2 tables), 2 fast kernel with
  * four-wave workgroups and int8-pair tables, 3 the same with plain float tables, -1 exact per-sample kernel
  * (mixed ramp multipliers), 6 the float64 per-sample kernel (GC_PREC_F64, gc_correlate and the host-closed loop);
@@ -683,6 +683,12 @@ int gc_debug_last_kernel(const gc_context* ctx);
  * kernels in flight (gc_track_multi), is retried with half as many workgroups per channel until it fits; only a grid that no
  * team size brings under the limit runs with a launch per epoch instead (same records). */
 int gc_debug_last_track_mode(const gc_context* ctx);
+
+/* Test hook: how many workgroups shared one block of one channel in the last gc_track / gc_track_device call on this context:
+ * the members of a team of the device loop or of the persistent host-fed kernel - after any halving that made the grid fit -
+ * or the splits of a launch per epoch; 1 for the float64 loops; 0 before the first call.  Team sizes follow from the channel
+ * count, the block length and the device's compute units, so a test can prove which ones it covered. */
+int gc_debug_last_track_team(const gc_context* ctx);
 /* Test hook for the lane kernel's flush (csrc/corr_common.h: wave_transpose_sum): `k` (1..32) vectors of 64 floats, in[v * 64 + lane];
  * out[v] = the sum over the 64 lanes as the one-wave transposing reduction forms it (the tree's own order of additions). */
 int gc_debug_wave_transpose_sum(gc_context* ctx, int k, const float* in, float* out);

@@ -25,6 +25,7 @@ normalised by N-1.
 from __future__ import annotations
 
 import cmath
+import functools
 import math
 import os
 from types import SimpleNamespace
@@ -552,6 +553,27 @@ def generate_e1_code(prn: int, component: str) -> np.ndarray:
 # --------------------------------------------------------------------------------------
 
 
+def fold_pilot(pilot_combine: int, p11, p61):
+    """The two pilot arms {BOC(1,1), BOC(6,1)} of the three-arm modes folded into one sextet I_E, Q_E, I_P, Q_P, I_L, Q_L."""
+    p11, p61 = [float(v) for v in p11], [float(v) for v in p61]
+    if pilot_combine == 4:
+        # BDS/B1C/include/WB_tracking.m:364-369: arms {data, pilot BOC(1,1), pilot BOC(6,1)}
+        a61, a11 = -math.sqrt(4 / 33), math.sqrt(29 / 33)
+        pil = []
+        for x in range(3):
+            pil += [a61 * p61[2 * x] + a11 * p11[2 * x + 1], a61 * p61[2 * x + 1] - a11 * p11[2 * x]]
+        return pil
+    # Galileo E1-C CBOC(6,1,1/11) pilot (OS SIS ICD 2.3.3): sqrt(10/11) BOC(1,1) - sqrt(1/11) BOC(6,1), in phase;
+    # not in the reference (GAL_E1C tracks with BOC(1,1) only): BASELINE config 3, parity against this oracle
+    a11, a61 = math.sqrt(10 / 11), -math.sqrt(1 / 11)
+    return [a11 * p11[v] + a61 * p61[v] for v in range(6)]
+
+
+def fold_pilot_gain(pilot_combine: int) -> float:
+    """Sum of the absolute coefficients of fold_pilot: how far the fold can stretch an error of its two inputs."""
+    return math.sqrt(4 / 33) + math.sqrt(29 / 33) if pilot_combine == 4 else math.sqrt(10 / 11) + math.sqrt(1 / 11)
+
+
 def tracking_generic(if_bytes: np.ndarray, channel, settings, spec, correlate=None):
     """spec: SimpleNamespace(
          tables(prn) -> list of padded tables (arm 0 = data, arm 1 = pilot),
@@ -561,7 +583,9 @@ def tracking_generic(if_bytes: np.ndarray, channel, settings, spec, correlate=No
                        | 2 plain average (GAL_E1C tracking.m:303-311,326-331)
                        | 3 pilot in quadrature atan(-I/Q) (B1C NB_tracking.m:341) | 4 B1C wide-band three-arm fold,
          optional pll_weight / dll_weight (data, pilot), dll_scale_spacing, arm_mult (per-arm ramp multipliers),
-         code_freq_from_channel  True: channel.codeFreq (GPS_L5C tracking.m:165), False: codeFreqBasis)
+         code_freq_from_channel  True: channel.codeFreq (GPS_L5C tracking.m:165), False: codeFreqBasis,
+         optional swap_iq (a Q,I record), file_type (1: a record of real samples; default 2), int16_branch)
+    correlate: as tracking_l1ca's; one row of six sums per arm, or for pilot_combine 4 / 5 two rows {data, folded pilot}.
     Epoch count NumToProcess = round(msToProcess/1000/intTime) (GAL_E1C tracking.m:51)."""
     n_ep = int(matlab_round(settings.msToProcess / 1000 / settings.intTime))
     d = settings.dllCorrelatorSpacing
@@ -571,7 +595,8 @@ def tracking_generic(if_bytes: np.ndarray, channel, settings, spec, correlate=No
         tau1carr, tau2carr = calc_loop_coef(settings.pllNoiseBandwidth, settings.pllDampingRatio, 0.25)
     else:
         pf3, pf2, pf1 = calc_loop_coef_carr(settings, spec.coef_variant)
-    n_total = if_bytes.shape[0] // 2
+    file_type = getattr(spec, "file_type", 2)     # 1: a record of real samples (GPS_L1CA tracking.m:126-130,232-236)
+    n_total = if_bytes.shape[0] // (1 if file_type == 1 else 2)
     fields = TRACK_FIELDS + ("Pilot_I_E", "Pilot_Q_E", "Pilot_I_P", "Pilot_Q_P", "Pilot_I_L", "Pilot_Q_L")
     results = []
     for _ in channel:
@@ -603,7 +628,7 @@ def tracking_generic(if_bytes: np.ndarray, channel, settings, spec, correlate=No
             tr.remCarrPhase[e] = rem_carr
             if correlate is None:
                 sums, rem_code_new, rem_carr_new = correlate_block(
-                    raw_from_if(if_bytes, pos, n, swap_iq=getattr(spec, "swap_iq", False)), tables, rem_code, step, d,
+                    raw_from_if(if_bytes, pos, n, file_type, swap_iq=getattr(spec, "swap_iq", False)), tables, rem_code, step, d,
                     carr_freq, rem_carr, settings.samplingFreq, settings.codeLength, r=spec.r,
                     arm_mult=getattr(spec, "arm_mult", None))
             else:
@@ -616,21 +641,9 @@ def tracking_generic(if_bytes: np.ndarray, channel, settings, spec, correlate=No
             code_err = float((math.sqrt(i_e * i_e + q_e * q_e) - math.sqrt(i_l * i_l + q_l * q_l)) /
                              (math.sqrt(i_e * i_e + q_e * q_e) + math.sqrt(i_l * i_l + q_l * q_l)))
             if spec.pilot_combine:
-                if spec.pilot_combine == 4:
-                    # BDS/B1C/include/WB_tracking.m:364-369: arms {data, pilot BOC(1,1), pilot BOC(6,1)}
-                    a61, a11 = -math.sqrt(4 / 33), math.sqrt(29 / 33)
-                    p11, p61 = [float(v) for v in sums[1]], [float(v) for v in sums[2]]
-                    pil = []
-                    for x in range(3):
-                        pil += [a61 * p61[2 * x] + a11 * p11[2 * x + 1], a61 * p61[2 * x + 1] - a11 * p11[2 * x]]
-                    pi_e, pq_e, pi_p, pq_p, pi_l, pq_l = pil
-                elif spec.pilot_combine == 5:
-                    # Galileo E1-C CBOC(6,1,1/11) pilot (OS SIS ICD 2.3.3): sqrt(10/11) BOC(1,1) - sqrt(1/11) BOC(6,1), in phase;
-                    # not in the reference (GAL_E1C tracks with BOC(1,1) only): BASELINE config 3, parity against this oracle
-                    a11, a61 = math.sqrt(10 / 11), -math.sqrt(1 / 11)
-                    p11, p61 = [float(v) for v in sums[1]], [float(v) for v in sums[2]]
-                    pi_e, pq_e, pi_p, pq_p, pi_l, pq_l = [a11 * p11[v] + a61 * p61[v] for v in range(6)]
-                else:
+                if spec.pilot_combine in (4, 5) and len(sums) == 3:
+                    pi_e, pq_e, pi_p, pq_p, pi_l, pq_l = fold_pilot(spec.pilot_combine, sums[1], sums[2])
+                else:      # one pilot arm - or a `correlate` hook that hands back the pilot of modes 4 / 5 folded already
                     pi_e, pq_e, pi_p, pq_p, pi_l, pq_l = (float(v) for v in sums[1])
                 with np.errstate(divide="ignore", invalid="ignore"):
                     if spec.pilot_combine == 1:
@@ -899,6 +912,7 @@ def _l2c_register(octal_as_int: int) -> np.ndarray:
     return np.where(reg == 1, -1.0, 1.0)
 
 
+@functools.lru_cache(maxsize=8)     # CL is 767 250 chips of a Python shift register; callers pad or index it, none writes to it
 def generate_l2c_code(prn: int, which: str, n_chips: int) -> np.ndarray:
     """GPS/GPS_L2C/include/generateCMcode.m:39-111 / generateCLcode.m: out = reg(end); reg = circshift(reg,1);
     reg([4 7 9 12 15 17 19 22 23 24 25]) *= out.  Returned interleaved with zeros: CM = [chip 0 chip 0 ...],
@@ -913,6 +927,7 @@ def generate_l2c_code(prn: int, which: str, n_chips: int) -> np.ndarray:
         reg[pos] *= chips[i]
     out = np.zeros(2 * n_chips)
     out[(0 if which == "CM" else 1)::2] = chips
+    out.flags.writeable = False
     return out
 
 
@@ -962,12 +977,13 @@ def generate_b1c_code(prn: int, which: str) -> np.ndarray:
     return (prim[:, None] * sub[None, :]).reshape(-1)
 
 
-def tracking_l2c(if_bytes: np.ndarray, channel, settings):
+def tracking_l2c(if_bytes: np.ndarray, channel, settings, correlate=None):
     """GPS/GPS_L2C/include/tracking.m:40-420 restated: the loop runs on the RZ-doubled code (earlyLateSpc*2,
     codeLength*2, codeFreqBasis*2, :107-109,171), seeks to skipNumberOfBytes + codePhase without -1 (:153), reads the
     CL arm at index + codeLength*(CLCodePhase-1) with CLCodePhase cycling 1..75 (:261,357-360), averages data and
     pilot discriminators when pilotTRKflag (:336-339,352-356), records remCodePhase, codeFreq, dllDiscr and
-    dllDiscrFilt halved and absoluteSample = position + 1 - remCodePhase/codePhaseStep (:226,250,376,382-383)."""
+    dllDiscrFilt halved and absoluteSample = position + 1 - remCodePhase/codePhaseStep (:226,250,376,382-383).
+    `correlate` as tracking_l1ca's, in the loop's doubled-code units, with the arms' table offsets as keyword `table_offset`."""
     n_ep = int(matlab_round(settings.msToProcess / 1000 / settings.intTime))
     d = settings.dllCorrelatorSpacing * 2
     code_length = settings.codeLength * 2
@@ -1008,8 +1024,11 @@ def tracking_l2c(if_bytes: np.ndarray, channel, settings):
             tr.remCodePhase[e] = rem_code / 2
             tr.remCarrPhase[e] = rem_carr
             off = [0, int(code_length) * (cl_phase - 1)] if pilot else None
-            sums, rem_code, rem_carr = correlate_block(raw_from_if(if_bytes, pos, n), tables, rem_code, step, d, carr_freq,
-                                                       rem_carr, settings.samplingFreq, code_length, table_offset=off)
+            if correlate is None:
+                sums, rem_code, rem_carr = correlate_block(raw_from_if(if_bytes, pos, n), tables, rem_code, step, d, carr_freq,
+                                                           rem_carr, settings.samplingFreq, code_length, table_offset=off)
+            else:
+                sums, rem_code, rem_carr = correlate(ch, pos, n, rem_code, step, d, carr_freq, rem_carr, table_offset=off)
             pos += n
             i_e, q_e, i_p, q_p, i_l, q_l = (float(v) for v in sums[0])
             with np.errstate(divide="ignore", invalid="ignore"):

@@ -158,19 +158,21 @@ def _l2c(P, S):
 
 
 # ---- oracle runners ------------------------------------------------------------------------------------------------------
-def _o_l1ca(O, rec, ch, S):
-    return O.tracking_l1ca(rec, ch, S)
+# hook (tests/loop_epochs.py): None, or hook(kind, spec, S, channels) -> the `correlate` argument of the oracle's loop, made once the
+# runner knows the spec and the channel objects that loop will be called with
+def _o_l1ca(O, rec, ch, S, hook=None):
+    return O.tracking_l1ca(rec, ch, S, correlate=hook and hook("l1ca", None, S, ch))
 
 
 def _o_generic(**kw):
-    def run(O, rec, ch, S):
+    def run(O, rec, ch, S, hook=None):
         k = dict(kw)
         tables = k.pop("tables")
         spec = SimpleNamespace(tables=lambda prn: tables(O, prn), **k)
         och = [SimpleNamespace(**{**vars(c), "PRN": (1 if c.status != "-" else 0) if hasattr(c, "K") else c.PRN}) for c in ch]
         if not hasattr(S, "skipNumberOfBytes"):
             S = SimpleNamespace(**vars(S), skipNumberOfBytes=getattr(S, "skipNumberOfSamples", 0))
-        return O.tracking_generic(rec, och, S, spec)
+        return O.tracking_generic(rec, och, S, spec, correlate=hook and hook("generic", spec, S, och))
     return run
 
 
@@ -186,13 +188,17 @@ def _e5_tables(i_sig, q_sig):
     return t
 
 
-def _o_b1c_wb(O, rec, ch, S):
+def _o_l2c(O, rec, ch, S, hook=None):
+    return O.tracking_l2c(rec, ch, S, correlate=hook and hook("l2c", None, S, ch))
+
+
+def _o_b1c_wb(O, rec, ch, S, hook=None):
     from cu_sdr_collection_amd import signals
     run = _o_generic(tables=lambda O_, prn: [O_.pad_code(O_.generate_b1c_code(prn, "data")), O_.pad_code(O_.generate_b1c_code(prn, "pilot11")),
                                              O_.pad_code(O_.generate_b1c_code(prn, "pilot61"))],
                      arm_mult=[1.0, 1.0, 6.0], r=2.0, pll="3state", coef_variant="b", pilot_combine=4, code_freq_from_channel=True,
                      dll_scale_spacing=True, pll_weight=(1.0, 3.0), dll_weight=signals._b1c_wb_dll_weight(S))
-    return run(O, rec, ch, S)
+    return run(O, rec, ch, S, hook)
 
 
 TRACK_SCENES = [
@@ -251,7 +257,7 @@ TRACK_SCENES = [
                fn="WB_tracking", pilot=True, oracle=_o_b1c_wb,
                notes="the DLL weighting factor comes from CalcWeighingFactor.m's four integral() calls"),
     TrackScene("GPS_L2C", "GPS/GPS_L2C", "GPS_L2C", "initSettings_GPS_L2C", dict(msToProcess=100, numberOfChannels=3, pilotTRKflag=1), _l2c,
-               pilot=True, oracle=lambda O, rec, ch, S: O.tracking_l2c(rec, ch, S)),
+               pilot=True, oracle=_o_l2c),
 ]
 
 
