@@ -468,10 +468,9 @@ int ensure_scratch(gc_context* ctx, int n, long long nbh, int nprn, int nbins, i
   ctx->acq_scratch = nullptr;
   s = new AcqScratch();
   std::memset(&s->shift, 0, sizeof s->shift);
-  if (!make_plan(n, &s->plan)) {
+  if (const int rc = plan_or_refuse(n, &s->plan)) {
     delete s;
-    gc_set_error("acquisition: FFT size %d is not of the form 2^a 3^b 5^c (or its factors are too large)", n);
-    return GC_E_UNSUPPORTED;
+    return rc;
   }
   s->n = n;
   s->nbh = nbh;
@@ -492,12 +491,10 @@ int ensure_scratch(gc_context* ctx, int n, long long nbh, int nprn, int nbins, i
     gc_set_error("acquisition: device allocation failed");
     return GC_E_NOMEM;
   }
-  std::vector<float2> tw(ne);
-  for (size_t k = 0; k < ne; ++k) {
-    const double ang = -2.0 * 3.14159265358979323846 * (double)k / (double)n;
-    tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+  if (const int rc = upload_twiddles(ctx, n, s->tw)) {
+    free_scratch(s);
+    return rc;
   }
-  GC_HIP(hipMemcpy(s->tw, tw.data(), ne * sizeof(float2), hipMemcpyHostToDevice));
   ctx->acq_scratch = s;
   *out = s;
   return GC_OK;

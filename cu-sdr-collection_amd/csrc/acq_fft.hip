@@ -16,6 +16,7 @@
 // This file: the transform plans, the pass kernels (run-time fft_pass_kernel, per-shape fft_pass_ct, the fused kernel of the tuning
 // build), launch_pass / forward.  The searches that use them: acq_coarse.hip, acq_shift.hip.
 #include "acq_internal.h"
+#include "record_fmt.h"
 
 using namespace gcacq;
 
@@ -113,6 +114,23 @@ bool make_plan(int n, Plan* pl) {
   pl->n1 = best;
   pl->n2 = n / best;
   return factor(pl->n1, &pl->p1) && factor(pl->n2, &pl->p2) && pl->n2 <= kMaxPassLen;
+}
+
+int plan_or_refuse(int n, Plan* pl) {
+  if (make_plan(n, pl)) return GC_OK;
+  gc_set_error("acquisition: FFT size %d is not of the form 2^a 3^b 5^c (or its factors are too large)", n);
+  return GC_E_UNSUPPORTED;
+}
+
+int upload_twiddles(gc_context* ctx, int n, float2* d_tw) {
+  std::vector<float2> tw((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    const double ang = -2.0 * 3.14159265358979323846 * (double)k / (double)n;
+    tw[(size_t)k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
+  }
+  GC_HIP(hipMemcpyAsync(d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+  GC_HIP(hipStreamSynchronize(ctx->stream));  // tw is gone when this returns
+  return GC_OK;
 }
 }  // namespace gcacq
 namespace {
@@ -1580,6 +1598,43 @@ int forward(gc_context* ctx, AcqScratch* s, PassArgs base, int pre, long long nb
   return launch_pass(ctx, a, nbatch);
 }
 
+}  // namespace gcacq
+namespace {
+// One workgroup per kFftThreads consecutive values of one row (gather_rows); row 0 is segment k0 of span span0.  The division is
+// taken only by the rows behind a span's end (wave-uniform), and the record is read without a branch - outside the span a sample
+// of the span that is not used - so that it and the window's value are in flight together.
+template <int MODE>
+__global__ __launch_bounds__(kFftThreads) void gather_rows_kernel(const uint8_t* __restrict__ rec, const RowGather r, long long span0, long long k0, int nfft,
+                                                                   int blocks_per_row, const float* __restrict__ win, float2* __restrict__ rows) {
+  const long long t = blockIdx.x / (unsigned)blocks_per_row;
+  const int n = (int)(blockIdx.x - (unsigned)(t * blocks_per_row)) * kFftThreads + (int)threadIdx.x;
+  if (n >= nfft) return;
+  long long span = span0, k = k0 + t;
+  if (k >= r.K) {
+    const long long q = k / r.K;
+    span += q;
+    k -= q * r.K;
+  }
+  const long long m = k * r.step - r.lead + n;
+  const bool inside = m >= 0 && m < r.nsamples;
+  int c0, c1;
+  gcorr::file_sample<MODE>(rec, r.first + span * r.nsamples + (inside ? m : 0), c0, c1);
+  const float w = win[n];
+  rows[t * nfft + n] = make_float2(w * (float)(inside ? c0 : 0), w * (float)(inside ? c1 : 0));  // a real record: w * 0 = +0, the windows are not negative
+}
+}  // namespace
+namespace gcacq {
+int gather_rows(gc_context* ctx, const RowGather& r, long long g0, long long nrows, int nfft, const float* win, float2* rows) {
+  const int bpr = (nfft + kFftThreads - 1) / kFftThreads;
+  const long long span0 = g0 / r.K, k0 = g0 - span0 * r.K;
+  gcorr::gc_with_file_mode(gcorr::gc_record_mode(ctx), [&](auto m) {
+    hipLaunchKernelGGL(gather_rows_kernel<decltype(m)::value>, dim3((unsigned int)(nrows * bpr)), dim3(kFftThreads), 0, ctx->stream, ctx->d_if, r, span0, k0, nfft,
+                       bpr, win, rows);
+  });
+  GC_HIP(hipGetLastError());
+  return GC_OK;
+}
+
 int transform_rows(gc_context* ctx, const Plan& pl, const float2* tw, float2* a_rows, float2* b_rows, long long nbatch, int inverse) {
   PassArgs a;
   std::memset(&a, 0, sizeof a);
@@ -1666,10 +1721,8 @@ extern "C" int gc_debug_fft(gc_context* ctx, int n, int nbatch, const float* in,
 extern "C" int gc_debug_fft_plan(int n, int* n1, int* n2, int* rad1, int* nrad1, int* rad2, int* nrad2, int* cols1, int* cols2) {
   if (n <= 1 || !n1 || !n2 || !rad1 || !nrad1 || !rad2 || !nrad2 || !cols1 || !cols2) return GC_E_INVALID;
   Plan pl;
-  if (!make_plan(n, &pl)) {
-    gc_set_error("acquisition: FFT size %d is not of the form 2^a 3^b 5^c (or its factors are too large)", n);
-    return GC_E_UNSUPPORTED;
-  }
+  const int rc = plan_or_refuse(n, &pl);
+  if (rc) return rc;
   *n1 = pl.n1;
   *n2 = pl.n2;
   *nrad1 = pl.p1.nrad;

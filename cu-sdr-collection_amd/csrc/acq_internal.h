@@ -312,6 +312,10 @@ struct AcqStreams {
 
 // ---- acq_fft.hip ------------------------------------------------------------------------------------------------------------------
 bool make_plan(int n, Plan* pl);
+// make_plan for a caller that has no other length to try: GC_E_UNSUPPORTED and the planner's message where it refuses n
+int plan_or_refuse(int n, Plan* pl);
+// exp(-2 pi i k / n), k < n, computed in float64 and rounded once, into d_tw on the context's stream, which is waited for
+int upload_twiddles(gc_context* ctx, int n, float2* d_tw);
 // tile width C1 of the specialised columns pass for vectors of `len`, `nvec` of them per transform; 0: no specialised pass
 int ct_columns_tile(int len, int nvec);
 int launch_pass(gc_context* ctx, PassArgs& a, long long nbatch_groups, bool* used_ct = nullptr);
@@ -322,6 +326,14 @@ int choose_cols(int L, int estride = 1);
 // entries; the result in storage order [k1][k2] (natural index k1 + n1 k2).  The two launches of gc_debug_fft: columns with
 // PRE_NONE / POST_TWIDDLE, rows with PRE_NONE / POST_STORE; inverse = 1 is the unnormalised inverse.  Shared by probe.hip and excise.hip.
 int transform_rows(gc_context* ctx, const Plan& pl, const float2* tw, float2* a_rows, float2* b_rows, long long nbatch, int inverse);
+// The rows such a transform takes, from the context's record in file order (c1 = 0 for a real record): the samples from `first` are
+// cut into spans of `nsamples`, a span into K segments `step` apart, the first one `lead` samples in front of the span.  Row t of
+// rows[nrows][nfft] is segment g = g0 + t (span = g / K, k = g - span K): value n is win[n] * x of span sample m = k step - lead + n,
+// and zero where m lies outside [0, nsamples).
+struct RowGather {
+  long long first, nsamples, step, K, lead;
+};
+int gather_rows(gc_context* ctx, const RowGather& r, long long g0, long long nrows, int nfft, const float* win, float2* rows);
 // Forward transform of `nbatch` sequences produced by `pre` into `dst` (layout [k1][k2])
 int forward(gc_context* ctx, AcqScratch* s, PassArgs base, int pre, long long nbatch, float2* dst);
 // GC_ACQ_FUSED (tuning build): the whole inverse side of a 36 000- / 24 000-point search in one launch; false: no fused kernel for this plan

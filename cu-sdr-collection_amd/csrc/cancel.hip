@@ -8,15 +8,17 @@
 // Pass 1 (cancel_project_kernel, only without amp_in): the prompt sums P and the integer E of every block.  A block is cut into
 //   chunks of kCancelChunk samples, one workgroup each - a cut that depends on the block alone, so a block's sums are the same bits whatever
 //   else is in the call.  Lanes by fixed shuffles, waves in index order, chunks in index order (cancel_amp_kernel, which also divides).
-// Pass 2 (cancel_apply_kernel): one thread per 16 bytes of record (8 int8 I/Q samples, 4 int16 I/Q, 16 int8 real, 8 int16 real): one
-//   16-byte load, its samples one after the other - for every channel of the call the block that covers the sample (a guess from the
-//   channel's mean block length, a binary search over the sorted starts where the guess misses), the replica, the sum in channel
-//   order - and one 16-byte store.  The record's last, partial 16 bytes and records whose base is not 16-byte aligned (gc_attach_if)
-//   go byte by byte.  No atomics; a sample's output depends on its own input and the blocks that cover it.
+// Pass 2 (cancel_apply_kernel): one thread per 16 bytes of record (8 int8 I/Q samples, 4 int16 I/Q, 16 int8 real, 8 int16 real) as a
+//   RecVec (record_fmt.h: one 16-byte load and store, byte by byte for the record's partial last vector), its samples one after the
+//   other - for every channel of the call the block that covers the sample (a guess from the channel's mean block length, a binary
+//   search over the sorted starts where the guess misses), the replica, the sum in channel order.  No atomics; a sample's output
+//   depends on its own input and the blocks that cover it.
+// What the call asks of its two records is record_check.h's check_record_pair.
 #include <algorithm>
 #include <cmath>
 
 #include "corr_common.h"
+#include "record_check.h"
 #include "replica_f64.h"
 
 using namespace gcorr;
@@ -156,10 +158,7 @@ struct ApplyArgs {
   double fs;
   int nchan;
   int mode;
-  int vec_ok;                // both records 16-byte aligned
 };
-
-__device__ __forceinline__ uint32_t pick_word(const uint32_t (&w)[4], int k) { return k == 0 ? w[0] : k == 1 ? w[1] : k == 2 ? w[2] : w[3]; }
 
 template <int MODE>
 __global__ __launch_bounds__(kCancelWG) void cancel_apply_kernel(const ApplyArgs p) {
@@ -172,28 +171,17 @@ __global__ __launch_bounds__(kCancelWG) void cancel_apply_kernel(const ApplyArgs
     for (int i = (int)threadIdx.x; i < words; i += kCancelWG) s[i] = g[i];
   }
   __syncthreads();
-  const long long nvec = (p.nsamples + F::per16 - 1) / F::per16;
+  const long long nvec = (p.nsamples + F::per16 - 1) / F::per16, nbytes = p.nsamples * F::bps;
   for (long long v = (long long)blockIdx.x * kCancelWG + threadIdx.x; v < nvec; v += (long long)gridDim.x * kCancelWG) {
     const long long n0 = v * F::per16;
     const int cnt = (int)min((long long)F::per16, p.nsamples - n0);
-    const bool whole = p.vec_ok && cnt == F::per16;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    if (whole) {
-      const uint4 q = *(const uint4*)(p.src + v * 16);
-      w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
-    } else {
-      const uint8_t* s = p.src + v * 16;
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (k < cnt * F::bps) w[k >> 2] |= (uint32_t)s[k] << (8 * (k & 3));
-    }
+    RecVec<MODE> w;
+    w.load(p.src, v * 16, nbytes);
 #pragma unroll 1
     for (int s = 0; s < cnt; ++s) {
       const long long n = n0 + s;
-      const int bit = s * F::bps * 8, word = bit >> 5, sh = bit & 31;
-      const uint32_t raw = pick_word(w, word) >> sh;
-      const int v0 = F::value_bytes == 1 ? (int)(signed char)(raw & 0xffu) : (int)(short)(raw & 0xffffu);
-      const int v1 = F::values == 1 ? 0 : F::value_bytes == 1 ? (int)(signed char)((raw >> 8) & 0xffu) : (int)(short)(raw >> 16);
+      int v0, v1;
+      w.get(s, v0, v1);
       const double x_re = (double)(F::swap ? v1 : v0), x_im = (double)(F::swap ? v0 : v1);
       double m_re = 0.0, m_im = 0.0;
       for (int c = 0; c < p.nchan; ++c) {
@@ -235,25 +223,10 @@ __global__ __launch_bounds__(kCancelWG) void cancel_apply_kernel(const ApplyArgs
       }
       const double y_re = p.mode == GC_CANCEL_MODEL ? m_re : __dadd_rn(x_re, -m_re);
       const double y_im = p.mode == GC_CANCEL_MODEL ? m_im : __dadd_rn(x_im, -m_im);
-      const int o_re = (int)fmin(fmax(rint(y_re), F::lo), F::hi);
-      const int o_im = (int)fmin(fmax(rint(y_im), F::lo), F::hi);
-      const int o0 = F::swap ? o_im : o_re, o1 = F::swap ? o_re : o_im;
-      constexpr uint32_t vmask = F::value_bytes == 1 ? 0xffu : 0xffffu;
-      constexpr uint32_t smask = F::bps == 4 ? 0xffffffffu : (1u << (F::bps * 8 % 32)) - 1u;
-      uint32_t bits = (uint32_t)o0 & vmask;
-      if constexpr (F::values == 2) bits |= ((uint32_t)o1 & vmask) << (8 * F::value_bytes);
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (q == word) w[q] = (w[q] & ~(smask << sh)) | (bits << sh);
+      const int o_re = quantise<MODE>(y_re), o_im = quantise<MODE>(y_im);
+      w.put(s, F::swap ? o_im : o_re, F::swap ? o_re : o_im);
     }
-    if (whole) {
-      *(uint4*)(p.dst + v * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-      uint8_t* o = p.dst + v * 16;
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (k < cnt * F::bps) o[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-    }
+    w.store(p.dst, v * 16, nbytes);
   }
 }
 
@@ -313,11 +286,6 @@ int check_block(const gc_context* ctx, long long i, const gc_block& k) {
   return GC_OK;
 }
 
-int cancel_nomem() {
-  gc_set_error("gc_cancel: device allocation failed");
-  return GC_E_NOMEM;
-}
-
 }  // namespace
 
 void gc_cancel_free(gc_context* ctx) {
@@ -337,23 +305,12 @@ extern "C" int gc_cancel(gc_context* src, gc_context* dst, int nblocks, const gc
     gc_set_error("gc_cancel: unknown mode %d", mode);
     return GC_E_INVALID;
   }
-  if (!src->d_if || !dst->d_if) {
-    gc_set_error("no IF buffer loaded");
+  if (nblocks > 0 && !(src->fs > 0)) {  // GC_E_STATE like a missing record, which check_record_pair names next
+    gc_set_error("gc_cancel: sampling frequency not set (gc_set_sampling_freq)");
     return GC_E_STATE;
   }
-  if (nblocks > 0 && !(src->fs > 0)) {
-    gc_set_error("sampling frequency not set (gc_set_sampling_freq)");
-    return GC_E_STATE;
-  }
-  const uint64_t bytes = src->if_nsamples * (uint64_t)gc_bytes_per_sample(src->if_dtype, src->if_layout);
-  if (dst->device != src->device || dst->if_nsamples != src->if_nsamples || dst->if_dtype != src->if_dtype || dst->if_layout != src->if_layout) {
-    gc_set_error("gc_cancel: the destination record differs from the source's in device, sample count, dtype or layout");
-    return GC_E_INVALID;
-  }
-  if (dst->d_if != src->d_if && dst->d_if < src->d_if + bytes && src->d_if < dst->d_if + bytes) {
-    gc_set_error("gc_cancel: the destination record overlaps the source without being the same record");
-    return GC_E_INVALID;
-  }
+  if (const int rc = check_record_pair("gc_cancel", src, dst)) return rc;
+  const uint64_t bytes = src->if_nsamples * (uint64_t)gc_record_bps(src);
   // the blocks grouped by channel in ascending index, each group sorted by first_sample
   std::vector<int> order((size_t)nblocks);
   for (int i = 0; i < nblocks; ++i) {
@@ -426,18 +383,14 @@ extern "C" int gc_cancel(gc_context* src, gc_context* dst, int nblocks, const gc
   // nothing has been written up to here
   GC_HIP(hipSetDevice(src->device));
   if (dst != src) GC_HIP(hipStreamSynchronize(dst->stream));  // the destination's own pending work comes first
-  CancelState* s = static_cast<CancelState*>(src->cancel);
-  if (!s) {
-    s = new (std::nothrow) CancelState();
-    if (!s) return cancel_nomem();
-    src->cancel = s;
-  }
+  CancelState* s = gc_unit_state<CancelState>(src->cancel);
+  if (!s) return gc_nomem("gc_cancel");
   if (nblocks > 0) {
     if (gc_buf_reserve(s->blocks, sizeof(gc_block) * (size_t)nblocks, false) != hipSuccess ||
         gc_buf_reserve(s->starts, sizeof(long long) * (size_t)nblocks, false) != hipSuccess ||
         gc_buf_reserve(s->chans, sizeof(CancelChan) * chans.size(), false) != hipSuccess ||
         gc_buf_reserve(s->amp, sizeof(double) * namp, false) != hipSuccess)
-      return cancel_nomem();
+      return gc_nomem("gc_cancel");
     GC_HIP(hipMemcpyAsync(s->blocks.p, sorted.data(), sizeof(gc_block) * (size_t)nblocks, hipMemcpyHostToDevice, src->stream));
     GC_HIP(hipMemcpyAsync(s->starts.p, starts.data(), sizeof(long long) * (size_t)nblocks, hipMemcpyHostToDevice, src->stream));
     GC_HIP(hipMemcpyAsync(s->chans.p, chans.data(), sizeof(CancelChan) * chans.size(), hipMemcpyHostToDevice, src->stream));
@@ -447,7 +400,7 @@ extern "C" int gc_cancel(gc_context* src, gc_context* dst, int nblocks, const gc
       if (gc_buf_reserve(s->prefix, sizeof(long long) * ((size_t)nblocks + 1), false) != hipSuccess ||
           gc_buf_reserve(s->part_p, sizeof(double) * (size_t)chunks * 2 * GC_MAX_ARMS, false) != hipSuccess ||
           gc_buf_reserve(s->part_e, sizeof(int32_t) * (size_t)chunks * GC_MAX_ARMS, false) != hipSuccess)
-        return cancel_nomem();
+        return gc_nomem("gc_cancel");
       GC_HIP(hipMemcpyAsync(s->prefix.p, prefix.data(), sizeof(long long) * ((size_t)nblocks + 1), hipMemcpyHostToDevice, src->stream));
       ProjectArgs pa;
       pa.if_base = src->d_if;
@@ -478,7 +431,6 @@ extern "C" int gc_cancel(gc_context* src, gc_context* dst, int nblocks, const gc
   aa.fs = src->fs;
   aa.nchan = (int)chans.size();
   aa.mode = mode;
-  aa.vec_ok = (((uintptr_t)src->d_if | (uintptr_t)dst->d_if) & 15u) == 0;
   const long long nvec = ((long long)bytes + 15) / 16;
   const long long wgs = std::min<long long>((nvec + kCancelWG - 1) / kCancelWG, 1LL << 20);  // grid-stride beyond
   if (wgs > 0) launch_apply(src, (unsigned int)wgs, aa);

@@ -4,10 +4,11 @@
 //
 // The outputs are cut into tiles of consecutive outputs (ddc_plan.h), one workgroup each:
 //   stage    the tile's input span [n_lo, n_hi] as the record's own bytes into LDS, in whole 16-byte vectors of the record from the
-//            vector that holds n_lo's first byte: one 16-byte global load where the vector lies inside the record, byte by byte (zero
-//            outside) for the record's partial last vector and for the padding in front of sample 0 and behind the last sample.  The
-//            samples stay integers in LDS - as doubles the span of the longest filter at the largest decimation would not fit - and
-//            are converted where they are used.  The taps go next to them as (re, im) doubles.
+//            vector that holds n_lo's first byte, each a RecVec load (record_fmt.h: one 16-byte global load where the vector lies
+//            inside the record, byte by byte and zero outside for the record's partial last vector and for the padding in front of
+//            sample 0 and behind the last sample).  The samples stay integers in LDS - as doubles the span of the longest filter
+//            at the largest decimation would not fit - and are converted where they are used.  The taps go next to them as
+//            (re, im) doubles.
 //   filter   a thread carries up to kDdcChains outputs, kDdcWG apart: that many independent add chains, which share every tap read
 //            (the tap's address is the same in all lanes: one broadcast read).  k ascending, products and sums as the definition
 //            writes them.
@@ -17,8 +18,6 @@
 //            of integer atomics per workgroup into one of 64 slots, which the host adds.
 // An output depends on its T samples and on n_m only; the tile decides nothing but who computes it.
 // The unit's buffers are its own (DdcState, kept in gc_context::ddc, grow-only, released by gc_destroy).
-#include <new>
-
 #include "ddc_plan.h"
 #include "record_fmt.h"
 
@@ -42,10 +41,10 @@ struct DdcArgs {
   unsigned long long phase_step, phase0;
   int decim, ntaps, tile;
   int dst_mode;                // gcorr::Mode of dst
-  int vec_ok;                  // the record's base is 16-byte aligned
 };
 
-// sample at byte offset `off` of the staged span as (re, im)
+// sample at byte offset `off` of the staged span as (re, im): record_sample (record_fmt.h) at a byte pointer.  Not folded into it: an
+// int16 pair is one 32-bit LDS read here and two 16-bit global loads there, and one form for both would change the kernels of one
 template <int MODE>
 __device__ __forceinline__ void staged_sample(const uint8_t* lds, int off, double& re, double& im) {
   using F = Fmt<MODE>;
@@ -90,20 +89,9 @@ __global__ __launch_bounds__(kDdcWG) void ddc_kernel(const DdcArgs p) {
   const int nvec = (int)ddc_stage_vecs(tile.n_lo, tile.n_hi, F::bps);  // <= (span * bps + 15 + 15) / 16: inside ddc_lds_bytes
 
   for (int i = tid; i < nvec; i += kDdcWG) {
-    const long long g = base16 + 16LL * i;
-    uint4 q = make_uint4(0u, 0u, 0u, 0u);
-    if (g >= 0 && g + 16 <= p.src_bytes && p.vec_ok) {
-      q = *(const uint4*)(p.src + g);
-    } else if (g + 16 > 0 && g < p.src_bytes) {  // the vector holds a byte of the record
-      uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const long long b = g + k;
-        if (b >= 0 && b < p.src_bytes) w[k >> 2] |= (uint32_t)p.src[b] << (8 * (k & 3));
-      }
-      q = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    vecs[i] = q;
+    RecVec<MODE> q;
+    q.load(p.src, base16 + 16LL * i, p.src_bytes);
+    vecs[i] = q.words();
   }
   for (int k = tid; k < T; k += kDdcWG) taps[k] = make_double2(p.taps[2 * k], p.taps[2 * k + 1]);
   __syncthreads();
@@ -187,12 +175,6 @@ __global__ __launch_bounds__(kDdcWG) void ddc_kernel(const DdcArgs p) {
   }
 }
 
-int ddc_nomem() {
-  (void)hipGetLastError();
-  gc_set_error("gc_downconvert: device allocation failed");
-  return GC_E_NOMEM;
-}
-
 }  // namespace
 
 void gc_ddc_free(gc_context* ctx) {
@@ -217,15 +199,11 @@ extern "C" int gc_downconvert(gc_context* src, gc_context* dst, const gc_ddc_par
   // nothing has been written up to here
   GC_HIP(hipSetDevice(src->device));
   GC_HIP(hipStreamSynchronize(dst->stream));  // the destination's own pending work comes first
-  DdcState* s = static_cast<DdcState*>(src->ddc);
-  if (!s) {
-    s = new (std::nothrow) DdcState();
-    if (!s) return ddc_nomem();
-    src->ddc = s;
-  }
+  DdcState* s = gc_unit_state<DdcState>(src->ddc);
+  if (!s) return gc_nomem("gc_downconvert");
   const size_t taps_bytes = (size_t)p->ntaps * 2 * sizeof(double);
   if (gc_buf_reserve(s->taps, taps_bytes, false) != hipSuccess || gc_buf_reserve(s->stats, sizeof(unsigned long long[kDdcStatSlots][2]), false) != hipSuccess)
-    return ddc_nomem();
+    return gc_nomem("gc_downconvert");
   GC_HIP(hipMemcpyAsync(s->taps.p, taps, taps_bytes, hipMemcpyHostToDevice, src->stream));
   GC_HIP(hipMemsetAsync(s->stats.p, 0, sizeof(unsigned long long[kDdcStatSlots][2]), src->stream));
   DdcArgs a;
@@ -243,7 +221,6 @@ extern "C" int gc_downconvert(gc_context* src, gc_context* dst, const gc_ddc_par
   a.ntaps = p->ntaps;
   a.tile = (int)pl.tile;
   a.dst_mode = gc_record_mode(dst);
-  a.vec_ok = ((uintptr_t)src->d_if & 15u) == 0 ? 1 : 0;
   gc_with_mode(gc_record_mode(src), [&](auto m) {
     hipLaunchKernelGGL(ddc_kernel<decltype(m)::value>, dim3((unsigned int)pl.ntiles), dim3(kDdcWG), (size_t)pl.lds_bytes, src->stream, a);
   });

@@ -6,7 +6,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "gc_internal.h"
+#include "record_check.h"
 
 constexpr int kDdcWG = 256;                 // threads of a workgroup
 constexpr int kDdcChains = 4;               // outputs a thread carries at most: independent float64 add chains that share every tap read
@@ -21,8 +21,6 @@ constexpr int kDdcMaxBps = 4;               // bytes per sample of the widest fo
 // 15 behind
 constexpr long long kDdcStageSlack = 32;
 constexpr double kDdcTwoPi = 6.283185307179586;
-
-inline int ddc_bytes_per_sample(const gc_context* c) { return (c->if_dtype == GC_I16 ? 2 : 1) * (c->if_layout == GC_REAL ? 1 : 2); }
 
 inline long long ddc_taps_bytes(int ntaps) { return 16LL * ntaps; }
 // input samples under `outs` consecutive outputs: the first output's oldest to the last output's newest
@@ -133,17 +131,15 @@ inline int ddc_check(const gc_context* src, const gc_context* dst, const gc_ddc_
     gc_set_error("gc_downconvert: the destination is on another device");
     return GC_E_INVALID;
   }
-  const int sb = ddc_bytes_per_sample(src), db = ddc_bytes_per_sample(dst);
+  // not check_record_pair: dst may differ in format and length, and may not be the source
+  const int sb = gc_record_bps(src), db = gc_record_bps(dst);
   const uint64_t sbytes = src->if_nsamples * (uint64_t)sb, dbytes = dst->if_nsamples * (uint64_t)db;
   if (dst->d_if == src->d_if || (dst->d_if < src->d_if + sbytes && src->d_if < dst->d_if + dbytes)) {
     gc_set_error("gc_downconvert: the destination record is the source's or overlaps it");
     return GC_E_INVALID;
   }
-  const unsigned long long dhave = dst->if_nsamples, dfirst = (unsigned long long)p->dst_first;
-  if (dfirst > dhave || dhave - dfirst < (unsigned long long)p->noutputs) {
-    gc_set_error("gc_downconvert: %lld outputs from %lld end beyond the destination record (%llu samples)", (long long)p->noutputs, (long long)p->dst_first, dhave);
-    return GC_E_RANGE;
-  }
+  const int rc = check_record_range("gc_downconvert (destination)", dst, (long long)p->dst_first, (long long)p->noutputs);
+  if (rc) return rc;
   // the last output's oldest sample: first_sample + (noutputs - 1) D - (T - 1), in 128 bits (noutputs is bounded by dst's record only)
   const __int128 oldest = (__int128)p->first_sample + (__int128)(p->noutputs - 1) * p->decim - (p->ntaps - 1);
   if (oldest >= (__int128)src->if_nsamples) {

@@ -7,9 +7,8 @@
 //                          bitmap word joined by shuffles, one store per word.  Samples outside the range give zero bits.
 //   excise_blank_kernel    the tile's words and a halo of the longest guard on either side into LDS, an exclusive prefix count of hot
 //                          bits over them; sample n is blanked iff the count over [n - after, n + before] is not zero: two prefix
-//                          reads and two masked popcounts.  A thread's 16 bytes are loaded, blanked and stored as cancel_apply_kernel
-//                          does (one 16-byte store; byte by byte for the record's last, partial 16 bytes - a record's base is always
-//                          16-byte aligned: gc_attach_if takes 32-byte aligned addresses only); in place, 16 bytes without a blanked sample are neither read nor written.  The tile's
+//                          reads and two masked popcounts.  A thread's 16 bytes are loaded, blanked and stored as a RecVec
+//                          (record_fmt.h); in place, 16 bytes without a blanked sample are neither read nor written.  The tile's
 //                          blanked bits are kept in LDS and folded into its summary: ones at its head, ones at its tail, longest run,
 //                          runs, blanked and hot samples.
 //   excise_combine_kernel  folds the tiles' summaries in tile order - a run that crosses a tile boundary is the tail of one joined to
@@ -18,22 +17,20 @@
 //
 // gc_excise_bins: a gain per frequency bin, by weighted overlap-add (sine window, half-overlapping segments) on the acquisition's
 // float32 transform.  The segment list is cut into tiles (excise_plan.h); per tile
-//   excise_gather_kernel   converts and windows the tile's segments into float2 rows, zero outside the range (the probe's gather
-//                          with the padding added),
+//   gather_rows            converts and windows the tile's segments into float2 rows, zero outside the range (acq_fft.hip),
 //   transform_rows         forward: the pass pair the probe runs (acq_fft.hip),
 //   excise_gain_kernel     multiplies by the gain and moves storage position [k1][k2] to natural bin k1 + n1 k2, where the inverse
 //                          pair expects it,
 //   transform_rows         inverse = 1,
 //   excise_add_kernel      one thread per 16 bytes of record: y = s v of the earlier segment's second half + s v of the later
-//                          segment's first half, rint, clamp, one 16-byte store (byte by byte where cancel_apply_kernel goes byte by
-//                          byte); y itself to a float2 buffer of the range when the caller asks for it,
+//                          segment's first half, quantised into a RecVec; y itself to a float2 buffer of the range when the caller
+//                          asks for it,
 //   excise_carry_kernel    keeps s v of the second half of the tile's last segment for the next tile: its samples are not gathered
 //                          again after they were overwritten (in place), and a sample's value is the same sum wherever the cut falls.
 // Out of place the record is copied first and the add kernel works on the copy.
 // The unit's buffers are its own (ExciseState, kept in gc_context::excise, grow-only, released by gc_destroy).
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 #include "acq_internal.h"
 #include "excise_plan.h"
@@ -85,25 +82,11 @@ struct ExciseArgs {
   unsigned long long* bitmap;  // word kExciseHalo + w holds the samples base + 64 w ..
   TileRuns* tiles;
   long long base, first, end;  // record samples: bit 0 of the bitmap, the range
-  long long rec_nsamples;
+  long long rec_bytes;         // of the record
   long long threshold2;
   int before, after;
   int in_place;
 };
-
-// the 16 bytes of vector v (samples n0 .. n0 + cnt - 1 of the record) as four words
-__device__ __forceinline__ void load16(const uint8_t* rec, long long v, int nbytes, bool whole, uint32_t (&w)[4]) {
-  if (whole) {
-    const uint4 q = *(const uint4*)(rec + v * 16);
-    w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
-  } else {
-    w[0] = w[1] = w[2] = w[3] = 0u;
-    const uint8_t* s = rec + v * 16;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (k < nbytes) w[k >> 2] |= (uint32_t)s[k] << (8 * (k & 3));
-  }
-}
 
 // the bits of the lanes that share a bitmap word (64 / per16 consecutive lanes), in every one of them
 template <int PER16>
@@ -125,20 +108,17 @@ __global__ __launch_bounds__(kExciseWG) void excise_mark_kernel(const ExciseArgs
 #pragma unroll 1
   for (int k = 0; k < kVecs; ++k) {
     const int q = k * kExciseWG + tid;
-    const long long n0 = tile0 + (long long)q * P, v = n0 / P;
+    const long long n0 = tile0 + (long long)q * P;
     unsigned int mask = 0u;
-    if (n0 + P > p.first && n0 < p.end) {  // p.end <= rec_nsamples: at least one sample of the record
-      const int cnt = (int)min((long long)P, p.rec_nsamples - n0);
-      uint32_t w[4];
-      load16(p.src, v, cnt * F::bps, cnt == P, w);
+    if (n0 + P > p.first && n0 < p.end) {  // p.end is inside the record: at least one sample of it
+      RecVec<MODE> d;
+      d.load(p.src, n0 * F::bps, p.rec_bytes);
 #pragma unroll
       for (int s = 0; s < P; ++s) {
-        const int bit = s * F::bps * 8;
-        const uint32_t raw = w[bit >> 5] >> (bit & 31);
-        const long long c0 = F::value_bytes == 1 ? (long long)(signed char)(raw & 0xffu) : (long long)(short)(raw & 0xffffu);
-        const long long c1 = F::values == 1 ? 0 : F::value_bytes == 1 ? (long long)(signed char)((raw >> 8) & 0xffu) : (long long)(short)(raw >> 16);
+        int c0, c1;
+        d.get(s, c0, c1);
         const long long n = n0 + s;
-        if (n >= p.first && n < p.end && c0 * c0 + c1 * c1 > p.threshold2) mask |= 1u << s;
+        if (n >= p.first && n < p.end && (long long)c0 * c0 + (long long)c1 * c1 > p.threshold2) mask |= 1u << s;
       }
     }
     const unsigned long long word = join_word<P>(mask, lane);
@@ -187,7 +167,7 @@ __global__ __launch_bounds__(kExciseWG) void excise_blank_kernel(const ExciseArg
 #pragma unroll 1
   for (int k = 0; k < kVecs; ++k) {
     const int q = k * kExciseWG + tid;
-    const long long n0 = tile0 + (long long)q * P, v = n0 / P;
+    const long long n0 = tile0 + (long long)q * P;
     unsigned int mask = 0u;
     const bool mine = n0 + P > p.first && n0 < p.end;  // the vector holds a sample of the range
     if (mine) {
@@ -199,24 +179,12 @@ __global__ __launch_bounds__(kExciseWG) void excise_blank_kernel(const ExciseArg
       }
     }
     if (mine && (mask != 0u || !p.in_place)) {
-      const int cnt = (int)min((long long)P, p.rec_nsamples - n0);
-      const bool whole = cnt == P;
-      uint32_t d[4];
-      load16(p.src, v, cnt * F::bps, whole, d);
+      RecVec<MODE> d;
+      d.load(p.src, n0 * F::bps, p.rec_bytes);
 #pragma unroll
-      for (int s = 0; s < P; ++s) {
-        constexpr uint32_t smask = F::bps == 4 ? 0xffffffffu : (1u << (F::bps * 8 % 32)) - 1u;
-        const int bit = s * F::bps * 8;
-        if (mask >> s & 1u) d[bit >> 5] &= ~(smask << (bit & 31));
-      }
-      if (whole) {
-        *(uint4*)(p.dst + v * 16) = make_uint4(d[0], d[1], d[2], d[3]);
-      } else {
-        uint8_t* o = p.dst + v * 16;
-#pragma unroll
-        for (int b = 0; b < 16; ++b)
-          if (b < cnt * F::bps) o[b] = (uint8_t)(d[b >> 2] >> (8 * (b & 3)));
-      }
+      for (int s = 0; s < P; ++s)
+        if (mask >> s & 1u) d.zero(s);
+      d.store(p.dst, n0 * F::bps, p.rec_bytes);
     }
     const unsigned long long word = join_word<P>(mask, lane);
     if ((lane & (64 / P - 1)) == 0) bl[(q * P) >> 6] = word;
@@ -280,32 +248,6 @@ __global__ __launch_bounds__(kExciseWG) void excise_combine_kernel(const TileRun
 
 // ---- gc_excise_bins ------------------------------------------------------------------------------------------------------------------
 
-// component `index` of the record in file order
-template <bool I16>
-__device__ __forceinline__ int file_component(const uint8_t* __restrict__ base, long long index) {
-  if constexpr (I16) return (int)reinterpret_cast<const int16_t*>(base)[index];
-  else return (int)reinterpret_cast<const int8_t*>(base)[index];
-}
-
-// rows[t][n] = w[n] * (float)x of segment g0 + t: range sample (g0 + t - 1) H + n, zero outside [0, nsamples); one workgroup per 256
-// consecutive n of one segment
-template <bool I16, int NC>
-__global__ __launch_bounds__(kExciseWG) void excise_gather_kernel(const uint8_t* __restrict__ rec, long long first_sample, long long nsamples, long long g0,
-                                                                   int nfft, int blocks_per_row, const float* __restrict__ win, float2* __restrict__ rows) {
-  const long long t = blockIdx.x / (unsigned)blocks_per_row;
-  const int n = (int)(blockIdx.x - (unsigned)(t * blocks_per_row)) * kExciseWG + (int)threadIdx.x;
-  if (n >= nfft) return;
-  const long long m = (g0 + t - 1) * (long long)(nfft / 2) + n;
-  float x0 = 0.0f, x1 = 0.0f;
-  if (m >= 0 && m < nsamples) {
-    const long long s = first_sample + m;
-    x0 = (float)file_component<I16>(rec, s * NC);
-    if constexpr (NC == 2) x1 = (float)file_component<I16>(rec, s * NC + 1);
-  }
-  const float w = win[n];
-  rows[t * nfft + n] = make_float2(w * x0, w * x1);
-}
-
 // out[t][b] = gain[b] * in[t][storage position of bin b], b = k1 + n1 k2 at position k1 n2 + k2
 __global__ __launch_bounds__(kExciseWG) void excise_gain_kernel(const float2* __restrict__ in, float2* __restrict__ out, const float* __restrict__ gain,
                                                                  int nfft, int n1, int n2, int blocks_per_row) {
@@ -325,7 +267,7 @@ struct AddArgs {
   uint8_t* rec;         // the destination record (out of place: a copy of the source)
   float2* values;       // [nsamples] or null
   long long first, m0, m1;  // the range's first record sample; the range samples this tile finishes
-  long long rec_nsamples;
+  long long rec_bytes;      // of the record
   long long g0;
   int nfft, n1, n2;
 };
@@ -343,11 +285,9 @@ __global__ __launch_bounds__(kExciseWG) void excise_add_kernel(const AddArgs p, 
   constexpr int P = F::per16;
   const long long i = (long long)blockIdx.x * kExciseWG + threadIdx.x;
   if (i >= nvec) return;
-  const long long v = v0 + i, n0 = v * P;
-  const int cnt = (int)min((long long)P, p.rec_nsamples - n0);
-  const bool whole = cnt == P;
-  uint32_t d[4];
-  load16(p.rec, v, cnt * F::bps, whole, d);
+  const long long n0 = (v0 + i) * P;
+  RecVec<MODE> d;
+  d.load(p.rec, n0 * F::bps, p.rec_bytes);
   const int H = p.nfft / 2;
 #pragma unroll
   for (int s = 0; s < P; ++s) {
@@ -359,35 +299,15 @@ __global__ __launch_bounds__(kExciseWG) void excise_add_kernel(const AddArgs p, 
     const float2 hi = scaled(p, k0 + 1 - p.g0, r);
     const float y_re = lo.x + hi.x, y_im = lo.y + hi.y;
     if (p.values) p.values[m] = make_float2(y_re, y_im);
-    const int o0 = (int)fminf(fmaxf(rintf(y_re), (float)F::lo), (float)F::hi);
-    const int o1 = (int)fminf(fmaxf(rintf(y_im), (float)F::lo), (float)F::hi);
-    constexpr uint32_t vmask = F::value_bytes == 1 ? 0xffu : 0xffffu;
-    constexpr uint32_t smask = F::bps == 4 ? 0xffffffffu : (1u << (F::bps * 8 % 32)) - 1u;
-    uint32_t bits = (uint32_t)o0 & vmask;
-    if constexpr (F::values == 2) bits |= ((uint32_t)o1 & vmask) << (8 * F::value_bytes);
-    const int bit = s * F::bps * 8;
-    d[bit >> 5] = (d[bit >> 5] & ~(smask << (bit & 31))) | (bits << (bit & 31));
+    d.put(s, quantise<MODE>(y_re), quantise<MODE>(y_im));
   }
-  if (whole) {
-    *(uint4*)(p.rec + v * 16) = make_uint4(d[0], d[1], d[2], d[3]);
-  } else {
-    uint8_t* o = p.rec + v * 16;
-#pragma unroll
-    for (int b = 0; b < 16; ++b)
-      if (b < cnt * F::bps) o[b] = (uint8_t)(d[b >> 2] >> (8 * (b & 3)));
-  }
+  d.store(p.rec, n0 * F::bps, p.rec_bytes);
 }
 
 // carry[r] = s[H + r] * v[H + r] of row `row`
 __global__ __launch_bounds__(kExciseWG) void excise_carry_kernel(const AddArgs p, long long row, float2* __restrict__ carry) {
   const int H = p.nfft / 2, r = (int)(blockIdx.x * kExciseWG + threadIdx.x);
   if (r < H) carry[r] = scaled(p, row, H + r);
-}
-
-int excise_nomem(const char* fn) {
-  (void)hipGetLastError();
-  gc_set_error("%s: device allocation failed", fn);
-  return GC_E_NOMEM;
 }
 
 }  // namespace
@@ -411,16 +331,12 @@ extern "C" int gc_excise_pulses(gc_context* src, gc_context* dst, const gc_excis
   // nothing has been written up to here
   GC_HIP(hipSetDevice(src->device));
   if (dst != src) GC_HIP(hipStreamSynchronize(dst->stream));  // the destination's own pending work comes first
-  ExciseState* s = static_cast<ExciseState*>(src->excise);
-  if (!s) {
-    s = new (std::nothrow) ExciseState();
-    if (!s) return excise_nomem("gc_excise_pulses");
-    src->excise = s;
-  }
+  ExciseState* s = gc_unit_state<ExciseState>(src->excise);
+  if (!s) return gc_nomem("gc_excise_pulses");
   if (gc_buf_reserve(s->bitmap, (size_t)pl.words * sizeof(unsigned long long), false) != hipSuccess ||
       gc_buf_reserve(s->tiles, (size_t)pl.ntiles * sizeof(TileRuns), false) != hipSuccess ||
       gc_buf_reserve(s->stats, 4 * sizeof(long long), false) != hipSuccess)
-    return excise_nomem("gc_excise_pulses");
+    return gc_nomem("gc_excise_pulses");
   const long long first = (long long)p->first_sample, end = first + (long long)p->nsamples;
   unsigned long long* const bitmap = (unsigned long long*)s->bitmap.p;
   const size_t back = (size_t)kExciseHalo + (size_t)pl.ntiles * kExciseTileWords;  // the mark kernel writes every word in between
@@ -440,7 +356,7 @@ extern "C" int gc_excise_pulses(gc_context* src, gc_context* dst, const gc_excis
   a.base = pl.base;
   a.first = first;
   a.end = end;
-  a.rec_nsamples = (long long)src->if_nsamples;
+  a.rec_bytes = (long long)src->if_nsamples * pl.bps;
   a.threshold2 = (long long)p->threshold2;
   a.before = p->before;
   a.after = p->after;
@@ -470,10 +386,8 @@ extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_
   int rc = excise_check_bins(src, dst, p, gain);
   if (rc) return rc;
   gcacq::Plan plan;
-  if (!gcacq::make_plan(p->nfft, &plan)) {
-    gc_set_error("acquisition: FFT size %d is not of the form 2^a 3^b 5^c (or its factors are too large)", p->nfft);
-    return GC_E_UNSUPPORTED;
-  }
+  rc = gcacq::plan_or_refuse(p->nfft, &plan);
+  if (rc) return rc;
   ExciseBinsPlan pl;
   rc = excise_check_bins_state(src, dst, p, ExciseBudget(), &pl);
   if (rc) return rc;
@@ -482,43 +396,35 @@ extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_
   // nothing has been written up to here
   GC_HIP(hipSetDevice(src->device));
   if (dst != src) GC_HIP(hipStreamSynchronize(dst->stream));  // the destination's own pending work comes first
-  ExciseState* s = static_cast<ExciseState*>(src->excise);
-  if (!s) {
-    s = new (std::nothrow) ExciseState();
-    if (!s) return excise_nomem("gc_excise_bins");
-    src->excise = s;
-  }
+  ExciseState* s = gc_unit_state<ExciseState>(src->excise);
+  if (!s) return gc_nomem("gc_excise_bins");
   const size_t rows_bytes = (size_t)std::min(pl.tile, pl.K) * (size_t)nfft * sizeof(float2);
   if (gc_buf_reserve(s->rows_a, rows_bytes, false) != hipSuccess || gc_buf_reserve(s->rows_b, rows_bytes, false) != hipSuccess ||
       gc_buf_reserve(s->gain, (size_t)nfft * sizeof(float), false) != hipSuccess || gc_buf_reserve(s->carry, (size_t)H * sizeof(float2), false) != hipSuccess ||
       (values && gc_buf_reserve(s->values, (size_t)nsamples * sizeof(float2), false) != hipSuccess))
-    return excise_nomem("gc_excise_bins");
+    return gc_nomem("gc_excise_bins");
   if (s->n != nfft) {  // the plan, the twiddle table, the window w and the scale s of an nfft-point excision
     s->n = 0;
     if (gc_buf_reserve(s->tw, (size_t)nfft * sizeof(float2), false) != hipSuccess || gc_buf_reserve(s->win, 2 * (size_t)nfft * sizeof(float), false) != hipSuccess)
-      return excise_nomem("gc_excise_bins");
+      return gc_nomem("gc_excise_bins");
     const double pi = 3.14159265358979323846;
-    std::vector<float2> tw((size_t)nfft);
     std::vector<float> win(2 * (size_t)nfft);
     for (int k = 0; k < nfft; ++k) {
-      const double ang = -2.0 * pi * (double)k / (double)nfft;
-      tw[(size_t)k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
       const float w = (float)std::sin(pi * ((double)k + 0.5) / (double)nfft);
       win[(size_t)k] = w;
       win[(size_t)nfft + (size_t)k] = (float)((double)w / (double)nfft);
     }
-    GC_HIP(hipMemcpyAsync(s->tw.p, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, src->stream));
     GC_HIP(hipMemcpyAsync(s->win.p, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice, src->stream));
-    GC_HIP(hipStreamSynchronize(src->stream));
+    rc = gcacq::upload_twiddles(src, nfft, (float2*)s->tw.p);  // waits for the stream: win is gone below
+    if (rc) return rc;
     s->plan = plan;
     s->n = nfft;
   }
   GC_HIP(hipMemcpyAsync(s->gain.p, gain, (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, src->stream));
-  const int bps = excise_bytes_per_sample(src);
+  const int bps = gc_record_bps(src);
   if (dst->d_if != src->d_if)  // out of place: the add kernel works on a copy
     GC_HIP(hipMemcpyAsync(dst->d_if, src->d_if, (size_t)src->if_nsamples * (size_t)bps, hipMemcpyDeviceToDevice, src->stream));
   const int bpr = (nfft + kExciseWG - 1) / kExciseWG, per16 = 16 / bps;
-  const bool i16 = src->if_dtype == GC_I16, real = src->if_layout == GC_REAL;
   float2 *const rows_a = (float2*)s->rows_a.p, *const rows_b = (float2*)s->rows_b.p;
   const float* const win = (const float*)s->win.p;
   AddArgs a;
@@ -528,18 +434,16 @@ extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_
   a.rec = dst->d_if;
   a.values = values ? (float2*)s->values.p : nullptr;
   a.first = first;
-  a.rec_nsamples = (long long)src->if_nsamples;
+  a.rec_bytes = (long long)src->if_nsamples * bps;
   a.nfft = nfft;
   a.n1 = plan.n1;
   a.n2 = plan.n2;
+  const gcacq::RowGather segs = {first, nsamples, H, pl.K, H};  // segment k covers the range samples [(k - 1) H, (k + 1) H): one span of K segments
   for (ExciseTile t; excise_next_tile(pl, t);) {
     const dim3 grid((unsigned int)(t.n * bpr)), wg(kExciseWG);
     // the gather reads the SOURCE: in place its samples are this tile's and later ones', which no add kernel has written yet
-    if (i16 && real) hipLaunchKernelGGL((excise_gather_kernel<true, 1>), grid, wg, 0, src->stream, src->d_if, first, nsamples, t.g0, nfft, bpr, win, rows_a);
-    else if (i16) hipLaunchKernelGGL((excise_gather_kernel<true, 2>), grid, wg, 0, src->stream, src->d_if, first, nsamples, t.g0, nfft, bpr, win, rows_a);
-    else if (real) hipLaunchKernelGGL((excise_gather_kernel<false, 1>), grid, wg, 0, src->stream, src->d_if, first, nsamples, t.g0, nfft, bpr, win, rows_a);
-    else hipLaunchKernelGGL((excise_gather_kernel<false, 2>), grid, wg, 0, src->stream, src->d_if, first, nsamples, t.g0, nfft, bpr, win, rows_a);
-    GC_HIP(hipGetLastError());
+    rc = gcacq::gather_rows(src, segs, t.g0, t.n, nfft, win, rows_a);
+    if (rc) return rc;
     rc = gcacq::transform_rows(src, s->plan, (const float2*)s->tw.p, rows_a, rows_b, t.n, 0);
     if (rc) return rc;
     hipLaunchKernelGGL(excise_gain_kernel, grid, wg, 0, src->stream, (const float2*)rows_a, rows_b, (const float*)s->gain.p, nfft, plan.n1, plan.n2, bpr);

@@ -2,12 +2,12 @@
 // the argument checks; how the blanker's range is laid over the hot-sample bitmap and cut into the tiles its kernels take one workgroup
 // each; the segment count of the spectral excision and the cut of its segment list into tiles whose rows fit a byte budget.  Nothing
 // here calls HIP, allocates on the device or launches; tests/excise_plan_shim.hip runs all of it without a device.  From the two
-// contexts the checks read d_if, device, if_nsamples, if_dtype and if_layout.  The one refusal that is not decided here is the
+// contexts the checks read d_if, device, if_nsamples, if_dtype and if_layout (record_check.h: the pair of records, the range).  The one refusal that is not decided here is the
 // transform planner's (make_plan, acq_fft.hip: GC_E_UNSUPPORTED).
 #pragma once
 #include <cstdint>
 
-#include "gc_internal.h"
+#include "record_check.h"
 
 constexpr int kExciseTile = 16384;                          // samples of the bitmap per workgroup of the mark and the blank kernel
 constexpr int kExciseTileWords = kExciseTile / 64;          // 64 samples per bitmap word
@@ -23,37 +23,6 @@ struct ExcisePulsePlan {
   long long words = 0;   // of the bitmap: kExciseHalo + ntiles * kExciseTileWords + kExciseHalo + 1 (the blank kernel's last prefix count reads one word past the halo)
   int bps = 0;           // bytes per sample
 };
-
-inline int excise_bytes_per_sample(const gc_context* c) { return (c->if_dtype == GC_I16 ? 2 : 1) * (c->if_layout == GC_REAL ? 1 : 2); }
-
-// What gc_cancel asks of its two records, in its order: GC_E_STATE without a record, GC_E_INVALID for a destination that differs from
-// the source in device, sample count, dtype or layout, or overlaps it without being it
-inline int excise_check_records(const char* fn, const gc_context* src, const gc_context* dst) {
-  if (!src->d_if || !dst->d_if) {
-    gc_set_error("%s: no IF record loaded", fn);
-    return GC_E_STATE;
-  }
-  if (dst->device != src->device || dst->if_nsamples != src->if_nsamples || dst->if_dtype != src->if_dtype || dst->if_layout != src->if_layout) {
-    gc_set_error("%s: the destination record differs from the source's in device, sample count, dtype or layout", fn);
-    return GC_E_INVALID;
-  }
-  const uint64_t bytes = src->if_nsamples * (uint64_t)excise_bytes_per_sample(src);
-  if (dst->d_if != src->d_if && dst->d_if < src->d_if + bytes && src->d_if < dst->d_if + bytes) {
-    gc_set_error("%s: the destination record overlaps the source without being the same record", fn);
-    return GC_E_INVALID;
-  }
-  return GC_OK;
-}
-
-// the range [first_sample, first_sample + nsamples) against the record: GC_E_RANGE
-inline int excise_check_range(const char* fn, const gc_context* src, long long first_sample, long long nsamples) {
-  const unsigned long long have = src->if_nsamples, first = (unsigned long long)first_sample;
-  if (first > have || have - first < (unsigned long long)nsamples) {
-    gc_set_error("%s: %lld samples from %lld end beyond the record (%llu samples)", fn, nsamples, first_sample, have);
-    return GC_E_RANGE;
-  }
-  return GC_OK;
-}
 
 inline ExcisePulsePlan excise_pulse_plan(long long first_sample, long long nsamples, int bps) {
   ExcisePulsePlan pl;
@@ -77,11 +46,11 @@ inline int excise_check_pulses(const gc_context* src, const gc_context* dst, con
                  (long long)p->nsamples, (long long)p->threshold2, p->before, p->after);
     return GC_E_INVALID;
   }
-  int rc = excise_check_records("gc_excise_pulses", src, dst);
+  int rc = check_record_pair("gc_excise_pulses", src, dst);
   if (rc) return rc;
-  rc = excise_check_range("gc_excise_pulses", src, (long long)p->first_sample, (long long)p->nsamples);
+  rc = check_record_range("gc_excise_pulses", src, (long long)p->first_sample, (long long)p->nsamples);
   if (rc) return rc;
-  *pl = excise_pulse_plan((long long)p->first_sample, (long long)p->nsamples, excise_bytes_per_sample(src));
+  *pl = excise_pulse_plan((long long)p->first_sample, (long long)p->nsamples, gc_record_bps(src));
   return GC_OK;
 }
 
@@ -151,9 +120,9 @@ inline int excise_check_bins(const gc_context* src, const gc_context* dst, const
 
 // ... and what the contexts must hold for them: GC_E_STATE, GC_E_INVALID (a destination that does not match), GC_E_RANGE; then the plan
 inline int excise_check_bins_state(const gc_context* src, const gc_context* dst, const gc_excise_bins_params* p, const ExciseBudget& b, ExciseBinsPlan* pl) {
-  int rc = excise_check_records("gc_excise_bins", src, dst);
+  int rc = check_record_pair("gc_excise_bins", src, dst);
   if (rc) return rc;
-  rc = excise_check_range("gc_excise_bins", src, (long long)p->first_sample, (long long)p->nsamples);
+  rc = check_record_range("gc_excise_bins", src, (long long)p->first_sample, (long long)p->nsamples);
   if (rc) return rc;
   pl->H = p->nfft / 2;
   pl->K = excise_segments((long long)p->nsamples, p->nfft);

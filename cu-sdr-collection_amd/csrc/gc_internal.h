@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -150,7 +151,8 @@ struct gc_context {
   int compute_units = 0;
   char device_name[128] = {0};
 
-  // IF buffer
+  // IF buffer.  d_if is always 32-byte aligned: it is hipMalloc's (gc_alloc_if) or an address gc_attach_if accepted, and that call
+  // refuses one that is not.  The kernels that take a record 16 bytes at a time (record_fmt.h RecVec) rely on it.
   uint8_t* d_if = nullptr;
   bool if_owned = false;
   uint64_t if_nsamples = 0;
@@ -276,7 +278,22 @@ int gc_track_device_window(gc_context* ctx, const gc_track_params* p, int nch, c
 // trackResults.CNo.VSMValue of finished records on the host (the host-closed loops; the device loop estimates in one pass inside devloop_post - both end in gcorr::cno_ratio, devloop.h)
 void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const double* out, const int32_t* epochs_done);
 
-int gc_bytes_per_sample(int dtype, int layout);
+inline int gc_bytes_per_sample(int dtype, int layout) { return (layout == GC_REAL ? 1 : 2) * (dtype == GC_I16 ? 2 : 1); }
+
+// The state a unit keeps in its void* slot of the context (probe, cancel, excise, ddc), made on first use; nullptr: no memory
+template <class S>
+S* gc_unit_state(void*& slot) {
+  if (!slot) slot = new (std::nothrow) S();
+  return static_cast<S*>(slot);
+}
+// ... and what the unit returns after an allocation that failed, on the host or on the device (whose sticky error is cleared, so that
+// the next call's GC_HIP(hipGetLastError()) does not report it)
+inline int gc_nomem(const char* fn) {
+  (void)hipGetLastError();
+  gc_set_error("%s: device allocation failed", fn);
+  return GC_E_NOMEM;
+}
+
 void gc_acq_free(gc_context* ctx);  // acq_coarse.hip
 void gc_probe_free(gc_context* ctx);  // probe.hip
 void gc_cancel_free(gc_context* ctx);  // cancel.hip

@@ -19,11 +19,6 @@ void gc_set_error(const char* fmt, ...) {
   g_last_error = buf;
 }
 
-int gc_bytes_per_sample(int dtype, int layout) {
-  const int comp = (layout == GC_REAL) ? 1 : 2;
-  return comp * (dtype == GC_I16 ? 2 : 1);
-}
-
 extern "C" {
 
 const char* gc_last_error(void) { return g_last_error.c_str(); }

@@ -3,17 +3,17 @@
 // :146-163 hist(., -128:128) and dmax), computed where the record lives.  DESIGN.md 4.10.
 //
 // Spectrum: the (span, segment) list is cut into tiles (probe_plan.h); per tile
-//   probe_gather_kernel   converts and windows the tile's segments into float2 rows,
-//   probe_transform       runs the acquisition's two pass kernels over the rows (the sequence gc_debug_fft launches),
+//   gather_rows           converts and windows the tile's segments into float2 rows (acq_fft.hip, next to the transform it feeds),
+//   transform_rows        runs the acquisition's two pass kernels over the rows (the sequence gc_debug_fft launches),
 //   probe_power_kernel    adds |X|^2 of the tile's segments, in segment order, into the float64 accumulator of (span, bin).
 // Histogram: probe_hist_kernel counts into per-wave LDS histograms and writes one partial row per workgroup,
 //   probe_hist_combine_kernel adds the rows in 64-bit, one workgroup per bin.
 // The probe's plan, twiddle table, window, rows and accumulators are its own (ProbeState, kept in gc_context::probe): nothing of the
 // acquisition's scratch, the conditioned signal or the bank's buffers is read, written or reallocated.
-#include <new>
-
+// A sample's components in file order are record_fmt.h's (file_sample, gc_with_file_mode); the range check is record_check.h's.
 #include "acq_internal.h"
 #include "probe_plan.h"
+#include "record_fmt.h"
 
 using namespace gcacq;
 
@@ -30,30 +30,6 @@ struct ProbeState {
   double sumw2 = 0.0;
   GcBuf tw, win, rows_a, rows_b, acc, hist_part, hist_max, hist_out;
 };
-
-// component c of sample s in file order
-template <bool I16>
-__device__ __forceinline__ int probe_component(const uint8_t* __restrict__ base, long long index) {
-  if constexpr (I16) return (int)reinterpret_cast<const int16_t*>(base)[index];
-  else return (int)reinterpret_cast<const int8_t*>(base)[index];
-}
-
-// rows[t][n] = (float)w[n] * (float)x of segment g0 + t, one workgroup per 256 consecutive n of one segment
-template <bool I16, int NC>
-__global__ __launch_bounds__(kProbeThreads) void probe_gather_kernel(const uint8_t* __restrict__ rec, long long first_sample, long long nsamples,
-                                                                      long long step, long long K, long long g0, int nfft, int blocks_per_row,
-                                                                      const float* __restrict__ win, float2* __restrict__ rows) {
-  const long long t = blockIdx.x / (unsigned)blocks_per_row;
-  const int n = (int)(blockIdx.x - (unsigned)(t * blocks_per_row)) * kProbeThreads + (int)threadIdx.x;
-  if (n >= nfft) return;
-  const long long g = g0 + t, span = g / K, k = g - span * K;
-  const long long s = first_sample + span * nsamples + k * step + n;
-  const float w = win[n];
-  const float x0 = (float)probe_component<I16>(rec, s * NC);
-  float x1 = 0.0f;
-  if constexpr (NC == 2) x1 = (float)probe_component<I16>(rec, s * NC + 1);
-  rows[t * nfft + n] = make_float2(w * x0, NC == 2 ? w * x1 : 0.0f);
-}
 
 // One thread per (span of the tile, storage position): |X|^2 of the span's segments in this tile, in segment order, added in float64 to
 // what the span's earlier tiles left (probe_span_range: carried when the span began before this tile), written to the natural bin
@@ -81,7 +57,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_power_kernel(const float2
 
 // Counts of samples [s0, s0 + per_wg) of the range (cut at nsamples) in a private histogram per wave - a noise-like record hits a few
 // dozen bins, and four waves on one LDS row would queue on them - then the workgroup's partial row and its largest c0^2 + c1^2.
-template <bool I16, int NC>
+template <int MODE>
 __global__ __launch_bounds__(kProbeThreads) void probe_hist_kernel(const uint8_t* __restrict__ rec, long long first_sample, long long nsamples,
                                                                     long long per_wg, unsigned int* __restrict__ part,
                                                                     long long* __restrict__ part_max) {
@@ -93,12 +69,11 @@ __global__ __launch_bounds__(kProbeThreads) void probe_hist_kernel(const uint8_t
   const long long lo = (long long)blockIdx.x * per_wg, hi = lo + per_wg < nsamples ? lo + per_wg : nsamples;
   long long m = 0;
   for (long long i = lo + tid; i < hi; i += kProbeThreads) {
-    const long long s = first_sample + i;
-    const int c0 = probe_component<I16>(rec, s * NC);
+    int c0, c1;
+    gcorr::file_sample<MODE>(rec, first_sample + i, c0, c1);
     atomicAdd(&h[wave][min(max(c0, -128), 128) + 128], 1u);
     long long n2 = (long long)c0 * c0;
-    if constexpr (NC == 2) {
-      const int c1 = probe_component<I16>(rec, s * NC + 1);
+    if constexpr (gcorr::Fmt<MODE>::values == 2) {
       atomicAdd(&h[wave][GC_PROBE_HIST_BINS + min(max(c1, -128), 128) + 128], 1u);
       n2 += (long long)c1 * c1;
     }
@@ -146,36 +121,20 @@ __global__ __launch_bounds__(kProbeThreads) void probe_hist_combine_kernel(const
   }
 }
 
-ProbeState* probe_state(gc_context* ctx) {
-  if (!ctx->probe) ctx->probe = new (std::nothrow) ProbeState();
-  return static_cast<ProbeState*>(ctx->probe);
-}
-
-int probe_nomem(const char* fn) {
-  (void)hipGetLastError();
-  gc_set_error("%s: device allocation failed", fn);
-  return GC_E_NOMEM;
-}
-
 // the plan and twiddle table of an n-point transform, the window of `kind`
 int probe_prepare(gc_context* ctx, ProbeState* s, const Plan& pl, int kind) {
   const int n = pl.n;
   if (s->n != n) {
     s->n = 0;
-    if (gc_buf_reserve(s->tw, (size_t)n * sizeof(float2), false) != hipSuccess) return probe_nomem("gc_probe_psd");
-    std::vector<float2> tw((size_t)n);
-    for (int k = 0; k < n; ++k) {
-      const double ang = -2.0 * 3.14159265358979323846 * (double)k / (double)n;
-      tw[(size_t)k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    }
-    GC_HIP(hipMemcpyAsync(s->tw.p, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
+    if (gc_buf_reserve(s->tw, (size_t)n * sizeof(float2), false) != hipSuccess) return gc_nomem("gc_probe_psd");
+    const int rc = upload_twiddles(ctx, n, (float2*)s->tw.p);
+    if (rc) return rc;
     s->plan = pl;
     s->n = n;
   }
   if (s->win_n != n || s->win_kind != kind) {
     s->win_n = 0;
-    if (gc_buf_reserve(s->win, (size_t)n * sizeof(float), false) != hipSuccess) return probe_nomem("gc_probe_psd");
+    if (gc_buf_reserve(s->win, (size_t)n * sizeof(float), false) != hipSuccess) return gc_nomem("gc_probe_psd");
     std::vector<float> w((size_t)n);
     double sum2 = 0.0;
     for (int k = 0; k < n; ++k) {
@@ -190,23 +149,6 @@ int probe_prepare(gc_context* ctx, ProbeState* s, const Plan& pl, int kind) {
     s->win_kind = kind;
   }
   return GC_OK;
-}
-
-// Forward transform of `nbatch` rows of a in place, b the intermediate; the result in storage order [k1][k2] (acq_fft.hip transform_rows)
-int probe_transform(gc_context* ctx, const ProbeState* s, float2* a_rows, float2* b_rows, long long nbatch) {
-  return transform_rows(ctx, s->plan, (const float2*)s->tw.p, a_rows, b_rows, nbatch, 0);
-}
-
-template <bool I16, int NC>
-void launch_gather(gc_context* ctx, const gc_probe_psd_params* p, const ProbePlan& pl, const ProbeTile& t, const ProbeState* s, int bpr) {
-  hipLaunchKernelGGL((probe_gather_kernel<I16, NC>), dim3((unsigned int)(t.n * bpr)), dim3(kProbeThreads), 0, ctx->stream, ctx->d_if,
-                     (long long)p->first_sample, (long long)p->nsamples, pl.step, pl.K, t.g0, p->nfft, bpr, (const float*)s->win.p, (float2*)s->rows_a.p);
-}
-
-template <bool I16, int NC>
-void launch_hist(gc_context* ctx, long long first_sample, long long nsamples, const ProbeHistGrid& g, const ProbeState* s) {
-  hipLaunchKernelGGL((probe_hist_kernel<I16, NC>), dim3((unsigned int)g.grid), dim3(kProbeThreads), 0, ctx->stream, ctx->d_if, first_sample, nsamples,
-                     g.per_wg, (unsigned int*)s->hist_part.p, (long long*)s->hist_max.p);
 }
 
 }  // namespace
@@ -225,33 +167,28 @@ extern "C" int gc_probe_psd(gc_context* ctx, const gc_probe_psd_params* p, doubl
   int rc = probe_check_args(ctx, p, psd);
   if (rc) return rc;
   Plan plan;
-  if (!make_plan(p->nfft, &plan)) {
-    gc_set_error("acquisition: FFT size %d is not of the form 2^a 3^b 5^c (or its factors are too large)", p->nfft);
-    return GC_E_UNSUPPORTED;
-  }
+  rc = plan_or_refuse(p->nfft, &plan);
+  if (rc) return rc;
   ProbePlan pl;
   rc = probe_check_state(ctx, p, ProbeBudget(), &pl);
   if (rc) return rc;
   GC_HIP(hipSetDevice(ctx->device));
-  ProbeState* s = probe_state(ctx);
-  if (!s) return probe_nomem("gc_probe_psd");
+  ProbeState* s = gc_unit_state<ProbeState>(ctx->probe);
+  if (!s) return gc_nomem("gc_probe_psd");
   const int nfft = p->nfft;
   const size_t cells = (size_t)p->nspans * (size_t)nfft;
   const size_t rows_bytes = (size_t)std::min(pl.tile, pl.total) * (size_t)nfft * sizeof(float2);
   if (gc_buf_reserve(s->rows_a, rows_bytes, false) != hipSuccess || gc_buf_reserve(s->rows_b, rows_bytes, false) != hipSuccess ||
       gc_buf_reserve(s->acc, cells * sizeof(double), false) != hipSuccess)
-    return probe_nomem("gc_probe_psd");
+    return gc_nomem("gc_probe_psd");
   rc = probe_prepare(ctx, s, plan, p->window);
   if (rc) return rc;
   const int bpr = (nfft + kProbeThreads - 1) / kProbeThreads;
-  const bool i16 = ctx->if_dtype == GC_I16, real = ctx->if_layout == GC_REAL;
+  const RowGather segs = {(long long)p->first_sample, (long long)p->nsamples, pl.step, pl.K, 0};
   for (ProbeTile t; probe_next_tile(pl, t);) {
-    if (i16 && real) launch_gather<true, 1>(ctx, p, pl, t, s, bpr);
-    else if (i16) launch_gather<true, 2>(ctx, p, pl, t, s, bpr);
-    else if (real) launch_gather<false, 1>(ctx, p, pl, t, s, bpr);
-    else launch_gather<false, 2>(ctx, p, pl, t, s, bpr);
-    GC_HIP(hipGetLastError());
-    rc = probe_transform(ctx, s, (float2*)s->rows_a.p, (float2*)s->rows_b.p, t.n);
+    rc = gather_rows(ctx, segs, t.g0, t.n, nfft, (const float*)s->win.p, (float2*)s->rows_a.p);
+    if (rc) return rc;
+    rc = transform_rows(ctx, s->plan, (const float2*)s->tw.p, (float2*)s->rows_a.p, (float2*)s->rows_b.p, t.n, 0);
     if (rc) return rc;
     const long long span0 = t.g0 / pl.K, span1 = (t.g0 + t.n - 1) / pl.K;
     hipLaunchKernelGGL(probe_power_kernel, dim3((unsigned int)((span1 - span0 + 1) * bpr)), dim3(kProbeThreads), 0, ctx->stream,
@@ -271,18 +208,17 @@ extern "C" int gc_probe_histogram(gc_context* ctx, int64_t first_sample, int64_t
   int rc = probe_check_histogram(ctx, (long long)first_sample, (long long)nsamples, counts);
   if (rc) return rc;
   GC_HIP(hipSetDevice(ctx->device));
-  ProbeState* s = probe_state(ctx);
-  if (!s) return probe_nomem("gc_probe_histogram");
+  ProbeState* s = gc_unit_state<ProbeState>(ctx->probe);
+  if (!s) return gc_nomem("gc_probe_histogram");
   const ProbeHistGrid g = probe_hist_grid((long long)nsamples);
   if (gc_buf_reserve(s->hist_part, (size_t)g.grid * kHistRow * sizeof(unsigned int), false) != hipSuccess ||
       gc_buf_reserve(s->hist_max, (size_t)g.grid * sizeof(long long), false) != hipSuccess ||
       gc_buf_reserve(s->hist_out, (size_t)(kHistRow + 1) * sizeof(unsigned long long), false) != hipSuccess)
-    return probe_nomem("gc_probe_histogram");
-  const bool i16 = ctx->if_dtype == GC_I16, real = ctx->if_layout == GC_REAL;
-  if (i16 && real) launch_hist<true, 1>(ctx, first_sample, nsamples, g, s);
-  else if (i16) launch_hist<true, 2>(ctx, first_sample, nsamples, g, s);
-  else if (real) launch_hist<false, 1>(ctx, first_sample, nsamples, g, s);
-  else launch_hist<false, 2>(ctx, first_sample, nsamples, g, s);
+    return gc_nomem("gc_probe_histogram");
+  gcorr::gc_with_file_mode(gcorr::gc_record_mode(ctx), [&](auto m) {
+    hipLaunchKernelGGL(probe_hist_kernel<decltype(m)::value>, dim3((unsigned int)g.grid), dim3(kProbeThreads), 0, ctx->stream, ctx->d_if,
+                       (long long)first_sample, (long long)nsamples, g.per_wg, (unsigned int*)s->hist_part.p, (long long*)s->hist_max.p);
+  });
   GC_HIP(hipGetLastError());
   hipLaunchKernelGGL(probe_hist_combine_kernel, dim3(kHistRow + 1), dim3(kProbeThreads), 0, ctx->stream,
                      (const unsigned int*)s->hist_part.p, (const long long*)s->hist_max.p, g.grid, (unsigned long long*)s->hist_out.p);

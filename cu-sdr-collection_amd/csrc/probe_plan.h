@@ -11,7 +11,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "gc_internal.h"
+#include "record_check.h"
 
 #if defined(__HIPCC__)
 #define GC_PROBE_HD __host__ __device__
@@ -117,12 +117,7 @@ inline int probe_check_histogram(const gc_context* ctx, long long first_sample, 
     gc_set_error("gc_probe_histogram: no IF record loaded");
     return GC_E_STATE;
   }
-  const unsigned long long have = ctx->if_nsamples, first = (unsigned long long)first_sample;
-  if (first > have || have - first < (unsigned long long)nsamples) {
-    gc_set_error("gc_probe_histogram: %lld samples from %lld end beyond the record (%llu samples)", nsamples, first_sample, have);
-    return GC_E_RANGE;
-  }
-  return GC_OK;
+  return check_record_range("gc_probe_histogram", ctx, first_sample, nsamples);
 }
 
 // workgroups of the histogram kernel and samples each takes: whole multiples of the workgroup's 256 threads, at most 2048 workgroups

@@ -10,8 +10,9 @@ holds two tile boundaries and three workgroups.
    sample, missing by one sample (two runs).  Out of place into a sentinel-filled record (outside the range the source's bytes
    arrive, the source stays as it was) and in place (the same bytes).
 2. No hot sample; every sample hot; the int16 pair (-32768, -32768), norm 2^31, against 2^31 - 1 and 2^31.
-3. A record that ends inside 16 bytes; a record attached inside another allocation (gc_attach_if takes 32-byte aligned addresses
-   only: an odd byte offset is refused there, which this test also holds).
+3. A record that ends inside 16 bytes, in all six formats; a record attached inside another allocation (gc_attach_if takes 32-byte
+   aligned addresses only: an odd byte offset is refused there, which this test also holds) - there gc_excise_bins and gc_cancel
+   in place as well: every call that writes a record 16 bytes at a time leaves the owner's bytes around it alone.
 4. Refusals: every one leaves dst (a sentinel fill) and the statistics untouched.
 5. Neighbours: a shift search and a spectrum give the same bytes with a gc_excise_pulses between their calls.
 6. A call on a context that shares the source's record works in place.
@@ -171,7 +172,7 @@ def test_the_squares_are_formed_in_64_bits(engine, dst_engine, fmt):
     assert st.hot == 5
 
 
-@pytest.mark.parametrize("fmt", ["i8_iq", "i16_real", "i16_iq"])
+@pytest.mark.parametrize("fmt", list(FORMATS))                         # int8 real: 13 samples in the last 16 bytes; int16 I/Q: 1
 def test_a_record_that_ends_inside_16_bytes(engine, dst_engine, fmt):
     dtype, layout = FORMATS[fmt]
     n = NS - 3
@@ -199,11 +200,19 @@ def test_a_record_attached_inside_another_allocation(engine, dst_engine):
         dst_engine.load_if(np.full_like(raw, 85), layout=layout)
         st = engine.excise_pulses(1, n - 1, THRESHOLD2, 63, 65, dst=dst_engine)
         assert np.array_equal(dst_engine.read_if(0, n), want) and _stats(st) == _stats(want_st)
+
+        def held(record):
+            after = owner.read_if(0, NS + 64)
+            assert np.array_equal(after[32:32 + 2 * n], record)
+            assert after[:32].tobytes() == whole[:32].tobytes() and after[32 + 2 * n:].tobytes() == whole[32 + 2 * n:].tobytes()   # the owner's bytes around it
         st = engine.excise_pulses(1, n - 1, THRESHOLD2, 63, 65)
         assert _stats(st) == _stats(want_st)
-        after = owner.read_if(0, NS + 64)
-        assert np.array_equal(after[32:32 + 2 * n], want)
-        assert after[:32].tobytes() == whole[:32].tobytes() and after[32 + 2 * n:].tobytes() == whole[32 + 2 * n:].tobytes()   # the owner's bytes around it
+        held(want)
+        # the other two calls that write a record 16 bytes at a time, in place on the same record
+        engine.excise_bins(0, n, np.ones(8, dtype=np.float32))          # a gain of ones: the identity
+        held(want)
+        assert engine.cancel(engine.make_blocks(0), mode="model").shape[0] == 0   # an empty list's model: the record cleared (test_gpu_cancel.py)
+        held(np.zeros_like(want))
     finally:
         engine.load_if(np.zeros(64, dtype=I8))                         # lets go of the owner's memory before it is freed
         owner.close()
