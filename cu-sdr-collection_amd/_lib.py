@@ -23,6 +23,7 @@ GC_PROBE_HIST_BINS = 257   # gc_probe_histogram: hist(x, -128:128)
 GC_CANCEL_MAX_CHANNELS = 64   # gc_cancel: distinct channels per call
 GC_CANCEL_SUBTRACT, GC_CANCEL_MODEL = 0, 1   # gc_cancel_mode
 GC_EXCISE_MAX_GUARD = 4096   # gc_excise_pulses: longest guard in front of and behind a hot sample
+GC_EXCISE_MAX_WIDEN = 64     # gc_excise_sweep: most bins cut on either side of a hot one
 GC_DDC_MAX_TAPS, GC_DDC_MAX_DECIM = 2048, 64   # gc_downconvert: longest filter, largest decimation
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
@@ -146,6 +147,23 @@ class gc_excise_bins_params(C.Structure):
     _fields_ = [("first_sample", C.c_int64), ("nsamples", C.c_int64), ("nfft", C.c_int32), ("reserved", C.c_int32)]
 
 
+class gc_excise_sweep_params(C.Structure):
+    """gc_excise_sweep: the range, the transform length (as gc_excise_bins') and the bins cut on either side of a hot one."""
+    _fields_ = [("first_sample", C.c_int64), ("nsamples", C.c_int64), ("nfft", C.c_int32), ("widen", C.c_int32)]
+
+
+class gc_excise_sweep_out(C.Structure):
+    """gc_excise_sweep's optional outputs, host memory, every member may be NULL: values [nsamples][2], power [K][nfft], hot and cut
+    [K][W] with W = (nfft + 63) // 64 words per segment, bin_cut [nfft]."""
+    _fields_ = [("values", C.POINTER(C.c_float)), ("power", C.POINTER(C.c_float)), ("hot", C.POINTER(C.c_uint64)), ("cut", C.POINTER(C.c_uint64)),
+                ("bin_cut", C.POINTER(C.c_int64))]
+
+
+class gc_excise_sweep_stats(C.Structure):
+    """gc_excise_sweep: K, hot cells, cut cells (hot ones included), segments with a cut cell, the most cut cells of one segment."""
+    _fields_ = [("segments", C.c_int64), ("hot", C.c_int64), ("cut", C.c_int64), ("segments_cut", C.c_int64), ("most_cut", C.c_int64)]
+
+
 class gc_ddc_params(C.Structure):
     """gc_downconvert: output m is filtered at record sample first_sample + m * decim and written to sample dst_first + m of dst."""
     _fields_ = [("first_sample", C.c_int64), ("noutputs", C.c_int64), ("dst_first", C.c_int64), ("decim", C.c_int32), ("ntaps", C.c_int32),
@@ -260,6 +278,8 @@ SYMBOLS = {
     "gc_excise_pulses": (C.c_int, [_P, _P, C.POINTER(gc_excise_pulse_params), C.POINTER(gc_excise_pulse_stats)]),
     "gc_excise_bins": (C.c_int, [_P, _P, C.POINTER(gc_excise_bins_params), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "gc_debug_excise_tile_segments": (C.c_longlong, [C.c_int]),
+    "gc_excise_sweep": (C.c_int, [_P, _P, C.POINTER(gc_excise_sweep_params), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                  C.POINTER(gc_excise_sweep_out), C.POINTER(gc_excise_sweep_stats)]),
     "gc_downconvert": (C.c_int, [_P, _P, C.POINTER(gc_ddc_params), C.POINTER(C.c_double), C.POINTER(gc_ddc_result)]),
     "gc_debug_ddc_tile_outputs": (C.c_longlong, [C.c_int, C.c_int]),
 }

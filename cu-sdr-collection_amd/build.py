@@ -44,7 +44,8 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                "probe.hip",       # gc_probe_psd, gc_probe_histogram: a record's Welch spectrum (on acq_fft.hip's pass kernels) and level histograms
                "cancel.hip",      # gc_cancel: tracked components rebuilt in float64 from their descriptors and subtracted from the record
                "excise.hip",      # gc_excise_pulses: samples over a level, and a guard around them, blanked in the record (integers throughout);
-                                  # gc_excise_bins: a gain per frequency bin by weighted overlap-add on acq_fft.hip's pass kernels
+                                  # gc_excise_bins: a gain per frequency bin by weighted overlap-add on acq_fft.hip's pass kernels;
+                                  # gc_excise_sweep: the same overlap-add with a decision per segment and bin (mark, apply, integer counts)
                "ddc.hip"]         # gc_downconvert: complex FIR, decimation, a 64-bit NCO and requantisation into a second record, float64
 
 
@@ -70,7 +71,7 @@ FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-f
 # instead of two: wrong table index at exact ties).  These translation units therefore forbid contraction;
 # wanted FMAs are written as fmaf() / fma().
 NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip", "corr_bank.hip", "cancel.hip",
-               "excise.hip",   # excise.hip: y = s v + s v' is two products and a sum, each rounded by itself
+               "excise.hip",   # excise.hip: y = s v + s v' and P = re re + im im are two products and a sum, each rounded by itself
                "ddc.hip"}      # ddc.hip: a tap is four products, a difference and three sums, each rounded by itself
 
 

@@ -28,6 +28,16 @@
 //   excise_carry_kernel    keeps s v of the second half of the tile's last segment for the next tile: its samples are not gathered
 //                          again after they were overwritten (in place), and a sample's value is the same sum wherever the cut falls.
 // Out of place the record is copied first and the add kernel works on the copy.
+//
+// gc_excise_sweep: the same overlap-add (one driver, excise_overlap_add) with a decision per cell (segment, bin) in the gain kernel's place:
+//   excise_sweep_mark_kernel      one lane per bin in natural order: P = re^2 + im^2 of X, P > limit[b]; a wave's ballot is one word of
+//                                 the segment's hot row, written by one lane; P itself to the tile's power rows when asked for,
+//   excise_sweep_apply_kernel     one lane per bin: cut iff a hot bit lies within `widen` bins around the circle (at most three words of
+//                                 the hot row); the ballot is a word of the cut row; Y = 0 where cut, else gain * X, in natural order,
+//   excise_sweep_segments_kernel  one thread per segment: the popcounts of its two rows; hot cells, cut cells, segments with a cut cell
+//                                 and the most cut cells of one segment by 64-bit integer atomics,
+//   excise_sweep_bins_kernel      bin_cut: a wave walks a stretch of one word column of the cut rows, lane b counting bit b.
+// The tile's mask rows and power go to the caller's [K] arrays at row g0 after each tile.  No float atomics: the counts are exact.
 // The unit's buffers are its own (ExciseState, kept in gc_context::excise, grow-only, released by gc_destroy).
 #include <algorithm>
 #include <cmath>
@@ -50,6 +60,7 @@ struct ExciseState {  // grow-only device buffers of the context (released by gc
   int n = 0;                   // gc_excise_bins: transform length of plan, tw and win (0: none)
   gcacq::Plan plan;
   GcBuf tw, win, gain, rows_a, rows_b, carry, values;  // win: w[nfft] then s[nfft]
+  GcBuf limit, hot, cut, power, counts;                // gc_excise_sweep: a tile's mask rows and power; the four sums, then bin_cut
 };
 
 // A stretch of samples as the run statistics see it: `pre` blanked samples at its head, `suf` at its tail (both `len` when all are),
@@ -260,6 +271,124 @@ __global__ __launch_bounds__(kExciseWG) void excise_gain_kernel(const float2* __
   out[t * nfft + b] = make_float2(g * x.x, g * x.y);
 }
 
+// ---- gc_excise_sweep: the gain kernel's place taken by a decision per cell ----------------------------------------------------------------
+
+constexpr int kSweepRows = 128;  // mask rows a wave of excise_sweep_bins_kernel walks
+
+struct SweepArgs {
+  const float2* x;                // the tile's forward transforms, storage order
+  float2* y;                      // what the inverse pair reads: natural bin order
+  const float* limit;             // [nfft]
+  const float* gain;              // [nfft] or null: a gain of ones
+  unsigned long long *hot, *cut;  // the tile's mask rows, [rows][W]
+  float* power;                   // the tile's [rows][nfft] or null
+  int nfft, n1, n2, blocks_per_row, W, widen;
+};
+
+// One lane per bin, in natural order: P and the comparison; a wave's ballot is one word of the segment's hot row.  The lanes from
+// nfft on vote 0, so the last word's upper bits are 0.
+__global__ __launch_bounds__(kExciseWG) void excise_sweep_mark_kernel(const SweepArgs p) {
+  const long long t = blockIdx.x / (unsigned)p.blocks_per_row;
+  const int b = (int)(blockIdx.x - (unsigned)(t * p.blocks_per_row)) * kExciseWG + (int)threadIdx.x;
+  bool hot = false;
+  if (b < p.nfft) {
+    const int k2 = b / p.n1, k1 = b - k2 * p.n1;
+    const float2 x = p.x[t * p.nfft + k1 * p.n2 + k2];
+    const float pw = __fadd_rn(__fmul_rn(x.x, x.x), __fmul_rn(x.y, x.y));  // two products and a sum, each rounded by itself
+    hot = pw > p.limit[b];
+    if (p.power) p.power[t * p.nfft + b] = pw;
+  }
+  const unsigned long long word = __ballot(hot);
+  if ((threadIdx.x & 63) == 0 && (b >> 6) < p.W) p.hot[t * p.W + (b >> 6)] = word;
+}
+
+// a hot bit among the bins lo .. hi of a row, 0 <= lo <= hi < nfft: at most three words where hi - lo <= 2 GC_EXCISE_MAX_WIDEN
+__device__ __forceinline__ bool any_hot(const unsigned long long* __restrict__ row, int lo, int hi) {
+  unsigned long long any = 0ull;
+  for (int j = lo >> 6; j <= hi >> 6; ++j) {
+    unsigned long long m = ~0ull;
+    if (j == lo >> 6) m &= ~0ull << (lo & 63);
+    if (j == hi >> 6) m &= ~0ull >> (63 - (hi & 63));
+    any |= row[j] & m;
+  }
+  return any != 0ull;
+}
+
+// One lane per bin: cut iff a hot bin lies within `widen` of it around the circle of nfft bins (the bits are addressed by bin number,
+// so an nfft that is no multiple of 64 wraps where it should); Y = 0 where cut, else gain * X, moved as excise_gain_kernel moves it.
+__global__ __launch_bounds__(kExciseWG) void excise_sweep_apply_kernel(const SweepArgs p) {
+  const long long t = blockIdx.x / (unsigned)p.blocks_per_row;
+  const int b = (int)(blockIdx.x - (unsigned)(t * p.blocks_per_row)) * kExciseWG + (int)threadIdx.x;
+  bool cut = false;
+  if (b < p.nfft) {
+    const unsigned long long* const row = p.hot + t * p.W;
+    const int lo = b - p.widen, hi = b + p.widen, last = p.nfft - 1;
+    if (2 * p.widen + 1 >= p.nfft) cut = any_hot(row, 0, last);  // every bin is within widen of every other
+    else if (lo < 0) cut = any_hot(row, lo + p.nfft, last) || any_hot(row, 0, hi);
+    else if (hi > last) cut = any_hot(row, lo, last) || any_hot(row, 0, hi - p.nfft);
+    else cut = any_hot(row, lo, hi);
+    float2 y = make_float2(0.0f, 0.0f);
+    if (!cut) {
+      const int k2 = b / p.n1, k1 = b - k2 * p.n1;
+      y = p.x[t * p.nfft + k1 * p.n2 + k2];
+      if (p.gain) {
+        const float g = p.gain[b];
+        y = make_float2(g * y.x, g * y.y);
+      }
+    }
+    p.y[t * p.nfft + b] = y;
+  }
+  const unsigned long long word = __ballot(cut);
+  if ((threadIdx.x & 63) == 0 && (b >> 6) < p.W) p.cut[t * p.W + (b >> 6)] = word;
+}
+
+// The counts, integers throughout.  acc = {hot cells, cut cells, segments with a cut cell, most cut cells of one segment}, then
+// bin_cut[nfft].  One thread per segment of the tile: the popcounts of its two rows, the waves' sums and maximum by integer atomics.
+__global__ __launch_bounds__(kExciseWG) void excise_sweep_segments_kernel(const unsigned long long* __restrict__ hot, const unsigned long long* __restrict__ cut,
+                                                                           long long rows, int W, unsigned long long* __restrict__ acc) {
+  const long long k = (long long)blockIdx.x * kExciseWG + threadIdx.x;
+  int h = 0, c = 0;
+  if (k < rows)
+    for (int j = 0; j < W; ++j) {
+      h += __popcll(hot[k * W + j]);
+      c += __popcll(cut[k * W + j]);
+    }
+  long long hs = h, cs = c;
+  int any = c > 0 ? 1 : 0, most = c;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    hs += __shfl_down(hs, o, 64);
+    cs += __shfl_down(cs, o, 64);
+    any += __shfl_down(any, o, 64);
+    most = max(most, __shfl_down(most, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0 && cs > 0) {  // no cut cell: no hot one either
+    atomicAdd(acc + 0, (unsigned long long)hs);
+    atomicAdd(acc + 1, (unsigned long long)cs);
+    atomicAdd(acc + 2, (unsigned long long)any);
+    atomicMax(acc + 3, (unsigned long long)most);
+  }
+}
+
+// bin_cut: workgroup (stretch, word) walks 4 kSweepRows rows of one word column, lane b adding bit b; one atomic per bin and workgroup
+__global__ __launch_bounds__(kExciseWG) void excise_sweep_bins_kernel(const unsigned long long* __restrict__ cut, long long rows, int W, int nfft,
+                                                                       unsigned long long* __restrict__ bin_cut) {
+  __shared__ unsigned int part[kExciseWG / 64][64];
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  const long long stretch = blockIdx.x / (unsigned)W;
+  const int w = (int)(blockIdx.x - (unsigned)(stretch * W));
+  const long long k0 = (stretch * (kExciseWG / 64) + wave) * kSweepRows, k1 = min(rows, k0 + kSweepRows);
+  unsigned int n = 0u;
+  for (long long k = k0; k < k1; ++k) n += (unsigned int)(cut[k * W + w] >> lane) & 1u;
+  part[wave][lane] = n;
+  __syncthreads();
+  if (wave == 0) {
+    for (int i = 1; i < kExciseWG / 64; ++i) n += part[i][lane];
+    const int b = w * 64 + lane;
+    if (b < nfft && n > 0u) atomicAdd(bin_cut + b, (unsigned long long)n);
+  }
+}
+
 struct AddArgs {
   const float2* rows;   // the tile's inverse transforms, storage order: value n of a row at (n mod n1) n2 + n / n1
   const float2* carry;  // s v of the second half of segment g0 - 1 (g0 > 0)
@@ -315,7 +444,9 @@ __global__ __launch_bounds__(kExciseWG) void excise_carry_kernel(const AddArgs p
 void gc_excise_free(gc_context* ctx) {
   ExciseState* s = static_cast<ExciseState*>(ctx->excise);
   if (!s) return;
-  for (GcBuf* b : {&s->bitmap, &s->tiles, &s->stats, &s->tw, &s->win, &s->gain, &s->rows_a, &s->rows_b, &s->carry, &s->values}) gc_buf_free(*b);
+  for (GcBuf* b : {&s->bitmap, &s->tiles, &s->stats, &s->tw, &s->win, &s->gain, &s->rows_a, &s->rows_b, &s->carry, &s->values, &s->limit,
+                   &s->hot, &s->cut, &s->power, &s->counts})
+    gc_buf_free(*b);
   delete s;
   ctx->excise = nullptr;
 }
@@ -382,31 +513,43 @@ extern "C" int gc_excise_pulses(gc_context* src, gc_context* dst, const gc_excis
 
 extern "C" long long gc_debug_excise_tile_segments(int nfft) { return nfft < 4 ? 0 : excise_tile_segments(nfft, ExciseBudget()); }
 
-extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_bins_params* p, const float* gain, float* values) {
-  int rc = excise_check_bins(src, dst, p, gain);
-  if (rc) return rc;
-  gcacq::Plan plan;
-  rc = gcacq::plan_or_refuse(p->nfft, &plan);
-  if (rc) return rc;
-  ExciseBinsPlan pl;
-  rc = excise_check_bins_state(src, dst, p, ExciseBudget(), &pl);
-  if (rc) return rc;
-  const int nfft = p->nfft, H = nfft / 2;
-  const long long first = (long long)p->first_sample, nsamples = (long long)p->nsamples;
-  // nothing has been written up to here
+namespace {
+
+struct Sweep {  // what gc_excise_sweep puts where gc_excise_bins has its gain kernel
+  const float* limit;
+  int widen;
+  const gc_excise_sweep_out* out;  // never null (its members may be)
+  gc_excise_sweep_stats* stats;    // may be null
+  ExciseSweepPlan pl;
+};
+
+// The overlap-add of both calls, after their checks: nothing has been written when it begins.  gain: [nfft] on the host, or null
+// (gc_excise_sweep's gain of ones); sw: null for gc_excise_bins.
+int excise_overlap_add(const char* who, gc_context* src, gc_context* dst, long long first, long long nsamples, int nfft, const gcacq::Plan& plan,
+                       const ExciseBinsPlan& pl, const float* gain, float* values, const Sweep* sw) {
+  const int H = nfft / 2;
+  int rc;
   GC_HIP(hipSetDevice(src->device));
   if (dst != src) GC_HIP(hipStreamSynchronize(dst->stream));  // the destination's own pending work comes first
   ExciseState* s = gc_unit_state<ExciseState>(src->excise);
-  if (!s) return gc_nomem("gc_excise_bins");
-  const size_t rows_bytes = (size_t)std::min(pl.tile, pl.K) * (size_t)nfft * sizeof(float2);
+  if (!s) return gc_nomem(who);
+  const size_t tile_rows = (size_t)std::min(pl.tile, pl.K), rows_bytes = tile_rows * (size_t)nfft * sizeof(float2);
   if (gc_buf_reserve(s->rows_a, rows_bytes, false) != hipSuccess || gc_buf_reserve(s->rows_b, rows_bytes, false) != hipSuccess ||
       gc_buf_reserve(s->gain, (size_t)nfft * sizeof(float), false) != hipSuccess || gc_buf_reserve(s->carry, (size_t)H * sizeof(float2), false) != hipSuccess ||
       (values && gc_buf_reserve(s->values, (size_t)nsamples * sizeof(float2), false) != hipSuccess))
-    return gc_nomem("gc_excise_bins");
+    return gc_nomem(who);
+  const size_t counts_bytes = (4 + (size_t)nfft) * sizeof(unsigned long long);  // the four sums, then bin_cut
+  if (sw) {
+    const size_t mask_bytes = tile_rows * (size_t)sw->pl.W * sizeof(unsigned long long);
+    if (gc_buf_reserve(s->limit, (size_t)nfft * sizeof(float), false) != hipSuccess || gc_buf_reserve(s->hot, mask_bytes, false) != hipSuccess ||
+        gc_buf_reserve(s->cut, mask_bytes, false) != hipSuccess || gc_buf_reserve(s->counts, counts_bytes, false) != hipSuccess ||
+        (sw->out->power && gc_buf_reserve(s->power, tile_rows * (size_t)nfft * sizeof(float), false) != hipSuccess))
+      return gc_nomem(who);
+  }
   if (s->n != nfft) {  // the plan, the twiddle table, the window w and the scale s of an nfft-point excision
     s->n = 0;
     if (gc_buf_reserve(s->tw, (size_t)nfft * sizeof(float2), false) != hipSuccess || gc_buf_reserve(s->win, 2 * (size_t)nfft * sizeof(float), false) != hipSuccess)
-      return gc_nomem("gc_excise_bins");
+      return gc_nomem(who);
     const double pi = 3.14159265358979323846;
     std::vector<float> win(2 * (size_t)nfft);
     for (int k = 0; k < nfft; ++k) {
@@ -420,7 +563,11 @@ extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_
     s->plan = plan;
     s->n = nfft;
   }
-  GC_HIP(hipMemcpyAsync(s->gain.p, gain, (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, src->stream));
+  if (gain) GC_HIP(hipMemcpyAsync(s->gain.p, gain, (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, src->stream));
+  if (sw) {
+    GC_HIP(hipMemcpyAsync(s->limit.p, sw->limit, (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, src->stream));
+    GC_HIP(hipMemsetAsync(s->counts.p, 0, counts_bytes, src->stream));
+  }
   const int bps = gc_record_bps(src);
   if (dst->d_if != src->d_if)  // out of place: the add kernel works on a copy
     GC_HIP(hipMemcpyAsync(dst->d_if, src->d_if, (size_t)src->if_nsamples * (size_t)bps, hipMemcpyDeviceToDevice, src->stream));
@@ -438,6 +585,18 @@ extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_
   a.nfft = nfft;
   a.n1 = plan.n1;
   a.n2 = plan.n2;
+  SweepArgs m = {};
+  if (sw) {
+    m.x = rows_a;
+    m.y = rows_b;
+    m.limit = (const float*)s->limit.p;
+    m.gain = gain ? (const float*)s->gain.p : nullptr;
+    m.hot = (unsigned long long*)s->hot.p;
+    m.cut = (unsigned long long*)s->cut.p;
+    m.power = sw->out->power ? (float*)s->power.p : nullptr;
+    m.nfft = nfft, m.n1 = plan.n1, m.n2 = plan.n2, m.blocks_per_row = bpr, m.W = (int)sw->pl.W, m.widen = sw->widen;
+  }
+  unsigned long long* const counts = (unsigned long long*)s->counts.p;
   const gcacq::RowGather segs = {first, nsamples, H, pl.K, H};  // segment k covers the range samples [(k - 1) H, (k + 1) H): one span of K segments
   for (ExciseTile t; excise_next_tile(pl, t);) {
     const dim3 grid((unsigned int)(t.n * bpr)), wg(kExciseWG);
@@ -446,8 +605,26 @@ extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_
     if (rc) return rc;
     rc = gcacq::transform_rows(src, s->plan, (const float2*)s->tw.p, rows_a, rows_b, t.n, 0);
     if (rc) return rc;
-    hipLaunchKernelGGL(excise_gain_kernel, grid, wg, 0, src->stream, (const float2*)rows_a, rows_b, (const float*)s->gain.p, nfft, plan.n1, plan.n2, bpr);
-    GC_HIP(hipGetLastError());
+    if (!sw) {
+      hipLaunchKernelGGL(excise_gain_kernel, grid, wg, 0, src->stream, (const float2*)rows_a, rows_b, (const float*)s->gain.p, nfft, plan.n1, plan.n2, bpr);
+      GC_HIP(hipGetLastError());
+    } else {
+      hipLaunchKernelGGL(excise_sweep_mark_kernel, grid, wg, 0, src->stream, m);
+      hipLaunchKernelGGL(excise_sweep_apply_kernel, grid, wg, 0, src->stream, m);
+      GC_HIP(hipGetLastError());
+      const long long stretches = (t.n + (kExciseWG / 64) * kSweepRows - 1) / ((kExciseWG / 64) * kSweepRows);
+      hipLaunchKernelGGL(excise_sweep_segments_kernel, dim3((unsigned int)((t.n + kExciseWG - 1) / kExciseWG)), wg, 0, src->stream,
+                         (const unsigned long long*)m.hot, (const unsigned long long*)m.cut, t.n, m.W, counts);
+      hipLaunchKernelGGL(excise_sweep_bins_kernel, dim3((unsigned int)(stretches * m.W)), wg, 0, src->stream, (const unsigned long long*)m.cut, t.n, m.W,
+                         nfft, counts + 4);
+      GC_HIP(hipGetLastError());
+      // the tile's rows of the [K] arrays: row g0 on (excise_plan.h); the next tile's kernels follow the copies on the stream
+      const size_t mask_bytes = (size_t)t.n * (size_t)m.W * sizeof(unsigned long long);
+      if (sw->out->hot) GC_HIP(hipMemcpyAsync(sw->out->hot + excise_mask_offset(sw->pl, t), m.hot, mask_bytes, hipMemcpyDeviceToHost, src->stream));
+      if (sw->out->cut) GC_HIP(hipMemcpyAsync(sw->out->cut + excise_mask_offset(sw->pl, t), m.cut, mask_bytes, hipMemcpyDeviceToHost, src->stream));
+      if (m.power)
+        GC_HIP(hipMemcpyAsync(sw->out->power + excise_power_offset(sw->pl, t), m.power, (size_t)t.n * (size_t)nfft * sizeof(float), hipMemcpyDeviceToHost, src->stream));
+    }
     rc = gcacq::transform_rows(src, s->plan, (const float2*)s->tw.p, rows_b, rows_a, t.n, 1);
     if (rc) return rc;
     a.g0 = t.g0;
@@ -456,8 +633,8 @@ extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_
     if (t.m0 < t.m1) {
       const long long v0 = (first + t.m0) / per16, v1 = (first + t.m1 + per16 - 1) / per16;
       const unsigned int wgs = (unsigned int)((v1 - v0 + kExciseWG - 1) / kExciseWG);
-      gc_with_mode(gc_record_mode(src), [&](auto m) {
-        hipLaunchKernelGGL(excise_add_kernel<decltype(m)::value>, dim3(wgs), wg, 0, src->stream, a, v0, v1 - v0);
+      gc_with_mode(gc_record_mode(src), [&](auto mode) {
+        hipLaunchKernelGGL(excise_add_kernel<decltype(mode)::value>, dim3(wgs), wg, 0, src->stream, a, v0, v1 - v0);
       });
       GC_HIP(hipGetLastError());
     }
@@ -467,6 +644,54 @@ extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_
     }
   }
   if (values) GC_HIP(hipMemcpyAsync(values, s->values.p, (size_t)nsamples * sizeof(float2), hipMemcpyDeviceToHost, src->stream));
+  std::vector<unsigned long long> host;
+  if (sw) {
+    host.resize(4 + (size_t)nfft);
+    GC_HIP(hipMemcpyAsync(host.data(), counts, counts_bytes, hipMemcpyDeviceToHost, src->stream));
+  }
   GC_HIP(hipStreamSynchronize(src->stream));
+  if (sw) {
+    if (sw->stats) {
+      sw->stats->segments = (int64_t)pl.K;
+      sw->stats->hot = (int64_t)host[0];
+      sw->stats->cut = (int64_t)host[1];
+      sw->stats->segments_cut = (int64_t)host[2];
+      sw->stats->most_cut = (int64_t)host[3];
+    }
+    if (sw->out->bin_cut)
+      for (int b = 0; b < nfft; ++b) sw->out->bin_cut[b] = (int64_t)host[4 + (size_t)b];
+  }
   return GC_OK;
 }
+
+}  // namespace
+
+extern "C" int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_bins_params* p, const float* gain, float* values) {
+  int rc = excise_check_bins(src, dst, p, gain);
+  if (rc) return rc;
+  gcacq::Plan plan;
+  rc = gcacq::plan_or_refuse(p->nfft, &plan);
+  if (rc) return rc;
+  ExciseBinsPlan pl;
+  rc = excise_check_bins_state(src, dst, p, ExciseBudget(), &pl);
+  if (rc) return rc;
+  // nothing has been written up to here
+  return excise_overlap_add("gc_excise_bins", src, dst, (long long)p->first_sample, (long long)p->nsamples, p->nfft, plan, pl, gain, values, nullptr);
+}
+
+extern "C" int gc_excise_sweep(gc_context* src, gc_context* dst, const gc_excise_sweep_params* p, const float* limit, const float* gain,
+                               const gc_excise_sweep_out* out, gc_excise_sweep_stats* stats) {
+  int rc = excise_check_sweep(src, dst, p, limit, gain);
+  if (rc) return rc;
+  gcacq::Plan plan;
+  rc = gcacq::plan_or_refuse(p->nfft, &plan);
+  if (rc) return rc;
+  const gc_excise_sweep_out none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  Sweep sw = {limit, p->widen, out ? out : &none, stats, ExciseSweepPlan()};
+  rc = excise_check_sweep_state(src, dst, p, ExciseBudget(), &sw.pl);
+  if (rc) return rc;
+  // nothing has been written up to here
+  return excise_overlap_add("gc_excise_sweep", src, dst, (long long)p->first_sample, (long long)p->nsamples, p->nfft, plan, sw.pl.seg, gain,
+                            sw.out->values, &sw);
+}
+

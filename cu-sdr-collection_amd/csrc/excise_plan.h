@@ -1,6 +1,7 @@
-// excise_plan.h — what the drivers of the excision (excise.hip: gc_excise_pulses, gc_excise_bins) decide on the host, from integers:
+// excise_plan.h — what the drivers of the excision (excise.hip: gc_excise_pulses, gc_excise_bins, gc_excise_sweep) decide on the host, from integers:
 // the argument checks; how the blanker's range is laid over the hot-sample bitmap and cut into the tiles its kernels take one workgroup
-// each; the segment count of the spectral excision and the cut of its segment list into tiles whose rows fit a byte budget.  Nothing
+// each; the segment count of the spectral excision and the cut of its segment list into tiles whose rows fit a byte budget; the mask
+// rows of the swept excision.  Nothing
 // here calls HIP, allocates on the device or launches; tests/excise_plan_shim.hip runs all of it without a device.  From the two
 // contexts the checks read d_if, device, if_nsamples, if_dtype and if_layout (record_check.h: the pair of records, the range).  The one refusal that is not decided here is the
 // transform planner's (make_plan, acq_fft.hip: GC_E_UNSUPPORTED).
@@ -119,14 +120,66 @@ inline int excise_check_bins(const gc_context* src, const gc_context* dst, const
 }
 
 // ... and what the contexts must hold for them: GC_E_STATE, GC_E_INVALID (a destination that does not match), GC_E_RANGE; then the plan
+inline int excise_check_segments(const char* who, const gc_context* src, const gc_context* dst, long long first_sample, long long nsamples, int nfft,
+                                 const ExciseBudget& b, ExciseBinsPlan* pl) {
+  int rc = check_record_pair(who, src, dst);
+  if (rc) return rc;
+  rc = check_record_range(who, src, first_sample, nsamples);
+  if (rc) return rc;
+  pl->H = nfft / 2;
+  pl->K = excise_segments(nsamples, nfft);
+  pl->tile = excise_tile_segments(nfft, b);
+  pl->nsamples = nsamples;
+  return GC_OK;
+}
+
 inline int excise_check_bins_state(const gc_context* src, const gc_context* dst, const gc_excise_bins_params* p, const ExciseBudget& b, ExciseBinsPlan* pl) {
-  int rc = check_record_pair("gc_excise_bins", src, dst);
+  return excise_check_segments("gc_excise_bins", src, dst, (long long)p->first_sample, (long long)p->nsamples, p->nfft, b, pl);
+}
+
+// ---- gc_excise_sweep: gc_excise_bins' segments and tiles, and one mask bit per cell (segment, bin) ---------------------------------------
+// A segment's mask row is W = ceil(nfft / 64) words; bin b is bit b & 63 of word b >> 6, the bits from nfft on are zero.  The [K]
+// arrays of the caller (hot, cut: W words per row; power: nfft floats per row) are filled tile by tile: the rows of the tile
+// [g0, g0 + n) begin at row g0, which is excise_mask_offset words into a mask and excise_power_offset floats into the power.
+struct ExciseSweepPlan {
+  ExciseBinsPlan seg;
+  long long W = 0;  // mask words per segment
+};
+
+inline long long excise_mask_words(int nfft) { return ((long long)nfft + 63) / 64; }
+inline long long excise_tile_rows(const ExciseSweepPlan& pl) { return pl.seg.tile < pl.seg.K ? pl.seg.tile : pl.seg.K; }  // rows the tile buffers hold
+inline long long excise_mask_offset(const ExciseSweepPlan& pl, const ExciseTile& t) { return t.g0 * pl.W; }
+inline long long excise_power_offset(const ExciseSweepPlan& pl, const ExciseTile& t) { return t.g0 * 2 * pl.seg.H; }
+
+// gc_excise_sweep's arguments (include/gnsscorr.h): GC_E_INVALID.  The planner's refusal comes between this and the state, as for the bins.
+inline int excise_check_sweep(const gc_context* src, const gc_context* dst, const gc_excise_sweep_params* p, const float* limit, const float* gain) {
+  if (!src || !dst || !p || !limit) {
+    gc_set_error("gc_excise_sweep: null argument");
+    return GC_E_INVALID;
+  }
+  if (p->first_sample < 0 || p->nsamples < 1 || p->nfft < 4 || (p->nfft & 1) || p->widen < 0 || p->widen > GC_EXCISE_MAX_WIDEN) {
+    gc_set_error("gc_excise_sweep: bad arguments (first_sample %lld, nsamples %lld, nfft %d, widen %d)", (long long)p->first_sample,
+                 (long long)p->nsamples, p->nfft, p->widen);
+    return GC_E_INVALID;
+  }
+  for (int b = 0; b < p->nfft; ++b) {
+    if (!(limit[b] >= 0.0f)) {  // a NaN or a negative value; +INF protects the bin
+      gc_set_error("gc_excise_sweep: limit[%d] is NaN or negative", b);
+      return GC_E_INVALID;
+    }
+    if (gain && !(gain[b] - gain[b] == 0.0f)) {
+      gc_set_error("gc_excise_sweep: gain[%d] is not finite", b);
+      return GC_E_INVALID;
+    }
+  }
+  return GC_OK;
+}
+
+inline int excise_check_sweep_state(const gc_context* src, const gc_context* dst, const gc_excise_sweep_params* p, const ExciseBudget& b, ExciseSweepPlan* pl) {
+  ExciseBinsPlan seg;
+  const int rc = excise_check_segments("gc_excise_sweep", src, dst, (long long)p->first_sample, (long long)p->nsamples, p->nfft, b, &seg);
   if (rc) return rc;
-  rc = check_record_range("gc_excise_bins", src, (long long)p->first_sample, (long long)p->nsamples);
-  if (rc) return rc;
-  pl->H = p->nfft / 2;
-  pl->K = excise_segments((long long)p->nsamples, p->nfft);
-  pl->tile = excise_tile_segments(p->nfft, b);
-  pl->nsamples = (long long)p->nsamples;
+  pl->seg = seg;
+  pl->W = excise_mask_words(p->nfft);
   return GC_OK;
 }

@@ -198,7 +198,8 @@ struct gc_context {
   void* probe = nullptr;     // gc_probe_psd / gc_probe_histogram: their own plan, twiddle table, window, rows and accumulators (probe.hip: ProbeState)
   void* cancel = nullptr;    // gc_cancel: sorted descriptors, channel list, projection partials and amplitudes (cancel.hip: CancelState)
   void* excise = nullptr;    // gc_excise_pulses: the hot-sample bitmap, the tiles' run summaries, the statistics; gc_excise_bins: its plan, twiddle
-                             // table, window, gain, rows, carry and values (excise.hip: ExciseState)
+                             // table, window, gain, rows, carry and values; gc_excise_sweep: its limit, a tile's mask rows and power, the
+                             // counts (excise.hip: ExciseState)
   void* ddc = nullptr;       // gc_downconvert: the taps and the two result counters on the device (ddc.hip: DdcState)
 
   // gc_track_multi: this context's tracking call runs next to other contexts' on the same device.  Its persistent kernels

@@ -391,6 +391,62 @@ class Engine:
         return None if out is None else out.view(np.complex64)[:, 0]
 
     @staticmethod
+    def _excise_sweep_args(first_sample, nsamples, limit, widen, gain):
+        """(gc_excise_sweep_params, limit, gain or None) of excise_sweep()'s arguments: limit and gain as contiguous float32 [nfft];
+        ValueError for a limit that is not one real value per bin of an even transform of at least 4 points, a gain of another
+        shape than the limit, or a whole number that does not fit its field - before any library call."""
+        lim = np.asarray(limit)
+        if lim.ndim != 1 or lim.shape[0] < 4 or lim.shape[0] % 2 or not (np.issubdtype(lim.dtype, np.floating) or np.issubdtype(lim.dtype, np.integer)):
+            raise ValueError(f"excise_sweep(): limit must be one real value per bin of an even transform length >= 4, not {lim.dtype} {lim.shape}")
+        g = None
+        if gain is not None:
+            g = np.asarray(gain)
+            if g.shape != lim.shape or not (np.issubdtype(g.dtype, np.floating) or np.issubdtype(g.dtype, np.integer)):
+                raise ValueError(f"excise_sweep(): gain must be one real value per bin, as the limit ({lim.shape[0]}), not {g.dtype} {g.shape}")
+            g = np.ascontiguousarray(g, dtype=np.float32)
+        vals = []
+        for name, v, bits in (("first_sample", first_sample, 64), ("nsamples", nsamples, 64), ("widen", widen, 32)):
+            if isinstance(v, (bool, str, bytes)) or v is None or v != int(v) or not -(1 << (bits - 1)) <= int(v) < 1 << (bits - 1):
+                raise ValueError(f"excise_sweep(): {name} must be a whole number of {bits} bits, not {v!r}")
+            vals.append(int(v))
+        with np.errstate(over="ignore"):                                                 # a float64 limit over float32's range: +inf
+            lim = np.ascontiguousarray(lim, dtype=np.float32)
+        return L.gc_excise_sweep_params(vals[0], vals[1], lim.shape[0], vals[2]), lim, g
+
+    @staticmethod
+    def _unpack_masks(words: np.ndarray, nfft: int) -> np.ndarray:
+        """gc_excise_sweep's mask rows uint64 [K, W] as bool [K, nfft]: bin b is bit b & 63 of word b >> 6."""
+        bits = np.unpackbits(np.ascontiguousarray(words).astype("<u8", copy=False).view(np.uint8), axis=1, bitorder="little")
+        return bits[:, :nfft].astype(bool)
+
+    def excise_sweep(self, first_sample: int, nsamples: int, limit, widen: int = 0, gain=None, dst: "Engine | None" = None, values: bool = False,
+                     power: bool = False, masks: bool = False, bin_cut: bool = False):
+        """gc_excise_sweep: excise_bins' overlap-add with a decision per segment and bin - cell (k, b) is hot iff its float32 power
+        |X_k[b]|^2 > limit[b] (inf protects a bin), cut iff a hot bin of the segment lies within `widen` bins around the circle
+        (0 .. GC_EXCISE_MAX_WIDEN); cut cells become 0, the others gain[b] X_k[b] (None: X_k[b]).  nfft = len(limit); bins as probe_psd's.
+        Into `dst`'s record or (None) in place.  Returns SimpleNamespace(stats, values, power, hot, cut, bin_cut): stats =
+        SimpleNamespace(segments, hot, cut, segments_cut, most_cut); values complex64 [nsamples], power float32 [K, nfft], hot and
+        cut bool [K, nfft] (masks=True), bin_cut int64 [nfft] - None where not asked for (include/gnsscorr.h)."""
+        p, lim, g = self._excise_sweep_args(first_sample, nsamples, limit, widen, gain)
+        nfft, n = p.nfft, max(p.nsamples, 0)
+        K, W = -(-n // (nfft // 2)) + 1, (nfft + 63) // 64
+        vals = np.zeros((n, 2), dtype=np.float32) if values else None
+        pw = np.zeros((K, nfft), dtype=np.float32) if power else None
+        hot, cut = (np.zeros((K, W), dtype=np.uint64), np.zeros((K, W), dtype=np.uint64)) if masks else (None, None)
+        bc = np.zeros(nfft, dtype=np.int64) if bin_cut else None
+        fp, up, ip = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+        out = L.gc_excise_sweep_out(None if vals is None else vals.ctypes.data_as(fp), None if pw is None else pw.ctypes.data_as(fp),
+                                    None if hot is None else hot.ctypes.data_as(up), None if cut is None else cut.ctypes.data_as(up),
+                                    None if bc is None else bc.ctypes.data_as(ip))
+        st = L.gc_excise_sweep_stats()
+        L.check(self._lib.gc_excise_sweep(self._ctx, (self if dst is None else dst)._ctx, C.byref(p), lim.ctypes.data_as(fp),
+                                          None if g is None else g.ctypes.data_as(fp), C.byref(out), C.byref(st)))
+        stats = SimpleNamespace(segments=int(st.segments), hot=int(st.hot), cut=int(st.cut), segments_cut=int(st.segments_cut), most_cut=int(st.most_cut))
+        return SimpleNamespace(stats=stats, values=None if vals is None else vals.view(np.complex64)[:, 0], power=pw,
+                               hot=None if hot is None else self._unpack_masks(hot, nfft), cut=None if cut is None else self._unpack_masks(cut, nfft),
+                               bin_cut=bc)
+
+    @staticmethod
     def debug_excise_tile_segments(nfft: int) -> int:
         """gc_debug_excise_tile_segments (test hook, host code only): segments of an nfft-point excise_bins the library transforms at a time."""
         return int(L.load().gc_debug_excise_tile_segments(int(nfft)))

@@ -543,6 +543,52 @@ def excise_interference(fid: Engine, settings, first_sample: int = 0, nsamples: 
     return res
 
 
+def excise_sweep_limit(power, factor: float) -> np.ndarray:
+    """excise_swept()'s limit from the power rows [segments, nfft] of a gc_excise_sweep call: float32(factor * median over the
+    segments / ln 2) per bin.  The median of a bin over the segments barely moves under a jammer that visits the bin a small share
+    of the time, and the median of an exponential variable - a noise bin's power - is ln 2 times its mean: the limit is `factor`
+    times the jam-free mean bin power."""
+    p = np.asarray(power, dtype=np.float64)
+    if p.ndim != 2 or p.shape[0] < 1:
+        raise ValueError(f"excise_sweep_limit(): power must be [segments, nfft], not {p.shape}")
+    return (float(factor) * np.median(p, axis=0) / math.log(2.0)).astype(np.float32)
+
+
+def excise_swept(fid: Engine, settings, first_sample: int = 0, nsamples: int | None = None, nfft: int = 64, factor: float = 6.0, widen: int = 1,
+                 train_segments: int = 4096, dst: Engine | None = None):
+    """Swept interference - a chirp jammer that crosses the band many times per millisecond - taken out of [first_sample, first_sample
+    + nsamples) of the loaded record (None: to its end) before acquisition(), by gc_excise_sweep: the time-frequency cells of
+    half-overlapping nfft-sample segments that stand over a limit, and `widen` bins either side of them, are cut.  The limit is
+    trained on the first `train_segments` segments of the range: one call with limit = +inf (nothing is cut) and power=True into a
+    scratch record (`dst`, which the cleaning overwrites, or a temporary one) gives their power, excise_sweep_limit(power, factor)
+    the limit.  Into `dst`'s record (same sample count, dtype and layout) or (None) in place.
+    Returns (holder, limit, stats, bin_cut): the engine that holds the cleaned record, the float32 [nfft] limit, gc_excise_sweep's
+    statistics and the segments in which each bin was cut."""
+    first_sample, nfft, train_segments = int(first_sample), int(nfft), int(train_segments)
+    if train_segments < 1:
+        raise ValueError(f"excise_swept(): train_segments must be at least 1, not {train_segments}")
+    total = int(fid.if_buffer()[1])
+    n = total - first_sample if nsamples is None else int(nsamples)
+    n_train = min(n, train_segments * (nfft // 2))                      # segments 0 .. train_segments - 1 lie in these samples
+    inf = np.full(nfft, np.inf, dtype=np.float32)
+    scratch = dst
+    try:
+        if scratch is None:
+            dt, layout = fid.if_format()
+            scratch = Engine(fid.device_id)
+            scratch.alloc_if(total, np.int16 if dt == L.GC_I16 else np.int8, layout)
+        power = fid.excise_sweep(first_sample, n_train, inf, 0, dst=scratch, power=True).power
+    finally:
+        if dst is None and scratch is not None:
+            scratch.close()
+    limit = excise_sweep_limit(power[:train_segments], factor)
+    res = fid.excise_sweep(first_sample, n, limit, widen, dst=dst, bin_cut=True)
+    holder = fid if dst is None else dst
+    if dst is not None:
+        dst.set_sampling_freq(float(settings.samplingFreq))
+    return holder, limit, res.stats, res.bin_cut
+
+
 def ddc_nco_step(freq: float, fs: float) -> int:
     """gc_downconvert's phase_step for `freq` at `fs` as a signed Python integer: ldexp(freq / fs, 64) rounded to the nearest integer,
     ties to even (what llrint gives the library)."""

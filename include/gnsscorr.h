@@ -885,6 +885,57 @@ int gc_excise_bins(gc_context* src, gc_context* dst, const gc_excise_bins_params
  * segment list); 0 for nfft < 4. */
 long long gc_debug_excise_tile_segments(int nfft);
 
+/* ---- ... and swept interference cut cell by cell: a decision per bin in every segment -------------------------------------------------
+ * A chirp jammer crosses most of the band many times per millisecond: every bin is hit a small share of the time, the Welch spectrum
+ * shows a plateau and no line, and a sample is a few times the noise level - neither a gain per bin nor the blanker takes it out.
+ * gc_excise_sweep decides bin by bin in every segment of gc_excise_bins' overlap-add and cuts only the time-frequency cells that
+ * stand over a limit.  The records and `dst` (out of place, in place, a context that shares the record), the stream and the buffers,
+ * file order, H, K = ceil(nsamples / H) + 1, w, s, the zero padding outside the range, X_k, the inverse transform, c_k, y and the
+ * rounding into the record are gc_excise_bins'.  New here, all in float32, every operation rounded by itself (no fused multiply-add):
+ *   power   P_k[b] = X_k[b].re * X_k[b].re + X_k[b].im * X_k[b].im
+ *   hot     cell (k, b) is hot iff P_k[b] > limit[b]: a limit of +INF protects a bin, a limit of 0 makes it hot wherever P > 0
+ *   cut     cell (k, b) is cut iff some bin b' of segment k is hot with min(|b - b'|, nfft - |b - b'|) <= widen: the distance is
+ *           circular (bin nfft - 1 is next to bin 0); with 2 widen + 1 >= nfft one hot bin cuts the segment
+ *   Y_k[b]  (+0, +0) where cut; elsewhere gain[b] * X_k[b] per component, X_k[b] itself with a NULL gain
+ * out (may be NULL; host memory, every member may be NULL): values as gc_excise_bins'; power [K][nfft], P_k[b] as it was compared;
+ * hot and cut [K][W] with W = (nfft + 63) / 64 words per segment, bin b bit b & 63 of word [k][b >> 6], the bits from nfft on 0;
+ * bin_cut [nfft], the segments in which bin b was cut.  power and the masks are in natural bin order, gc_probe_psd's.
+ * stats (may be NULL): K, the hot cells, the cut cells (the hot ones included), the segments with a cut cell, the most cut cells of
+ * one segment.  The counts are integer sums: exact, whatever order the device forms them in.
+ * Guarantees: the same input gives the same bytes, values, power, masks and counts.  A segment's decisions depend on that segment
+ * only - not on the tile of the segment list it falls in (gc_debug_excise_tile_segments), not on which of the optional outputs were
+ * asked for.  In place equals out of place.  With every limit at +INF the call is gc_excise_bins with the same gain byte for byte,
+ * record and values; a NULL gain is a gain of ones.
+ *
+ * Refusals (a refused call writes nothing: not dst, not out's arrays, not stats): those of gc_excise_bins (there is no reserved
+ * member), and GC_E_INVALID for a null limit, a limit[b] that is NaN or negative, a widen outside [0, GC_EXCISE_MAX_WIDEN] and a gain
+ * that is not finite. */
+#define GC_EXCISE_MAX_WIDEN 64
+typedef struct gc_excise_sweep_params {
+  int64_t first_sample;   /* 0-based sample (pair) index of the range */
+  int64_t nsamples;       /* >= 1 */
+  int32_t nfft;           /* even, >= 4, 2^a 3^b 5^c with a plan */
+  int32_t widen;          /* 0 .. GC_EXCISE_MAX_WIDEN */
+} gc_excise_sweep_params; /* 24 bytes */
+typedef struct gc_excise_sweep_out {   /* host memory, every member may be NULL */
+  float*    values;   /* [nsamples][2]: y before rounding, as gc_excise_bins */
+  float*    power;    /* [K][nfft]: P_k[b] as it was compared */
+  uint64_t* hot;      /* [K][W] */
+  uint64_t* cut;      /* [K][W] */
+  int64_t*  bin_cut;  /* [nfft]: segments in which bin b was cut */
+} gc_excise_sweep_out;
+typedef struct gc_excise_sweep_stats {
+  int64_t segments;      /* K */
+  int64_t hot;           /* hot cells */
+  int64_t cut;           /* cut cells, the hot ones included */
+  int64_t segments_cut;  /* segments with a cut cell */
+  int64_t most_cut;      /* most cut cells in one segment */
+} gc_excise_sweep_stats;  /* 40 bytes */
+int gc_excise_sweep(gc_context* src, gc_context* dst, const gc_excise_sweep_params* p,
+                    const float* limit /* [nfft] */, const float* gain /* [nfft] or NULL */,
+                    const gc_excise_sweep_out* out /* may be NULL */,
+                    gc_excise_sweep_stats* stats /* may be NULL */);
+
 /* ---- a band of a record as a record at a lower rate: the digital down-converter -----------------------------------------------------
  * gc_downconvert filters a record with a complex FIR, keeps every D-th output, rotates it by a numerically controlled oscillator and
  * requantises it into a SECOND record (csrc/ddc.hip): a 50 Msps L5 file, one FDMA carrier of a GLONASS record, the C/A main lobe of

@@ -67,6 +67,13 @@
  *   v    = gnsscorr_mex('excise_bins', hSrc, hDst, firstSample0, nSamples, gain)      % the range through a gain per frequency bin (gain(b)
  *          is bin b of 'probe_psd' with nfft = numel(gain), bin 1 = DC) by weighted overlap-add, from hSrc's record into hDst's (hDst ==
  *          hSrc: in place; gc_excise_bins); v (only when asked for) 2 x nSamples single: the values before rounding (re; im)
+ *   [st, binCut, v, power, hot, cut] = gnsscorr_mex('excise_sweep', hSrc, hDst, firstSample0, nSamples, limit[, widen[, gain]])
+ *          % swept interference cut cell by cell (gc_excise_sweep): in every half-overlapping segment of nfft = numel(limit) samples the
+ *          bins whose power stands over limit(b) (Inf protects a bin), and widen (0 .. 64, default 0) bins either side of them around
+ *          the circle, are zeroed, the others multiplied by gain(b) ([] = ones); from hSrc's record into hDst's (hDst == hSrc: in place).
+ *          st = [segments hot cut segmentsCut mostCut]; only when asked for: binCut nfft x 1 int64 (segments in which each bin was cut),
+ *          v 2 x nSamples single, power nfft x K single, hot and cut W x K uint64 (bin b, 0-based, is bit mod(b, 64) of word
+ *          floor(b / 64) + 1 of its segment's column)
  *   [r, nco] = gnsscorr_mex('downconvert', hSrc, hDst, taps, decim[, carrFreq[, carrPhase[, firstSample0[, nOutputs[, dstFirst0]]]]])
  *          % hSrc's record through the complex FIR taps (2 x T doubles: re; im), every decim-th output rotated by an NCO of carrFreq Hz
  *          and rounded into hDst's record from sample dstFirst0 (gc_downconvert); nOutputs absent or [] = every output with a record
@@ -775,6 +782,63 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxFree(g);
     if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
     if (rc) fail("gc_excise_bins");
+  } else if (!strcmp(cmd, "excise_sweep")) {
+    /* [st, binCut, values, power, hot, cut] = gnsscorr_mex('excise_sweep', hSrc, hDst, firstSample0, nSamples, limit[, widen[, gain]]):
+     * gc_excise_sweep; every output past st is asked of the library only when it is asked for here */
+    if (nrhs < 6) mexErrMsgIdAndTxt("gnsscorr:usage", "excise_sweep: hSrc, hDst, firstSample0, nSamples, limit (one real value per bin)[, widen[, gain]]");
+    const size_t nfft = mxGetNumberOfElements(prhs[5]);
+    const int have_gain = nrhs > 7 && mxGetNumberOfElements(prhs[7]) > 0;
+    const double first = mxGetScalar(prhs[3]), count = mxGetScalar(prhs[4]), widen = nrhs > 6 && mxGetNumberOfElements(prhs[6]) > 0 ? mxGetScalar(prhs[6]) : 0.0;
+#ifndef GNSSCORR_TEST_MEX_H /* (the test-only mex.h builds no complex arrays and has no mxIsComplex) */
+    if (mxIsComplex(prhs[5]) || (have_gain && mxIsComplex(prhs[7]))) mexErrMsgIdAndTxt("gnsscorr:usage", "excise_sweep: limit and gain must be real");
+#endif
+    if (!(mxIsDouble(prhs[5]) || mxIsSingle(prhs[5])) || nfft < 4 || nfft > 2147483647u)
+      mexErrMsgIdAndTxt("gnsscorr:usage", "excise_sweep: limit must be real double or single, one value per bin of an even transform length >= 4");
+    if (have_gain && (!(mxIsDouble(prhs[7]) || mxIsSingle(prhs[7])) || mxGetNumberOfElements(prhs[7]) != nfft))
+      mexErrMsgIdAndTxt("gnsscorr:usage", "excise_sweep: gain must be real double or single, one value per bin as the limit, or []");
+    if (!(first >= -9007199254740992.0 && first <= 9007199254740992.0) || first != (double)(int64_t)first ||
+        !(count >= -9007199254740992.0 && count <= 9007199254740992.0) || count != (double)(int64_t)count ||
+        !(widen >= -2147483648.0 && widen <= 2147483647.0) || widen != (double)(int32_t)widen)
+      mexErrMsgIdAndTxt("gnsscorr:usage", "excise_sweep: firstSample0, nSamples and widen must be whole numbers that fit their fields");
+    gc_context *const hs = handle(prhs[1]), *const hd = handle(prhs[2]);
+    gc_excise_sweep_params p;
+    p.first_sample = (int64_t)first;
+    p.nsamples = (int64_t)count;
+    p.nfft = (int32_t)nfft;
+    p.widen = (int32_t)widen;
+    /* the outputs are sized only for a range that lies in the record: any other call is the library's to refuse, and gets no arrays */
+    void* ptr = NULL;
+    uint64_t have = 0;
+    const int sized = !(nfft & 1) && p.first_sample >= 0 && p.nsamples >= 1 && gc_if_buffer(hs, &ptr, &have) == GC_OK &&
+                      (uint64_t)p.first_sample <= have && (uint64_t)p.nsamples <= have - (uint64_t)p.first_sample;
+    const mwSize H = (mwSize)(nfft / 2), K = sized ? (mwSize)(((uint64_t)p.nsamples + H - 1) / H + 1) : 0, W = (mwSize)((nfft + 63) / 64);
+    gc_excise_sweep_out out = {NULL, NULL, NULL, NULL, NULL};
+    if (nlhs > 1) plhs[1] = mxCreateNumericMatrix(sized ? (mwSize)nfft : 0, 1, mxINT64_CLASS, mxREAL);
+    if (nlhs > 2) plhs[2] = mxCreateNumericMatrix(2, sized ? (mwSize)p.nsamples : 0, mxSINGLE_CLASS, mxREAL);
+    if (nlhs > 3) plhs[3] = mxCreateNumericMatrix(sized ? (mwSize)nfft : 0, K, mxSINGLE_CLASS, mxREAL);
+    if (nlhs > 4) plhs[4] = mxCreateNumericMatrix(sized ? W : 0, K, mxUINT64_CLASS, mxREAL);
+    if (nlhs > 5) plhs[5] = mxCreateNumericMatrix(sized ? W : 0, K, mxUINT64_CLASS, mxREAL);
+    if (sized) {
+      if (nlhs > 1) out.bin_cut = (int64_t*)mxGetData(plhs[1]);
+      if (nlhs > 2) out.values = (float*)mxGetData(plhs[2]);
+      if (nlhs > 3) out.power = (float*)mxGetData(plhs[3]);
+      if (nlhs > 4) out.hot = (uint64_t*)mxGetData(plhs[4]);
+      if (nlhs > 5) out.cut = (uint64_t*)mxGetData(plhs[5]);
+    }
+    float* lim = (float*)mxMalloc(2 * nfft * sizeof(float));
+    float* g = have_gain ? lim + nfft : NULL;
+    for (size_t i = 0; i < nfft; ++i) {
+      lim[i] = mxIsDouble(prhs[5]) ? (float)mxGetDoubles(prhs[5])[i] : ((const float*)mxGetData(prhs[5]))[i];
+      if (g) g[i] = mxIsDouble(prhs[7]) ? (float)mxGetDoubles(prhs[7])[i] : ((const float*)mxGetData(prhs[7]))[i];
+    }
+    gc_excise_sweep_stats st;
+    int rc = gc_excise_sweep(hs, hd, &p, lim, g, &out, &st);
+    mxFree(lim);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
+    if (rc) fail("gc_excise_sweep");
+    plhs[0] = mxCreateDoubleMatrix(1, 5, mxREAL);
+    double* o = mxGetDoubles(plhs[0]);
+    o[0] = (double)st.segments, o[1] = (double)st.hot, o[2] = (double)st.cut, o[3] = (double)st.segments_cut, o[4] = (double)st.most_cut;
   } else if (!strcmp(cmd, "downconvert")) {
     /* [r, nco] = gnsscorr_mex('downconvert', hSrc, hDst, taps, decim[, carrFreq[, carrPhase[, firstSample0[, nOutputs[, dstFirst0]]]]]) */
     if (nrhs < 5) mexErrMsgIdAndTxt("gnsscorr:usage", "downconvert: hSrc, hDst, taps 2 x T, decim[, carrFreq[, carrPhase[, firstSample0[, nOutputs[, dstFirst0]]]]]");
