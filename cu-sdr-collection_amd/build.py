@@ -39,12 +39,15 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                                   # the same kernel at up to 64 carrier offsets, every table boundary computed once per group of bins;
                                   # gc_correlate_ddm_integrate: those maps added over runs of blocks on the device;
                                   # gc_correlate_ddm_search: that integration under many hypotheses, peaks picked on the device
-               # the acquisition, one translation unit per part of the search (acq_internal.h is what they share)
+               # the acquisition, one translation unit per part of the search (acq_internal.h is what they share; fft_plan.h: the plan and
+               # the storage order of a transform, which the record units below use too)
                "acq_fft.hip", "acq_coarse.hip", "acq_shift.hip", "acq_fine.hip", "acq_cond.hip", "acq_guard.hip", "navsync.hip",
-               "probe.hip",       # gc_probe_psd, gc_probe_histogram: a record's Welch spectrum (on acq_fft.hip's pass kernels) and level histograms
+               "seg_fft.hip",     # the segment transform probe.hip and excise.hip share (seg_fft.h): a tile's rows gathered from the record and
+                                  # transformed on acq_fft.hip's pass kernels, the tile budget and walk, the per-context plan state
+               "probe.hip",       # gc_probe_psd, gc_probe_histogram: a record's Welch spectrum (on seg_fft.hip's transform) and level histograms
                "cancel.hip",      # gc_cancel: tracked components rebuilt in float64 from their descriptors and subtracted from the record
                "excise.hip",      # gc_excise_pulses: samples over a level, and a guard around them, blanked in the record (integers throughout);
-                                  # gc_excise_bins: a gain per frequency bin by weighted overlap-add on acq_fft.hip's pass kernels;
+                                  # gc_excise_bins: a gain per frequency bin by weighted overlap-add on seg_fft.hip's transform;
                                   # gc_excise_sweep: the same overlap-add with a decision per segment and bin (mark, apply, integer counts)
                "ddc.hip"]         # gc_downconvert: complex FIR, decimation, a 64-bit NCO and requantisation into a second record, float64
 
@@ -60,7 +63,7 @@ LIBS = {
     "libgnsscorr_tuning.so": [_tuned(u) for u in _CORR_UNITS],
     "libgnsssynth.so": ["synth.hip"],
 }
-HEADERS = ["gc_internal.h", "corr_common.h", "record_fmt.h", "record_check.h", "replica_f64.h", "launch_plan.h", "bank_plan.h", "probe_plan.h", "excise_plan.h", "ddc_plan.h", "devloop.h", "acq_guard.h", "acq_internal.h", os.path.join("..", "..", "include", "gnsscorr.h")]
+HEADERS = ["gc_internal.h", "corr_common.h", "record_fmt.h", "record_check.h", "replica_f64.h", "launch_plan.h", "bank_plan.h", "probe_plan.h", "excise_plan.h", "ddc_plan.h", "devloop.h", "acq_guard.h", "acq_internal.h", "fft_plan.h", "seg_fft.h", os.path.join("..", "..", "include", "gnsscorr.h")]
 # --offload-compress: the gfx950 code objects inside the fat binary are zstd-compressed (10.1 -> ~1.6 MB; the HIP runtime inflates them
 # when the library is loaded: ~20 ms once per process)
 FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",

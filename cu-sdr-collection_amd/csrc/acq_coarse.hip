@@ -923,11 +923,7 @@ static int coarse_search(gc_context* ctx, const gc_acq_params* p, int nprn, int 
       a.n = pl.n;
       a.tw = s->tw;
       a.inverse = 1;
-      fill_sub(a, pl.p2);
-      a.nvec = pl.n1;
-      a.estride = 1;
-      a.vstride = pl.n2;
-      a.cols = choose_cols(a.len, a.estride);
+      rows_pass(a, pl);
       a.pre = PRE_MUL_CONJ;
       a.post = POST_TWIDDLE;
       a.in = s->sig;
@@ -954,11 +950,7 @@ static int coarse_search(gc_context* ctx, const gc_acq_params* p, int nprn, int 
       a.out_blocked = 0;
       a.row_reps = 0;
       a.in_blocked = hblock;
-      fill_sub(a, pl.p1);
-      a.nvec = pl.n2;
-      a.estride = pl.n2;
-      a.vstride = 1;
-      a.cols = choose_cols(a.len, a.estride);
+      columns_pass(a, pl);
       a.pre = PRE_NONE;
       a.post = POST_ABS_ACC;
       a.in = tmp;

@@ -13,10 +13,12 @@
 //     the twiddles, abs() and the non-coherent sum over hops are fused into the passes;
 //   * the peak pick reproduces max(max(.)) first-occurrence semantics with exact float compares.
 //
-// This file: the transform plans, the pass kernels (run-time fft_pass_kernel, per-shape fft_pass_ct, the fused kernel of the tuning
-// build), launch_pass / forward.  The searches that use them: acq_coarse.hip, acq_shift.hip.
+// This file: the transform plans (declared in fft_plan.h with the storage order), the pass kernels (run-time fft_pass_kernel,
+// per-shape fft_pass_ct, the fused kernel of the tuning build), launch_pass, the geometry of a pass (columns_pass, rows_pass) and the
+// one two-pass sequence (two_pass; forward and seg_fft.hip's transform_rows are calls of it).  The searches that use them:
+// acq_coarse.hip, acq_shift.hip; the record units' segment transforms: seg_fft.hip.
 #include "acq_internal.h"
-#include "record_fmt.h"
+#include "seg_fft.h"
 
 using namespace gcacq;
 
@@ -1547,14 +1549,8 @@ int handover_block(const Plan& pl) {
   return 0;
 }
 
-void fill_sub(PassArgs& a, const SubPlan& sp) {
-  a.len = sp.len;
-  a.nrad = sp.nrad;
-  for (int i = 0; i < sp.nrad; ++i) a.rad[i] = sp.rad[i];
-}
-
 // columns per tile: keep 2*L*C*8 bytes <= 64 KiB and L*C <= 8*256 (POST_ABS_ACC register slots)
-int choose_cols(int L, int estride) {
+static int choose_cols(int L, int estride) {
   int budget = 2048;
   if (const char* e = GC_TUNE_ENV("GC_ACQ_TILE")) budget = std::max(256, std::atoi(e));  // tuning: elements per tile
   int c = std::max(1, std::min(16, budget / L));
@@ -1564,111 +1560,56 @@ int choose_cols(int L, int estride) {
   return c;
 }
 
-// Forward transform of `nbatch` sequences produced by `pre` into `dst` (layout [k1][k2]).
-int forward(gc_context* ctx, AcqScratch* s, PassArgs base, int pre, long long nbatch, float2* dst) {
-  const Plan& pl = s->plan;
-  PassArgs a = base;
-  a.n = pl.n;
-  a.tw = s->tw;
-  a.inverse = 0;
-  // F1: columns (length n1, element stride n2), twiddle, store [k1][n2]
+static void fill_sub(PassArgs& a, const SubPlan& sp) {
+  a.len = sp.len;
+  a.nrad = sp.nrad;
+  for (int i = 0; i < sp.nrad; ++i) a.rad[i] = sp.rad[i];
+}
+
+void columns_pass(PassArgs& a, const Plan& pl) {  // vectors of n1 values, n2 apart
   fill_sub(a, pl.p1);
   a.nvec = pl.n2;
   a.estride = pl.n2;
   a.vstride = 1;
   a.cols = choose_cols(a.len, a.estride);
-  a.pre = pre;
-  a.post = POST_TWIDDLE;
-  a.out = s->tmp;
-  a.out_batch_stride = pl.n;
-  int rc = launch_pass(ctx, a, nbatch);
-  if (rc) return rc;
-  // F2: rows (length n2, contiguous)
+}
+
+void rows_pass(PassArgs& a, const Plan& pl) {  // vectors of n2 values, contiguous
   fill_sub(a, pl.p2);
   a.nvec = pl.n1;
   a.estride = 1;
   a.vstride = pl.n2;
   a.cols = choose_cols(a.len, a.estride);
-  a.pre = PRE_NONE;
-  a.post = POST_STORE;
-  a.in = s->tmp;
-  a.in_batch_stride = pl.n;
-  a.out = dst;
-  a.out_batch_stride = pl.n;
-  return launch_pass(ctx, a, nbatch);
 }
 
-}  // namespace gcacq
-namespace {
-// One workgroup per kFftThreads consecutive values of one row (gather_rows); row 0 is segment k0 of span span0.  The division is
-// taken only by the rows behind a span's end (wave-uniform), and the record is read without a branch - outside the span a sample
-// of the span that is not used - so that it and the window's value are in flight together.
-template <int MODE>
-__global__ __launch_bounds__(kFftThreads) void gather_rows_kernel(const uint8_t* __restrict__ rec, const RowGather r, long long span0, long long k0, int nfft,
-                                                                   int blocks_per_row, const float* __restrict__ win, float2* __restrict__ rows) {
-  const long long t = blockIdx.x / (unsigned)blocks_per_row;
-  const int n = (int)(blockIdx.x - (unsigned)(t * blocks_per_row)) * kFftThreads + (int)threadIdx.x;
-  if (n >= nfft) return;
-  long long span = span0, k = k0 + t;
-  if (k >= r.K) {
-    const long long q = k / r.K;
-    span += q;
-    k -= q * r.K;
-  }
-  const long long m = k * r.step - r.lead + n;
-  const bool inside = m >= 0 && m < r.nsamples;
-  int c0, c1;
-  gcorr::file_sample<MODE>(rec, r.first + span * r.nsamples + (inside ? m : 0), c0, c1);
-  const float w = win[n];
-  rows[t * nfft + n] = make_float2(w * (float)(inside ? c0 : 0), w * (float)(inside ? c1 : 0));  // a real record: w * 0 = +0, the windows are not negative
-}
-}  // namespace
-namespace gcacq {
-int gather_rows(gc_context* ctx, const RowGather& r, long long g0, long long nrows, int nfft, const float* win, float2* rows) {
-  const int bpr = (nfft + kFftThreads - 1) / kFftThreads;
-  const long long span0 = g0 / r.K, k0 = g0 - span0 * r.K;
-  gcorr::gc_with_file_mode(gcorr::gc_record_mode(ctx), [&](auto m) {
-    hipLaunchKernelGGL(gather_rows_kernel<decltype(m)::value>, dim3((unsigned int)(nrows * bpr)), dim3(kFftThreads), 0, ctx->stream, ctx->d_if, r, span0, k0, nfft,
-                       bpr, win, rows);
-  });
-  GC_HIP(hipGetLastError());
-  return GC_OK;
-}
-
-int transform_rows(gc_context* ctx, const Plan& pl, const float2* tw, float2* a_rows, float2* b_rows, long long nbatch, int inverse) {
-  PassArgs a;
-  std::memset(&a, 0, sizeof a);
+int two_pass(gc_context* ctx, const Plan& pl, const float2* tw, PassArgs a, int pre, int inverse, float2* mid, float2* dst, long long nbatch) {
   a.n = pl.n;
   a.tw = tw;
   a.inverse = inverse;
-  fill_sub(a, pl.p1);
-  a.nvec = pl.n2;
-  a.estride = pl.n2;
-  a.vstride = 1;
-  a.cols = choose_cols(a.len, a.estride);
-  a.pre = PRE_NONE;
+  columns_pass(a, pl);  // twiddle, store [k1][n2]
+  a.pre = pre;
   a.post = POST_TWIDDLE;
-  a.in = a_rows;
-  a.in_batch_stride = pl.n;
-  a.out = b_rows;
+  a.out = mid;
   a.out_batch_stride = pl.n;
-  int rc = launch_pass(ctx, a, nbatch);
+  const int rc = launch_pass(ctx, a, nbatch);
   if (rc) return rc;
-  fill_sub(a, pl.p2);
-  a.nvec = pl.n1;
-  a.estride = 1;
-  a.vstride = pl.n2;
-  a.cols = choose_cols(a.len, a.estride);
+  rows_pass(a, pl);
+  a.pre = PRE_NONE;
   a.post = POST_STORE;
-  a.in = b_rows;
-  a.out = a_rows;
+  a.in = mid;
+  a.in_batch_stride = pl.n;
+  a.out = dst;
   return launch_pass(ctx, a, nbatch);
 }
+
+int forward(gc_context* ctx, AcqScratch* s, PassArgs base, int pre, long long nbatch, float2* dst) {
+  return two_pass(ctx, s->plan, s->tw, base, pre, 0, s->tmp, dst, nbatch);
+}
+
 }  // namespace gcacq
 
-// Test hook: forward FFT of `nbatch` host sequences of length n (complex64) with the library's
-// transform; output in natural frequency order.
-
+// Test hook: the library's transform of `nbatch` host sequences of length n (complex64), forward or unnormalised inverse; output in
+// natural frequency order.
 extern "C" int gc_debug_fft(gc_context* ctx, int n, int nbatch, const float* in, float* out_natural, int inverse) {
   if (!ctx || n <= 1 || nbatch <= 0 || !in || !out_natural) return GC_E_INVALID;
   GC_HIP(hipSetDevice(ctx->device));
@@ -1677,41 +1618,14 @@ extern "C" int gc_debug_fft(gc_context* ctx, int n, int nbatch, const float* in,
   if (rc) return rc;
   const Plan& pl = s->plan;
   GC_HIP(hipMemcpy(s->sig, in, (size_t)nbatch * n * sizeof(float2), hipMemcpyHostToDevice));
-  PassArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.n = pl.n;
-  a.tw = s->tw;
-  a.inverse = inverse;
-  fill_sub(a, pl.p1);
-  a.nvec = pl.n2;
-  a.estride = pl.n2;
-  a.vstride = 1;
-  a.cols = choose_cols(a.len, a.estride);
-  a.pre = PRE_NONE;
-  a.post = POST_TWIDDLE;
-  a.in = s->sig;
-  a.in_batch_stride = pl.n;
-  a.out = s->tmp;
-  a.out_batch_stride = pl.n;
-  rc = launch_pass(ctx, a, nbatch);
-  if (rc) return rc;
-  fill_sub(a, pl.p2);
-  a.nvec = pl.n1;
-  a.estride = 1;
-  a.vstride = pl.n2;
-  a.cols = choose_cols(a.len, a.estride);
-  a.post = POST_STORE;
-  a.in = s->tmp;
-  a.out = s->sig;
-  rc = launch_pass(ctx, a, nbatch);
+  rc = transform_rows(ctx, pl, s->tw, s->sig, s->tmp, nbatch, inverse);
   if (rc) return rc;
   std::vector<float2> h((size_t)nbatch * n);
   GC_HIP(hipMemcpyAsync(h.data(), s->sig, h.size() * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
   GC_HIP(hipStreamSynchronize(ctx->stream));
   float2* o = (float2*)out_natural;
   for (int b = 0; b < nbatch; ++b)
-    for (int k1 = 0; k1 < pl.n1; ++k1)
-      for (int k2 = 0; k2 < pl.n2; ++k2) o[(size_t)b * n + k1 + (size_t)pl.n1 * k2] = h[(size_t)b * n + (size_t)k1 * pl.n2 + k2];
+    for (int pos = 0; pos < n; ++pos) o[(size_t)b * n + fft_bin_at(pos, pl.n1, pl.n2)] = h[(size_t)b * n + pos];
   return GC_OK;
 }
 

@@ -1,4 +1,5 @@
-// acq_internal.h - what the translation units of the acquisition share (csrc/acq_fft.hip: plans, pass kernels, launch_pass;
+// acq_internal.h - what the translation units of the acquisition share (csrc/acq_fft.hip: pass kernels, launch_pass, pass geometry,
+// the two-pass transform - its plan is fft_plan.h's, which the record units reach without this header through seg_fft.h;
 // acq_coarse.hip: the carrier-per-bin searches, peak reductions, scratch; acq_shift.hip: the circshift family; acq_fine.hip: fine
 // frequency stages; acq_cond.hip: input conditioning; acq_guard.hip: float64 re-evaluation of single cells).
 // Reference: GPS/GPS_L1CA/include/acquisition.m:116-260 and its per-package variants.
@@ -14,26 +15,15 @@
 #include <vector>
 
 #include "acq_guard.h"
+#include "fft_plan.h"
 #include "gc_internal.h"
 
 namespace gcacq {
 
 constexpr int kGuardListCap = 4096;  // cells within gc_acq_tie_eps of a PRN's winner that the guard's slow path re-evaluates at most
-constexpr int kMaxRadices = 12;
 constexpr int kMaxPassLen = 2048;  // longest vector of a pass: one tile of 2048 complex values (choose_cols), i.e. transforms of up to 2048 x 2048 points
 constexpr int kFftThreads = 256;
 constexpr int kFftSlots = 8;  // tile elements per thread at most: L*C <= kFftSlots * kFftThreads
-
-struct SubPlan {
-  int len;
-  int nrad;
-  int rad[kMaxRadices];
-};
-
-struct Plan {
-  int n, n1, n2;  // n = n1 * n2; n1 = column length (stride n2), n2 = row length (contiguous)
-  SubPlan p1, p2;
-};
 
 // Division of a small wave-uniform number by a run-time constant of the launch (hops per bin, bins per spectrum, hop groups ...) as one
 // multiply-high: q = (x * mul) >> 32 with mul = floor(2^32 / d) + 1 is floor(x / d) whenever x * d < 2^32 (launch_pass checks the
@@ -310,31 +300,19 @@ struct AcqStreams {
   hipStream_t main = nullptr, lane = nullptr;
 };
 
-// ---- acq_fft.hip ------------------------------------------------------------------------------------------------------------------
-bool make_plan(int n, Plan* pl);
-// make_plan for a caller that has no other length to try: GC_E_UNSUPPORTED and the planner's message where it refuses n
-int plan_or_refuse(int n, Plan* pl);
-// exp(-2 pi i k / n), k < n, computed in float64 and rounded once, into d_tw on the context's stream, which is waited for
-int upload_twiddles(gc_context* ctx, int n, float2* d_tw);
+// ---- acq_fft.hip (the plan, plan_or_refuse and upload_twiddles: fft_plan.h) -----------------------------------------------------------
 // tile width C1 of the specialised columns pass for vectors of `len`, `nvec` of them per transform; 0: no specialised pass
 int ct_columns_tile(int len, int nvec);
 int launch_pass(gc_context* ctx, PassArgs& a, long long nbatch_groups, bool* used_ct = nullptr);
 int handover_block(const Plan& pl);
-void fill_sub(PassArgs& a, const SubPlan& sp);
-int choose_cols(int L, int estride = 1);
-// Transform of `nbatch` rows of a (natural order, pl.n values each) in place, b the intermediate, with the twiddle table tw of pl.n
-// entries; the result in storage order [k1][k2] (natural index k1 + n1 k2).  The two launches of gc_debug_fft: columns with
-// PRE_NONE / POST_TWIDDLE, rows with PRE_NONE / POST_STORE; inverse = 1 is the unnormalised inverse.  Shared by probe.hip and excise.hip.
-int transform_rows(gc_context* ctx, const Plan& pl, const float2* tw, float2* a_rows, float2* b_rows, long long nbatch, int inverse);
-// The rows such a transform takes, from the context's record in file order (c1 = 0 for a real record): the samples from `first` are
-// cut into spans of `nsamples`, a span into K segments `step` apart, the first one `lead` samples in front of the span.  Row t of
-// rows[nrows][nfft] is segment g = g0 + t (span = g / K, k = g - span K): value n is win[n] * x of span sample m = k step - lead + n,
-// and zero where m lies outside [0, nsamples).
-struct RowGather {
-  long long first, nsamples, step, K, lead;
-};
-int gather_rows(gc_context* ctx, const RowGather& r, long long g0, long long nrows, int nfft, const float* win, float2* rows);
-// Forward transform of `nbatch` sequences produced by `pre` into `dst` (layout [k1][k2])
+// The geometry of a pass (len, radices, nvec, estride, vstride, cols) from the plan - columns: the n2 vectors of n1 values, n2 apart;
+// rows: the n1 contiguous vectors of n2 values.  A forward transform runs columns then rows, the searches' inverse rows then columns.
+void columns_pass(PassArgs& a, const Plan& pl);
+void rows_pass(PassArgs& a, const Plan& pl);
+// A transform of `nbatch` sequences as its two launches: the columns pass, `pre` on the way in (a holds in, in_batch_stride and the pre-operation's
+// fields) / POST_TWIDDLE into mid, then the rows pass PRE_NONE / POST_STORE from mid into dst ([k1][k2], fft_plan.h; dst may be a.in); inverse = 1: unnormalised.
+int two_pass(gc_context* ctx, const Plan& pl, const float2* tw, PassArgs a, int pre, int inverse, float2* mid, float2* dst, long long nbatch);
+// Forward transform of `nbatch` sequences produced by `pre` into `dst` (layout [k1][k2]): two_pass through s->tmp
 int forward(gc_context* ctx, AcqScratch* s, PassArgs base, int pre, long long nbatch, float2* dst);
 // GC_ACQ_FUSED (tuning build): the whole inverse side of a 36 000- / 24 000-point search in one launch; false: no fused kernel for this plan
 struct FusedArgs {

@@ -209,11 +209,7 @@ static int shift_search_passes(gc_context* ctx, AcqScratch* s, int narms, const 
     a.n = pl.n;
     a.tw = s->tw;
     a.inverse = 1;
-    fill_sub(a, pl.p2);
-    a.nvec = pl.n1;
-    a.estride = 1;
-    a.vstride = pl.n2;
-    a.cols = choose_cols(a.len, a.estride);
+    rows_pass(a, pl);
     a.pre = PRE_MUL_CONJ;
     a.post = POST_TWIDDLE;
     a.in = s->sig;
@@ -236,11 +232,7 @@ static int shift_search_passes(gc_context* ctx, AcqScratch* s, int narms, const 
       a.arm_hops = 1;
       for (int k = 0; k < 4; ++k) a.arm_w[k] = (arm_weight && k < narms) ? (float)arm_weight[k] : 1.0f;
     }
-    fill_sub(a, pl.p1);
-    a.nvec = pl.n2;
-    a.estride = pl.n2;
-    a.vstride = 1;
-    a.cols = choose_cols(a.len, a.estride);
+    columns_pass(a, pl);
     a.pre = PRE_NONE;
     a.shift_bins = 0;
     a.post = POST_ABS_ACC;
@@ -333,11 +325,7 @@ static int shift_row_passes(gc_context* ctx, AcqScratch* s, int irow, int narms,
     a.n = pl.n;
     a.tw = s->tw;
     a.inverse = 1;
-    fill_sub(a, pl.p2);
-    a.nvec = pl.n1;
-    a.estride = 1;
-    a.vstride = pl.n2;
-    a.cols = choose_cols(a.len, a.estride);
+    rows_pass(a, pl);
     a.pre = PRE_MUL_CONJ;
     a.post = POST_TWIDDLE;
     a.in = s->sig;
@@ -351,11 +339,7 @@ static int shift_row_passes(gc_context* ctx, AcqScratch* s, int irow, int narms,
     a.batch0 = irow;
     int rc = launch_pass(ctx, a, 1);
     if (rc) return rc;
-    fill_sub(a, pl.p1);
-    a.nvec = pl.n2;
-    a.estride = pl.n2;
-    a.vstride = 1;
-    a.cols = choose_cols(a.len, a.estride);
+    columns_pass(a, pl);
     a.pre = PRE_NONE;
     a.shift_bins = 0;
     a.post = POST_ABS_ACC;

@@ -16,11 +16,12 @@
 // No atomics; integer sums; a sample's output depends on its own bytes and the hot bits within the guards of it.
 //
 // gc_excise_bins: a gain per frequency bin, by weighted overlap-add (sine window, half-overlapping segments) on the acquisition's
-// float32 transform.  The segment list is cut into tiles (excise_plan.h); per tile
-//   gather_rows            converts and windows the tile's segments into float2 rows, zero outside the range (acq_fft.hip),
-//   transform_rows         forward: the pass pair the probe runs (acq_fft.hip),
-//   excise_gain_kernel     multiplies by the gain and moves storage position [k1][k2] to natural bin k1 + n1 k2, where the inverse
-//                          pair expects it,
+// float32 transform.  The segment list is cut into tiles (seg_fft.h, shared with the probe: budget, walk, rows and transform state;
+// excise_plan.h: the samples a tile finishes); per tile
+//   gather_rows            converts and windows the tile's segments into float2 rows, zero outside the range (seg_fft.hip),
+//   transform_rows         forward: the pass pair the probe runs (seg_fft.hip),
+//   excise_gain_kernel     multiplies by the gain and moves every value from its storage position to its natural bin (fft_plan.h),
+//                          where the inverse pair expects it,
 //   transform_rows         inverse = 1,
 //   excise_add_kernel      one thread per 16 bytes of record: y = s v of the earlier segment's second half + s v of the later
 //                          segment's first half, quantised into a RecVec; y itself to a float2 buffer of the range when the caller
@@ -42,7 +43,6 @@
 #include <algorithm>
 #include <cmath>
 
-#include "acq_internal.h"
 #include "excise_plan.h"
 #include "record_fmt.h"
 
@@ -57,9 +57,8 @@ static_assert(kExciseTileWords == kExciseWG, "one thread per word of the tile's 
 
 struct ExciseState {  // grow-only device buffers of the context (released by gc_destroy)
   GcBuf bitmap, tiles, stats;  // gc_excise_pulses
-  int n = 0;                   // gc_excise_bins: transform length of plan, tw and win (0: none)
-  gcacq::Plan plan;
-  GcBuf tw, win, gain, rows_a, rows_b, carry, values;  // win: w[nfft] then s[nfft]
+  gcacq::SegFft fft;           // gc_excise_bins: fft.n is also the length that win holds
+  GcBuf win, gain, carry, values;  // win: w[nfft] then s[nfft]
   GcBuf limit, hot, cut, power, counts;                // gc_excise_sweep: a tile's mask rows and power; the four sums, then bin_cut
 };
 
@@ -259,14 +258,12 @@ __global__ __launch_bounds__(kExciseWG) void excise_combine_kernel(const TileRun
 
 // ---- gc_excise_bins ------------------------------------------------------------------------------------------------------------------
 
-// out[t][b] = gain[b] * in[t][storage position of bin b], b = k1 + n1 k2 at position k1 n2 + k2
+// out[t][b] = gain[b] * in[t][storage position of bin b]
 __global__ __launch_bounds__(kExciseWG) void excise_gain_kernel(const float2* __restrict__ in, float2* __restrict__ out, const float* __restrict__ gain,
                                                                  int nfft, int n1, int n2, int blocks_per_row) {
-  const long long t = blockIdx.x / (unsigned)blocks_per_row;
-  const int b = (int)(blockIdx.x - (unsigned)(t * blocks_per_row)) * kExciseWG + (int)threadIdx.x;
+  const auto [t, b] = gcacq::row_element<kExciseWG>(blocks_per_row);
   if (b >= nfft) return;
-  const int k2 = b / n1, k1 = b - k2 * n1;
-  const float2 x = in[t * nfft + k1 * n2 + k2];
+  const float2 x = in[t * nfft + gcacq::fft_pos_of(b, n1, n2)];
   const float g = gain[b];
   out[t * nfft + b] = make_float2(g * x.x, g * x.y);
 }
@@ -288,12 +285,10 @@ struct SweepArgs {
 // One lane per bin, in natural order: P and the comparison; a wave's ballot is one word of the segment's hot row.  The lanes from
 // nfft on vote 0, so the last word's upper bits are 0.
 __global__ __launch_bounds__(kExciseWG) void excise_sweep_mark_kernel(const SweepArgs p) {
-  const long long t = blockIdx.x / (unsigned)p.blocks_per_row;
-  const int b = (int)(blockIdx.x - (unsigned)(t * p.blocks_per_row)) * kExciseWG + (int)threadIdx.x;
+  const auto [t, b] = gcacq::row_element<kExciseWG>(p.blocks_per_row);
   bool hot = false;
   if (b < p.nfft) {
-    const int k2 = b / p.n1, k1 = b - k2 * p.n1;
-    const float2 x = p.x[t * p.nfft + k1 * p.n2 + k2];
+    const float2 x = p.x[t * p.nfft + gcacq::fft_pos_of(b, p.n1, p.n2)];
     const float pw = __fadd_rn(__fmul_rn(x.x, x.x), __fmul_rn(x.y, x.y));  // two products and a sum, each rounded by itself
     hot = pw > p.limit[b];
     if (p.power) p.power[t * p.nfft + b] = pw;
@@ -317,8 +312,7 @@ __device__ __forceinline__ bool any_hot(const unsigned long long* __restrict__ r
 // One lane per bin: cut iff a hot bin lies within `widen` of it around the circle of nfft bins (the bits are addressed by bin number,
 // so an nfft that is no multiple of 64 wraps where it should); Y = 0 where cut, else gain * X, moved as excise_gain_kernel moves it.
 __global__ __launch_bounds__(kExciseWG) void excise_sweep_apply_kernel(const SweepArgs p) {
-  const long long t = blockIdx.x / (unsigned)p.blocks_per_row;
-  const int b = (int)(blockIdx.x - (unsigned)(t * p.blocks_per_row)) * kExciseWG + (int)threadIdx.x;
+  const auto [t, b] = gcacq::row_element<kExciseWG>(p.blocks_per_row);
   bool cut = false;
   if (b < p.nfft) {
     const unsigned long long* const row = p.hot + t * p.W;
@@ -329,8 +323,7 @@ __global__ __launch_bounds__(kExciseWG) void excise_sweep_apply_kernel(const Swe
     else cut = any_hot(row, lo, hi);
     float2 y = make_float2(0.0f, 0.0f);
     if (!cut) {
-      const int k2 = b / p.n1, k1 = b - k2 * p.n1;
-      y = p.x[t * p.nfft + k1 * p.n2 + k2];
+      y = p.x[t * p.nfft + gcacq::fft_pos_of(b, p.n1, p.n2)];
       if (p.gain) {
         const float g = p.gain[b];
         y = make_float2(g * y.x, g * y.y);
@@ -390,7 +383,7 @@ __global__ __launch_bounds__(kExciseWG) void excise_sweep_bins_kernel(const unsi
 }
 
 struct AddArgs {
-  const float2* rows;   // the tile's inverse transforms, storage order: value n of a row at (n mod n1) n2 + n / n1
+  const float2* rows;   // the tile's inverse transforms, storage order (fft_plan.h)
   const float2* carry;  // s v of the second half of segment g0 - 1 (g0 > 0)
   const float* scale;   // s[nfft]
   uint8_t* rec;         // the destination record (out of place: a copy of the source)
@@ -402,8 +395,7 @@ struct AddArgs {
 };
 
 __device__ __forceinline__ float2 scaled(const AddArgs& p, long long row, int n) {
-  const int k2 = n / p.n1, k1 = n - k2 * p.n1;
-  const float2 v = p.rows[row * p.nfft + k1 * p.n2 + k2];
+  const float2 v = p.rows[row * p.nfft + gcacq::fft_pos_of(n, p.n1, p.n2)];
   const float s = p.scale[n];
   return make_float2(s * v.x, s * v.y);
 }
@@ -444,8 +436,8 @@ __global__ __launch_bounds__(kExciseWG) void excise_carry_kernel(const AddArgs p
 void gc_excise_free(gc_context* ctx) {
   ExciseState* s = static_cast<ExciseState*>(ctx->excise);
   if (!s) return;
-  for (GcBuf* b : {&s->bitmap, &s->tiles, &s->stats, &s->tw, &s->win, &s->gain, &s->rows_a, &s->rows_b, &s->carry, &s->values, &s->limit,
-                   &s->hot, &s->cut, &s->power, &s->counts})
+  gcacq::seg_fft_free(&s->fft);
+  for (GcBuf* b : {&s->bitmap, &s->tiles, &s->stats, &s->win, &s->gain, &s->carry, &s->values, &s->limit, &s->hot, &s->cut, &s->power, &s->counts})
     gc_buf_free(*b);
   delete s;
   ctx->excise = nullptr;
@@ -533,9 +525,8 @@ int excise_overlap_add(const char* who, gc_context* src, gc_context* dst, long l
   if (dst != src) GC_HIP(hipStreamSynchronize(dst->stream));  // the destination's own pending work comes first
   ExciseState* s = gc_unit_state<ExciseState>(src->excise);
   if (!s) return gc_nomem(who);
-  const size_t tile_rows = (size_t)std::min(pl.tile, pl.K), rows_bytes = tile_rows * (size_t)nfft * sizeof(float2);
-  if (gc_buf_reserve(s->rows_a, rows_bytes, false) != hipSuccess || gc_buf_reserve(s->rows_b, rows_bytes, false) != hipSuccess ||
-      gc_buf_reserve(s->gain, (size_t)nfft * sizeof(float), false) != hipSuccess || gc_buf_reserve(s->carry, (size_t)H * sizeof(float2), false) != hipSuccess ||
+  const size_t tile_rows = (size_t)std::min(pl.tile, pl.K);
+  if (gc_buf_reserve(s->gain, (size_t)nfft * sizeof(float), false) != hipSuccess || gc_buf_reserve(s->carry, (size_t)H * sizeof(float2), false) != hipSuccess ||
       (values && gc_buf_reserve(s->values, (size_t)nsamples * sizeof(float2), false) != hipSuccess))
     return gc_nomem(who);
   const size_t counts_bytes = (4 + (size_t)nfft) * sizeof(unsigned long long);  // the four sums, then bin_cut
@@ -546,23 +537,22 @@ int excise_overlap_add(const char* who, gc_context* src, gc_context* dst, long l
         (sw->out->power && gc_buf_reserve(s->power, tile_rows * (size_t)nfft * sizeof(float), false) != hipSuccess))
       return gc_nomem(who);
   }
-  if (s->n != nfft) {  // the plan, the twiddle table, the window w and the scale s of an nfft-point excision
-    s->n = 0;
-    if (gc_buf_reserve(s->tw, (size_t)nfft * sizeof(float2), false) != hipSuccess || gc_buf_reserve(s->win, 2 * (size_t)nfft * sizeof(float), false) != hipSuccess)
-      return gc_nomem(who);
+  std::vector<float> host_win;
+  if (s->fft.n != nfft) {  // the window w and the scale s of an nfft-point excision, queued in front of the plan's twiddle table
+    s->fft.n = 0;
+    if (gc_buf_reserve(s->win, 2 * (size_t)nfft * sizeof(float), false) != hipSuccess) return gc_nomem(who);
     const double pi = 3.14159265358979323846;
-    std::vector<float> win(2 * (size_t)nfft);
+    host_win.resize(2 * (size_t)nfft);
     for (int k = 0; k < nfft; ++k) {
       const float w = (float)std::sin(pi * ((double)k + 0.5) / (double)nfft);
-      win[(size_t)k] = w;
-      win[(size_t)nfft + (size_t)k] = (float)((double)w / (double)nfft);
+      host_win[(size_t)k] = w;
+      host_win[(size_t)nfft + (size_t)k] = (float)((double)w / (double)nfft);
     }
-    GC_HIP(hipMemcpyAsync(s->win.p, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice, src->stream));
-    rc = gcacq::upload_twiddles(src, nfft, (float2*)s->tw.p);  // waits for the stream: win is gone below
-    if (rc) return rc;
-    s->plan = plan;
-    s->n = nfft;
+    GC_HIP(hipMemcpyAsync(s->win.p, host_win.data(), host_win.size() * sizeof(float), hipMemcpyHostToDevice, src->stream));
   }
+  rc = gcacq::seg_fft_prepare(src, &s->fft, plan, (long long)tile_rows, who);  // a new length: waits for the stream, host_win may go
+  if (rc && !host_win.empty()) (void)hipStreamSynchronize(src->stream);
+  if (rc) return rc;
   if (gain) GC_HIP(hipMemcpyAsync(s->gain.p, gain, (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, src->stream));
   if (sw) {
     GC_HIP(hipMemcpyAsync(s->limit.p, sw->limit, (size_t)nfft * sizeof(float), hipMemcpyHostToDevice, src->stream));
@@ -572,7 +562,8 @@ int excise_overlap_add(const char* who, gc_context* src, gc_context* dst, long l
   if (dst->d_if != src->d_if)  // out of place: the add kernel works on a copy
     GC_HIP(hipMemcpyAsync(dst->d_if, src->d_if, (size_t)src->if_nsamples * (size_t)bps, hipMemcpyDeviceToDevice, src->stream));
   const int bpr = (nfft + kExciseWG - 1) / kExciseWG, per16 = 16 / bps;
-  float2 *const rows_a = (float2*)s->rows_a.p, *const rows_b = (float2*)s->rows_b.p;
+  float2 *const rows_a = (float2*)s->fft.rows_a.p, *const rows_b = (float2*)s->fft.rows_b.p;
+  const float2* const tw = (const float2*)s->fft.tw.p;
   const float* const win = (const float*)s->win.p;
   AddArgs a;
   a.rows = rows_b;
@@ -603,7 +594,7 @@ int excise_overlap_add(const char* who, gc_context* src, gc_context* dst, long l
     // the gather reads the SOURCE: in place its samples are this tile's and later ones', which no add kernel has written yet
     rc = gcacq::gather_rows(src, segs, t.g0, t.n, nfft, win, rows_a);
     if (rc) return rc;
-    rc = gcacq::transform_rows(src, s->plan, (const float2*)s->tw.p, rows_a, rows_b, t.n, 0);
+    rc = gcacq::transform_rows(src, s->fft.plan, tw, rows_a, rows_b, t.n, 0);
     if (rc) return rc;
     if (!sw) {
       hipLaunchKernelGGL(excise_gain_kernel, grid, wg, 0, src->stream, (const float2*)rows_a, rows_b, (const float*)s->gain.p, nfft, plan.n1, plan.n2, bpr);
@@ -625,7 +616,7 @@ int excise_overlap_add(const char* who, gc_context* src, gc_context* dst, long l
       if (m.power)
         GC_HIP(hipMemcpyAsync(sw->out->power + excise_power_offset(sw->pl, t), m.power, (size_t)t.n * (size_t)nfft * sizeof(float), hipMemcpyDeviceToHost, src->stream));
     }
-    rc = gcacq::transform_rows(src, s->plan, (const float2*)s->tw.p, rows_b, rows_a, t.n, 1);
+    rc = gcacq::transform_rows(src, s->fft.plan, tw, rows_b, rows_a, t.n, 1);
     if (rc) return rc;
     a.g0 = t.g0;
     a.m0 = t.m0;

@@ -1,7 +1,7 @@
 // excise_plan.h — what the drivers of the excision (excise.hip: gc_excise_pulses, gc_excise_bins, gc_excise_sweep) decide on the host, from integers:
 // the argument checks; how the blanker's range is laid over the hot-sample bitmap and cut into the tiles its kernels take one workgroup
-// each; the segment count of the spectral excision and the cut of its segment list into tiles whose rows fit a byte budget; the mask
-// rows of the swept excision.  Nothing
+// each; the segment count of the spectral excision and the samples a tile of its segment list finishes (the budget of a tile and
+// the walk over the list are seg_fft.h's, shared with the probe); the mask rows of the swept excision.  Nothing
 // here calls HIP, allocates on the device or launches; tests/excise_plan_shim.hip runs all of it without a device.  From the two
 // contexts the checks read d_if, device, if_nsamples, if_dtype and if_layout (record_check.h: the pair of records, the range).  The one refusal that is not decided here is the
 // transform planner's (make_plan, acq_fft.hip: GC_E_UNSUPPORTED).
@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "record_check.h"
+#include "seg_fft.h"
 
 constexpr int kExciseTile = 16384;                          // samples of the bitmap per workgroup of the mark and the blank kernel
 constexpr int kExciseTileWords = kExciseTile / 64;          // 64 samples per bitmap word
@@ -56,12 +57,9 @@ inline int excise_check_pulses(const gc_context* src, const gc_context* dst, con
 }
 
 // ---- gc_excise_bins: segments of nfft samples that overlap by half, cut into tiles whose rows fit a byte budget ------------------------
-// What one tile's rows may take: two buffers of float2 rows (the transform's passes go from one to the other and back), as the
-// probe's.  The library always passes the default and has no switch for it; the CPU tests pass budgets of a few segments.
-struct ExciseBudget {
-  long long tile_bytes = 128LL << 20;
-};
-
+// (seg_fft.h under the excision's names; the library always passes the default budget and has no switch for it)
+using ExciseBudget = SegBudget;
+inline long long excise_tile_segments(int nfft, const SegBudget& b) { return seg_tile_segments(nfft, b); }
 struct ExciseBinsPlan {
   long long H = 0;     // nfft / 2: the hop, and the samples a segment pair finishes
   long long K = 0;     // segments: ceil(nsamples / H) + 1; segment k covers the range-relative samples [(k - 1) H, (k + 1) H)
@@ -71,27 +69,19 @@ struct ExciseBinsPlan {
 
 // A tile [g0, g0 + n) of the segment list finishes the range samples [m0, m1): those whose two segments it holds, counting the
 // second half of segment g0 - 1 that the tile before it left behind (carried: g0 > 0).  The tile's last segment is the next carry.
-struct ExciseTile {
-  long long g0 = 0, n = 0;    // first segment, segments (0: before the first tile)
+struct ExciseTile : SegTile {
   long long carried = -1;     // the segment whose second half the tile reads from the carry buffer (-1: none)
   long long m0 = 0, m1 = 0;   // range samples the tile writes (empty: m0 >= m1)
 };
-
-inline long long excise_tile_segments(int nfft, const ExciseBudget& b) {
-  const long long row = 2LL * (long long)nfft * (long long)sizeof(float2);
-  const long long t = b.tile_bytes / row;
-  return t > 1 ? t : 1;
-}
 
 inline long long excise_segments(long long nsamples, int nfft) {
   const long long H = nfft / 2;
   return (nsamples + H - 1) / H + 1;
 }
 
+// the tile walk: for (ExciseTile t; excise_next_tile(pl, t);) - seg_next_tile and what the tile it names finishes
 inline bool excise_next_tile(const ExciseBinsPlan& pl, ExciseTile& t) {
-  t.g0 += t.n;
-  t.n = pl.tile < pl.K - t.g0 ? pl.tile : pl.K - t.g0;
-  if (t.n <= 0) return false;
+  if (!seg_next_tile(pl.tile, pl.K, t)) return false;
   t.carried = t.g0 > 0 ? t.g0 - 1 : -1;
   t.m0 = (t.g0 > 0 ? t.g0 - 1 : 0) * pl.H;
   t.m1 = (t.g0 + t.n - 1) * pl.H;
@@ -121,7 +111,7 @@ inline int excise_check_bins(const gc_context* src, const gc_context* dst, const
 
 // ... and what the contexts must hold for them: GC_E_STATE, GC_E_INVALID (a destination that does not match), GC_E_RANGE; then the plan
 inline int excise_check_segments(const char* who, const gc_context* src, const gc_context* dst, long long first_sample, long long nsamples, int nfft,
-                                 const ExciseBudget& b, ExciseBinsPlan* pl) {
+                                 const SegBudget& b, ExciseBinsPlan* pl) {
   int rc = check_record_pair(who, src, dst);
   if (rc) return rc;
   rc = check_record_range(who, src, first_sample, nsamples);
@@ -133,7 +123,7 @@ inline int excise_check_segments(const char* who, const gc_context* src, const g
   return GC_OK;
 }
 
-inline int excise_check_bins_state(const gc_context* src, const gc_context* dst, const gc_excise_bins_params* p, const ExciseBudget& b, ExciseBinsPlan* pl) {
+inline int excise_check_bins_state(const gc_context* src, const gc_context* dst, const gc_excise_bins_params* p, const SegBudget& b, ExciseBinsPlan* pl) {
   return excise_check_segments("gc_excise_bins", src, dst, (long long)p->first_sample, (long long)p->nsamples, p->nfft, b, pl);
 }
 
@@ -175,7 +165,7 @@ inline int excise_check_sweep(const gc_context* src, const gc_context* dst, cons
   return GC_OK;
 }
 
-inline int excise_check_sweep_state(const gc_context* src, const gc_context* dst, const gc_excise_sweep_params* p, const ExciseBudget& b, ExciseSweepPlan* pl) {
+inline int excise_check_sweep_state(const gc_context* src, const gc_context* dst, const gc_excise_sweep_params* p, const SegBudget& b, ExciseSweepPlan* pl) {
   ExciseBinsPlan seg;
   const int rc = excise_check_segments("gc_excise_sweep", src, dst, (long long)p->first_sample, (long long)p->nsamples, p->nfft, b, &seg);
   if (rc) return rc;

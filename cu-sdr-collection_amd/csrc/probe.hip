@@ -2,16 +2,15 @@
 // (probeData.m:76 the stretch of record, :104 z = first + i * second value of each pair, :128-131 pwelch(data, 32768, 2048, 32768, fs),
 // :146-163 hist(., -128:128) and dmax), computed where the record lives.  DESIGN.md 4.10.
 //
-// Spectrum: the (span, segment) list is cut into tiles (probe_plan.h); per tile
-//   gather_rows           converts and windows the tile's segments into float2 rows (acq_fft.hip, next to the transform it feeds),
-//   transform_rows        runs the acquisition's two pass kernels over the rows (the sequence gc_debug_fft launches),
+// Spectrum: the (span, segment) list is cut into tiles (seg_fft.h, shared with the excision); per tile
+//   gather_rows           converts and windows the tile's segments into float2 rows (seg_fft.hip, next to the transform it feeds),
+//   transform_rows        runs the acquisition's two pass kernels over the rows (seg_fft.hip),
 //   probe_power_kernel    adds |X|^2 of the tile's segments, in segment order, into the float64 accumulator of (span, bin).
 // Histogram: probe_hist_kernel counts into per-wave LDS histograms and writes one partial row per workgroup,
 //   probe_hist_combine_kernel adds the rows in 64-bit, one workgroup per bin.
-// The probe's plan, twiddle table, window, rows and accumulators are its own (ProbeState, kept in gc_context::probe): nothing of the
+// The probe's plan, twiddle table and rows (SegFft), window and accumulators are its own (ProbeState, kept in gc_context::probe): nothing of the
 // acquisition's scratch, the conditioned signal or the bank's buffers is read, written or reallocated.
 // A sample's components in file order are record_fmt.h's (file_sample, gc_with_file_mode); the range check is record_check.h's.
-#include "acq_internal.h"
 #include "probe_plan.h"
 #include "record_fmt.h"
 
@@ -24,28 +23,25 @@ constexpr int kHistWaves = kProbeThreads / 64;
 constexpr int kHistRow = 2 * GC_PROBE_HIST_BINS;  // a workgroup's partial row: both components
 
 struct ProbeState {
-  int n = 0;       // transform length of plan and tw (0: none)
-  Plan plan;
+  SegFft fft;
   int win_n = 0, win_kind = -1;  // what `win` holds
   double sumw2 = 0.0;
-  GcBuf tw, win, rows_a, rows_b, acc, hist_part, hist_max, hist_out;
+  GcBuf win, acc, hist_part, hist_max, hist_out;
 };
 
 // One thread per (span of the tile, storage position): |X|^2 of the span's segments in this tile, in segment order, added in float64 to
 // what the span's earlier tiles left (probe_span_range: carried when the span began before this tile), written to the natural bin
-// k1 + n1 * k2 of storage position k1 * n2 + k2.
+// of the storage position (fft_plan.h).
 __global__ __launch_bounds__(kProbeThreads) void probe_power_kernel(const float2* __restrict__ rows, long long g0, long long nseg, long long K,
                                                                      long long span0, int nfft, int n1, int n2, int blocks_per_row,
                                                                      double* __restrict__ acc) {
-  const long long j = blockIdx.x / (unsigned)blocks_per_row;
-  const int pos = (int)(blockIdx.x - (unsigned)(j * blocks_per_row)) * kProbeThreads + (int)threadIdx.x;
+  const auto [j, pos] = row_element<kProbeThreads>(blocks_per_row);
   if (pos >= nfft) return;
   const long long span = span0 + j;
   long long k0, k1;
   probe_span_range(g0, nseg, K, span, &k0, &k1);
   if (k0 >= k1) return;
-  const int a = pos / n2, b = pos - a * n2;
-  double* const dst = acc + span * nfft + (a + n1 * b);
+  double* const dst = acc + span * nfft + fft_bin_at(pos, n1, n2);
   double sum = k0 > 0 ? *dst : 0.0;
   const float2* __restrict__ src = rows + (span * K + k0 - g0) * nfft + pos;
   for (long long k = k0; k < k1; ++k, src += nfft) {
@@ -121,33 +117,23 @@ __global__ __launch_bounds__(kProbeThreads) void probe_hist_combine_kernel(const
   }
 }
 
-// the plan and twiddle table of an n-point transform, the window of `kind`
-int probe_prepare(gc_context* ctx, ProbeState* s, const Plan& pl, int kind) {
-  const int n = pl.n;
-  if (s->n != n) {
-    s->n = 0;
-    if (gc_buf_reserve(s->tw, (size_t)n * sizeof(float2), false) != hipSuccess) return gc_nomem("gc_probe_psd");
-    const int rc = upload_twiddles(ctx, n, (float2*)s->tw.p);
-    if (rc) return rc;
-    s->plan = pl;
-    s->n = n;
+// the n-point window of `kind`
+int probe_window(gc_context* ctx, ProbeState* s, int n, int kind) {
+  if (s->win_n == n && s->win_kind == kind) return GC_OK;
+  s->win_n = 0;
+  if (gc_buf_reserve(s->win, (size_t)n * sizeof(float), false) != hipSuccess) return gc_nomem("gc_probe_psd");
+  std::vector<float> w((size_t)n);
+  double sum2 = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double v = kind == GC_WIN_HAMMING ? 0.54 - 0.46 * std::cos(2.0 * 3.14159265358979323846 * (double)k / (double)(n - 1)) : 1.0;
+    sum2 += v * v;
+    w[(size_t)k] = (float)v;
   }
-  if (s->win_n != n || s->win_kind != kind) {
-    s->win_n = 0;
-    if (gc_buf_reserve(s->win, (size_t)n * sizeof(float), false) != hipSuccess) return gc_nomem("gc_probe_psd");
-    std::vector<float> w((size_t)n);
-    double sum2 = 0.0;
-    for (int k = 0; k < n; ++k) {
-      const double v = kind == GC_WIN_HAMMING ? 0.54 - 0.46 * std::cos(2.0 * 3.14159265358979323846 * (double)k / (double)(n - 1)) : 1.0;
-      sum2 += v * v;
-      w[(size_t)k] = (float)v;
-    }
-    GC_HIP(hipMemcpyAsync(s->win.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    GC_HIP(hipStreamSynchronize(ctx->stream));
-    s->sumw2 = sum2;
-    s->win_n = n;
-    s->win_kind = kind;
-  }
+  GC_HIP(hipMemcpyAsync(s->win.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  GC_HIP(hipStreamSynchronize(ctx->stream));
+  s->sumw2 = sum2;
+  s->win_n = n;
+  s->win_kind = kind;
   return GC_OK;
 }
 
@@ -156,7 +142,8 @@ int probe_prepare(gc_context* ctx, ProbeState* s, const Plan& pl, int kind) {
 void gc_probe_free(gc_context* ctx) {
   ProbeState* s = static_cast<ProbeState*>(ctx->probe);
   if (!s) return;
-  for (GcBuf* b : {&s->tw, &s->win, &s->rows_a, &s->rows_b, &s->acc, &s->hist_part, &s->hist_max, &s->hist_out}) gc_buf_free(*b);
+  seg_fft_free(&s->fft);
+  for (GcBuf* b : {&s->win, &s->acc, &s->hist_part, &s->hist_max, &s->hist_out}) gc_buf_free(*b);
   delete s;
   ctx->probe = nullptr;
 }
@@ -177,22 +164,22 @@ extern "C" int gc_probe_psd(gc_context* ctx, const gc_probe_psd_params* p, doubl
   if (!s) return gc_nomem("gc_probe_psd");
   const int nfft = p->nfft;
   const size_t cells = (size_t)p->nspans * (size_t)nfft;
-  const size_t rows_bytes = (size_t)std::min(pl.tile, pl.total) * (size_t)nfft * sizeof(float2);
-  if (gc_buf_reserve(s->rows_a, rows_bytes, false) != hipSuccess || gc_buf_reserve(s->rows_b, rows_bytes, false) != hipSuccess ||
-      gc_buf_reserve(s->acc, cells * sizeof(double), false) != hipSuccess)
-    return gc_nomem("gc_probe_psd");
-  rc = probe_prepare(ctx, s, plan, p->window);
+  if (gc_buf_reserve(s->acc, cells * sizeof(double), false) != hipSuccess) return gc_nomem("gc_probe_psd");
+  rc = seg_fft_prepare(ctx, &s->fft, plan, std::min(pl.tile, pl.total), "gc_probe_psd");
   if (rc) return rc;
+  rc = probe_window(ctx, s, nfft, p->window);
+  if (rc) return rc;
+  float2 *const rows_a = (float2*)s->fft.rows_a.p, *const rows_b = (float2*)s->fft.rows_b.p;
   const int bpr = (nfft + kProbeThreads - 1) / kProbeThreads;
   const RowGather segs = {(long long)p->first_sample, (long long)p->nsamples, pl.step, pl.K, 0};
   for (ProbeTile t; probe_next_tile(pl, t);) {
-    rc = gather_rows(ctx, segs, t.g0, t.n, nfft, (const float*)s->win.p, (float2*)s->rows_a.p);
+    rc = gather_rows(ctx, segs, t.g0, t.n, nfft, (const float*)s->win.p, rows_a);
     if (rc) return rc;
-    rc = transform_rows(ctx, s->plan, (const float2*)s->tw.p, (float2*)s->rows_a.p, (float2*)s->rows_b.p, t.n, 0);
+    rc = transform_rows(ctx, s->fft.plan, (const float2*)s->fft.tw.p, rows_a, rows_b, t.n, 0);
     if (rc) return rc;
     const long long span0 = t.g0 / pl.K, span1 = (t.g0 + t.n - 1) / pl.K;
     hipLaunchKernelGGL(probe_power_kernel, dim3((unsigned int)((span1 - span0 + 1) * bpr)), dim3(kProbeThreads), 0, ctx->stream,
-                       (const float2*)s->rows_a.p, t.g0, t.n, pl.K, span0, nfft, plan.n1, plan.n2, bpr, (double*)s->acc.p);
+                       (const float2*)rows_a, t.g0, t.n, pl.K, span0, nfft, plan.n1, plan.n2, bpr, (double*)s->acc.p);
     GC_HIP(hipGetLastError());
   }
   std::vector<double> host(cells);

@@ -1,5 +1,6 @@
 // probe_plan.h — what the drivers of the record probe (probe.hip: gc_probe_psd, gc_probe_histogram) decide on the host, from integers:
-// the argument checks, the segment count of a span, and the cut of the (span, segment) list into tiles whose rows fit a byte budget.
+// the argument checks, the segment count of a span, and what of a span a tile of the (span, segment) list holds (the budget of a
+// tile and the walk over the list are seg_fft.h's, shared with the excision).
 // Nothing here calls HIP, allocates on the device or launches; tests/probe_plan_shim.hip runs all of it without a device.  From the
 // context the checks read d_if, fs and if_nsamples.  The one refusal that is not decided here is the transform planner's (make_plan,
 // acq_fft.hip: GC_E_UNSUPPORTED for a prime factor of 7 or more or a row longer than 2048) - the driver asks it between
@@ -12,22 +13,15 @@
 #include <cstdint>
 
 #include "record_check.h"
+#include "seg_fft.h"
 
-#if defined(__HIPCC__)
-#define GC_PROBE_HD __host__ __device__
-#else
-#define GC_PROBE_HD
-#endif
-
-// What one tile's rows may take: two buffers of float2 rows (the transform's passes go from one to the other and back), so that a
-// tile that is gathered, transformed and added up stays inside the 256 MB last-level cache.  The library always passes the default
-// and has no switch for it; the CPU tests pass budgets of a few segments.
+// The probe's names for the shared budget and walk (seg_fft.h).  The library always passes ProbeBudget() and has no switch for it.
 #ifndef GC_PROBE_TILE_MB
 #define GC_PROBE_TILE_MB 128  // build macro for A/B libraries only (docs/KNOBS.md, scripts/variants.sh probe "T64:-DGC_PROBE_TILE_MB=64")
 #endif
-struct ProbeBudget {
-  long long tile_bytes = (long long)GC_PROBE_TILE_MB << 20;
-};
+struct ProbeBudget : SegBudget { ProbeBudget() : SegBudget{(long long)GC_PROBE_TILE_MB << 20} {} };
+using ProbeTile = SegTile;
+inline long long probe_tile_segments(int nfft, const SegBudget& b) { return seg_tile_segments(nfft, b); }
 
 struct ProbePlan {
   long long step = 0;   // nfft - noverlap
@@ -35,17 +29,8 @@ struct ProbePlan {
   long long total = 0;  // nspans * K: the list the tiles cut, global segment g = span * K + k
   long long tile = 0;   // segments per tile at most
 };
-
-struct ProbeTile {
-  long long g0 = 0;  // first global segment
-  long long n = 0;   // segments (0: before the first tile)
-};
-
-// segments of an nfft-point probe per tile under `b`: two float2 rows each, at least one
-inline long long probe_tile_segments(int nfft, const ProbeBudget& b) {
-  const long long row = 2LL * (long long)nfft * (long long)sizeof(float2);
-  return std::max<long long>(1, b.tile_bytes / row);
-}
+// the tile walk: for (ProbeTile t; probe_next_tile(pl, t);) - a tile may end one span and begin the next
+inline bool probe_next_tile(const ProbePlan& pl, ProbeTile& t) { return seg_next_tile(pl.tile, pl.total, t); }
 
 // K = floor((nsamples - noverlap) / step) (pwelch; >= 1 for every nsamples >= nfft)
 inline long long probe_segments(long long nsamples, int nfft, int noverlap) { return (nsamples - noverlap) / (long long)(nfft - noverlap); }
@@ -53,7 +38,7 @@ inline long long probe_segments(long long nsamples, int nfft, int noverlap) { re
 // What of span `span` a tile [g0, g0 + n) of the segment list holds: its segments [*k0, *k1) (empty: k0 >= k1).  The span's
 // accumulator is carried (read before it is added to) when *k0 > 0, and the span is finished by this tile when *k1 == K.  The
 // power kernel and the shim both go through this function.
-GC_PROBE_HD inline void probe_span_range(long long g0, long long n, long long K, long long span, long long* k0, long long* k1) {
+GC_FFT_HD inline void probe_span_range(long long g0, long long n, long long K, long long span, long long* k0, long long* k1) {
   const long long lo = span * K, hi = lo + K;
   const long long a = g0 > lo ? g0 : lo, b = g0 + n < hi ? g0 + n : hi;
   *k0 = a - lo;
@@ -76,7 +61,7 @@ inline int probe_check_args(const gc_context* ctx, const gc_probe_psd_params* p,
 }
 
 // ... and what the context must hold for them: GC_E_STATE, GC_E_RANGE; then the plan
-inline int probe_check_state(const gc_context* ctx, const gc_probe_psd_params* p, const ProbeBudget& b, ProbePlan* pl) {
+inline int probe_check_state(const gc_context* ctx, const gc_probe_psd_params* p, const SegBudget& b, ProbePlan* pl) {
   if (!ctx->d_if) {
     gc_set_error("gc_probe_psd: no IF record loaded");
     return GC_E_STATE;
@@ -97,14 +82,6 @@ inline int probe_check_state(const gc_context* ctx, const gc_probe_psd_params* p
   pl->total = pl->K * (long long)p->nspans;
   pl->tile = probe_tile_segments(p->nfft, b);
   return GC_OK;
-}
-
-// the tile walk: for (ProbeTile t; probe_next_tile(pl, t);) - consecutive runs of at most pl.tile segments of the whole list, so a
-// tile may end one span and begin the next
-inline bool probe_next_tile(const ProbePlan& pl, ProbeTile& t) {
-  t.g0 += t.n;
-  t.n = std::min(pl.tile, pl.total - t.g0);
-  return t.n > 0;
 }
 
 // gc_probe_histogram's checks: GC_E_INVALID, GC_E_STATE, GC_E_RANGE

@@ -5,7 +5,15 @@ own length list (tests/acq_fft_lengths.py).
 Stage positions: factor() lists a pass's radices in non-increasing order and takes the FEWEST stages, so a radix-2 stage is always
 the last one - a second 2 (or anything smaller) behind it would have been merged into a 4.  Radix 2 therefore has no inner position
 in any plan; test_radix_2_is_never_an_inner_stage proves that over every pass length, and the coverage test asks for every other
-(radix, position) pair in both passes."""
+(radix, position) pair in both passes.
+
+Storage order: csrc/fft_plan.h states once which natural bin a storage position of a transform holds (every kernel that reads a
+transform, and gc_debug_fft, go through it); tests/fft_order_shim.hip runs the two functions on the CPU."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
 import pytest
 
 import acq_fft_lengths as FL
@@ -89,3 +97,37 @@ def test_lengths_the_planner_refuses(n):
             while m % q == 0:
                 m //= q
         assert m == 1
+
+
+def _order_shim():
+    from cu_sdr_collection_amd import build as B
+    here = os.path.dirname(os.path.abspath(__file__))
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    src, out = os.path.join(here, "fft_order_shim.hip"), os.path.join(here, "build", "libfft_order_shim.so")
+    deps = [src] + [os.path.join(B.CSRC, h) for h in B.HEADERS]
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        flags = [f for f in B._tu_flags("probe.hip") if f != "--offload-compress"]
+        subprocess.run([hipcc, *flags, "-shared", src, "-o", out], check=True)
+    lib = C.CDLL(out)
+    lib.order_shim_bin_at.argtypes = lib.order_shim_pos_of.argtypes = [C.c_int, C.c_int, C.c_int]
+    return lib
+
+
+def test_storage_order_is_a_bijection_with_its_inverse_and_the_stated_layout():
+    """Position k1 n2 + k2 holds bin k1 + n1 k2.  6, 12, 60, 72, 1000 and 32768 split into n1 != n2: a swapped pair fails there
+    (and passes at the squares 4, 100 and 4096)."""
+    lib = _order_shim()
+    for n in (4, 6, 12, 60, 72, 100, 1000, 4096, 32768):
+        p = _plan(n)
+        n1, n2 = p["n1"], p["n2"]
+        assert n1 * n2 == n
+        if n in (6, 12, 60, 72, 1000, 32768):
+            assert n1 != n2, (n, n1, n2)
+        pos = [lib.order_shim_pos_of(b, n1, n2) for b in range(n)]
+        assert sorted(pos) == list(range(n)), n                                            # bin -> storage: a bijection of [0, n)
+        assert all(lib.order_shim_bin_at(pos[b], n1, n2) == b for b in range(n)), n        # storage -> bin: its inverse
+        assert all(lib.order_shim_bin_at(k1 * n2 + k2, n1, n2) == k1 + n1 * k2 and pos[k1 + n1 * k2] == k1 * n2 + k2
+                   for k1 in range(n1) for k2 in range(n2)), n
