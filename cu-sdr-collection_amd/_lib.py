@@ -25,6 +25,7 @@ GC_CANCEL_SUBTRACT, GC_CANCEL_MODEL = 0, 1   # gc_cancel_mode
 GC_EXCISE_MAX_GUARD = 4096   # gc_excise_pulses: longest guard in front of and behind a hot sample
 GC_EXCISE_MAX_WIDEN = 64     # gc_excise_sweep: most bins cut on either side of a hot one
 GC_DDC_MAX_TAPS, GC_DDC_MAX_DECIM = 2048, 64   # gc_downconvert: longest filter, largest decimation
+GC_RS_MAX_INTERP, GC_RS_MAX_TAPS = 64, 2048    # gc_resample: largest L, longest prototype (decim goes up to GC_DDC_MAX_DECIM * L)
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -175,6 +176,18 @@ class gc_ddc_result(C.Structure):
     _fields_ = [("phase_step", C.c_uint64), ("phase0", C.c_uint64), ("clipped", C.c_int64), ("sum_sq", C.c_uint64), ("carr_freq", C.c_double)]
 
 
+class gc_rs_params(C.Structure):
+    """gc_resample: output m sits at tick first_tick + m * decim (a tick is 1 / interp input sample) and is written to sample dst_first + m of dst."""
+    _fields_ = [("first_tick", C.c_int64), ("noutputs", C.c_int64), ("dst_first", C.c_int64), ("interp", C.c_int32), ("decim", C.c_int32),
+                ("ntaps", C.c_int32), ("reserved", C.c_int32), ("carr_freq", C.c_double), ("carr_phase", C.c_double)]
+
+
+class gc_rs_result(C.Structure):
+    """gc_resample: gc_ddc_result's fields (phase_step per tick) and the rate of the record written."""
+    _fields_ = [("phase_step", C.c_uint64), ("phase0", C.c_uint64), ("clipped", C.c_int64), ("sum_sq", C.c_uint64), ("carr_freq", C.c_double),
+                ("out_rate", C.c_double)]
+
+
 class gc_acq_result(C.Structure):
     _fields_ = [("coarse_bin", C.c_int32), ("code_phase", C.c_int32), ("peak", C.c_double),
                 ("peak_metric", C.c_double), ("coarse_freq", C.c_double)]
@@ -282,6 +295,8 @@ SYMBOLS = {
                                   C.POINTER(gc_excise_sweep_out), C.POINTER(gc_excise_sweep_stats)]),
     "gc_downconvert": (C.c_int, [_P, _P, C.POINTER(gc_ddc_params), C.POINTER(C.c_double), C.POINTER(gc_ddc_result)]),
     "gc_debug_ddc_tile_outputs": (C.c_longlong, [C.c_int, C.c_int]),
+    "gc_resample": (C.c_int, [_P, _P, C.POINTER(gc_rs_params), C.POINTER(C.c_double), C.POINTER(gc_rs_result)]),
+    "gc_debug_rs_tile_outputs": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
 }
 
 _lib = None

@@ -19,6 +19,7 @@
 // An output depends on its T samples and on n_m only; the tile decides nothing but who computes it.
 // The unit's buffers are its own (DdcState, kept in gc_context::ddc, grow-only, released by gc_destroy).
 #include "ddc_plan.h"
+#include "fir_common.h"
 #include "record_fmt.h"
 
 using namespace gcorr;
@@ -42,35 +43,6 @@ struct DdcArgs {
   int decim, ntaps, tile;
   int dst_mode;                // gcorr::Mode of dst
 };
-
-// sample at byte offset `off` of the staged span as (re, im): record_sample (record_fmt.h) at a byte pointer.  Not folded into it: an
-// int16 pair is one 32-bit LDS read here and two 16-bit global loads there, and one form for both would change the kernels of one
-template <int MODE>
-__device__ __forceinline__ void staged_sample(const uint8_t* lds, int off, double& re, double& im) {
-  using F = Fmt<MODE>;
-  int v0, v1 = 0;
-  if constexpr (F::values == 2 && F::value_bytes == 1) {
-    const unsigned int w = *(const unsigned short*)(lds + off);
-    v0 = (int)(signed char)(w & 0xffu);
-    v1 = (int)(signed char)(w >> 8);
-  } else if constexpr (F::values == 2) {
-    const unsigned int w = *(const unsigned int*)(lds + off);
-    v0 = (int)(short)(w & 0xffffu);
-    v1 = (int)(short)(w >> 16);
-  } else if constexpr (F::value_bytes == 1) {
-    v0 = (int)*(const signed char*)(lds + off);
-  } else {
-    v0 = (int)*(const short*)(lds + off);
-  }
-  re = (double)(F::swap ? v1 : v0);
-  im = (double)(F::swap ? v0 : v1);
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
 
 template <int MODE>
 __global__ __launch_bounds__(kDdcWG) void ddc_kernel(const DdcArgs p) {

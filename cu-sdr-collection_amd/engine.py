@@ -500,6 +500,43 @@ class Engine:
         """gc_debug_ddc_tile_outputs (test hook, host code only): outputs a workgroup of downconvert() takes; 0 for a refused (decim, ntaps)."""
         return int(L.load().gc_debug_ddc_tile_outputs(int(decim), int(ntaps)))
 
+    def resample(self, dst: "Engine", taps, interp: int, decim: int, carr_freq: float = 0.0, carr_phase: float = 0.0, first_tick: int = 0,
+                 noutputs: int | None = None, dst_first: int = 0):
+        """gc_resample: this engine's record at interp / decim times its rate.  `taps` ([T] complex or [T][2] real) is the prototype
+        at the rate fs * interp; output m sits at tick first_tick + m * decim (a tick is 1 / interp input sample), is rotated by an NCO
+        of carr_freq Hz (phase carr_phase at tick 0) and rounded into sample dst_first + m of `dst`'s record (another engine on the
+        same device; any sample count, dtype and layout).  noutputs=None: every output that still has a record sample under it, up to
+        dst's capacity.  With interp == 1 it is downconvert().
+        Returns SimpleNamespace(phase_step, phase0, clipped, sum_sq, carr_freq, out_rate, noutputs) (include/gnsscorr.h)."""
+        try:
+            g = self._ddc_taps(taps)
+            li =self._ddc_whole("interp", interp, 32)
+            d = self._ddc_whole("decim", decim, 32)
+            first = self._ddc_whole("first_tick", first_tick, 64)
+            dfirst = self._ddc_whole("dst_first", dst_first, 64)
+            nout = None if noutputs is None else self._ddc_whole("noutputs", noutputs, 64)
+        except ValueError as e:
+            raise ValueError(str(e).replace("downconvert()", "resample()")) from None
+        if not 1 <= li <= L.GC_RS_MAX_INTERP:
+            raise ValueError(f"resample(): interp must lie in 1 .. {L.GC_RS_MAX_INTERP}, not {li}")
+        if not 1 <= d <= L.GC_DDC_MAX_DECIM * li:
+            raise ValueError(f"resample(): decim must lie in 1 .. {L.GC_DDC_MAX_DECIM} * interp = {L.GC_DDC_MAX_DECIM * li}, not {d}")
+        if nout is None:
+            _, have = self.if_buffer()
+            _, room = dst.if_buffer()
+            branches = -(-g.shape[0] // li)
+            nout = min(((int(have) + branches - 1) * li - 1 - first) // d + 1, int(room) - dfirst)
+        p = L.gc_rs_params(first, nout, dfirst, li, d, g.shape[0], 0, float(carr_freq), float(carr_phase))
+        r = L.gc_rs_result()
+        L.check(self._lib.gc_resample(self._ctx, dst._ctx, C.byref(p), g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)))
+        return SimpleNamespace(phase_step=int(r.phase_step), phase0=int(r.phase0), clipped=int(r.clipped), sum_sq=int(r.sum_sq),
+                               carr_freq=float(r.carr_freq), out_rate=float(r.out_rate), noutputs=nout)
+
+    @staticmethod
+    def debug_rs_tile_outputs(interp: int, decim: int, ntaps: int) -> int:
+        """gc_debug_rs_tile_outputs (test hook, host code only): outputs a workgroup of resample() takes; 0 for a refused (interp, decim, ntaps)."""
+        return int(L.load().gc_debug_rs_tile_outputs(int(interp), int(decim), int(ntaps)))
+
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition
         (corr_multi.hip), 5 hybrid for channels with a derived six-fold arm (corr_cboc.hip), 6 float64 (corr_f64.hip), -1 mixed

@@ -660,6 +660,98 @@ def downconvert_band(engine: Engine, dst: Engine, center_freq: float, bandwidth:
                                 delay=(T - 1) / 2.0 - first, decim=d)
 
 
+def resample_ratio(fs: float, fs_out: float) -> tuple[int, int]:
+    """(L, M) of resample_record(fs_out=): fs_out / fs as the fraction L / M in lowest terms with M <= GC_DDC_MAX_DECIM *
+    GC_RS_MAX_INTERP.  ValueError where no such fraction gives fs_out to 1e-9 of it, or where gc_resample refuses it (L > 64, M > 64 L)."""
+    from fractions import Fraction
+    if not (fs > 0.0 and fs_out > 0.0):
+        raise ValueError(f"resample_record(): the rates must be positive, not {fs!r} -> {fs_out!r}")
+    r = Fraction(float(fs_out) / float(fs)).limit_denominator(L.GC_DDC_MAX_DECIM * L.GC_RS_MAX_INTERP)
+    li, m = r.numerator, r.denominator
+    if li < 1 or abs(float(fs) * li / m - float(fs_out)) > 1e-9 * float(fs_out):
+        raise ValueError(f"resample_record(): {fs_out!r} / {fs!r} is no fraction L / M with M <= {L.GC_DDC_MAX_DECIM * L.GC_RS_MAX_INTERP} (the nearest is {li} / {m})")
+    _resample_ratio_check(li, m)
+    return li, m
+
+
+def _resample_ratio_check(li: int, m: int):
+    if not 1 <= li <= L.GC_RS_MAX_INTERP:
+        raise ValueError(f"resample_record(): the rate change {li} / {m} needs L = {li}; gc_resample takes L in 1 .. {L.GC_RS_MAX_INTERP}")
+    if not 1 <= m <= L.GC_DDC_MAX_DECIM * li:
+        raise ValueError(f"resample_record(): the rate change {li} / {m} lowers the rate by more than {L.GC_DDC_MAX_DECIM} (M in 1 .. {L.GC_DDC_MAX_DECIM} L)")
+
+
+def resample_taps(fs: float, interp: int, decim: int, center_freq: float = 0.0, bandwidth: float | None = None, ntaps: int | None = None,
+                  window="hamming"):
+    """(g, f_used, h) of resample_record(): the prototype at the rate fs * L.  h = L * scipy.signal.firwin(T, cut, fs=fs * L) - a
+    low-pass of gain L at DC, which the L - 1 zeros between the samples bring back to 1 - with cut = bandwidth / 2, or
+    0.4 * fs * min(1, L / M): inside the narrower of the two Nyquist bands.  T = ntaps, or the odd number 16 max(L, M) + 1, at most
+    GC_RS_MAX_TAPS - 1.  g[k] = h[k] exp(+j 2 pi f_used k / (fs L)) is the filter around f_used, the frequency gc_resample's NCO runs
+    at for center_freq."""
+    from scipy.signal import firwin
+    li, m = int(interp), int(decim)
+    rate = float(fs) * float(li)
+    T = min(16 * max(li, m) + 1, L.GC_RS_MAX_TAPS - 1) if ntaps is None else int(ntaps)
+    cut = float(bandwidth) / 2.0 if bandwidth is not None else 0.4 * float(fs) * min(1.0, li / m)
+    h = float(li) * np.asarray(firwin(T, cut, window=window, fs=rate), dtype=np.float64) if T > 1 else np.full(1, float(li))
+    f_used = ddc_nco_freq(ddc_nco_step(center_freq, rate), rate)
+    return ddc_modulate(h, f_used, rate), f_used, h
+
+
+def resample_record(engine: Engine, dst: Engine, fs_out: float | None = None, ratio=None, center_freq: float = 0.0,
+                    bandwidth: float | None = None, ntaps: int | None = None, target_rms: float | None = None, h=None, window="hamming"):
+    """`engine`'s record at another rate in `dst` (another engine on the same device with a record from alloc_if; any dtype and
+    layout): one gc_resample at the rate change L / M with a windowed-sinc low-pass (resample_taps) moved to center_freq, the NCO
+    taking center_freq to DC.  engine's sampling frequency must be set.
+      fs_out      the rate wanted: L / M = fs_out / fs in lowest terms (resample_ratio); or
+      ratio       (L, M) as given.  Exactly one of the two.
+      bandwidth, ntaps   of the low-pass: see resample_taps.
+      h           a real prototype of the caller's at the rate fs * L, gain L at DC (bandwidth, ntaps and window are then ignored).
+      target_rms  None: gain 1.  Else the rms a stored component should have, in two passes as downconvert_band() does.
+    first_tick = (T - 1) // 2, so that output m lines up with tick m * M, input sample m * M / L.
+    Returns (result of Engine.resample, SimpleNamespace(samplingFreq = fs * L / M, IF = center_freq - f_used, f_used, gain, interp,
+    decim, delay: the filter's residual delay in TICKS, 0 for odd T)) - a code phase found on dst maps back as sample * M / L.  dst's
+    sampling frequency is set."""
+    fs = getattr(engine, "sampling_freq", None)
+    if fs is None:
+        raise ValueError("resample_record(): set the engine's sampling frequency first")
+    if (fs_out is None) == (ratio is None):
+        raise ValueError("resample_record(): give fs_out or ratio=(L, M), one of the two")
+    if ratio is not None:
+        try:
+            li, m = ratio
+            if li != int(li) or m != int(m) or isinstance(li, bool) or isinstance(m, bool):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"resample_record(): ratio must be two whole numbers (L, M), not {ratio!r}") from None
+        li, m = int(li), int(m)
+        _resample_ratio_check(li, m)
+    else:
+        li, m = resample_ratio(fs, fs_out)
+    rate = float(fs) * float(li)
+    if h is None:
+        g, f_used, _ = resample_taps(fs, li, m, center_freq, bandwidth, ntaps, window)
+    else:
+        f_used = ddc_nco_freq(ddc_nco_step(center_freq, rate), rate)
+        g = ddc_modulate(h, f_used, rate)
+    T = g.shape[0]
+    first = (T - 1) // 2
+    gain = 1.0
+    comps = 1 if dst.if_format()[1] == L.GC_REAL else 2
+    if target_rms is not None:
+        branches = -(-T // li)
+        full = min(((int(engine.if_buffer()[1]) + branches - 1) * li - 1 - first) // m + 1, int(dst.if_buffer()[1]))
+        trial = engine.resample(dst, g, li, m, carr_freq=center_freq, first_tick=first, noutputs=min(full, 65536))
+        rms = math.sqrt(trial.sum_sq / (comps * trial.noutputs))
+        if not rms > 0.0:
+            raise ValueError("resample_record(): the band holds nothing to scale (every stored component of the trial is zero)")
+        gain = float(target_rms) / rms
+    res = engine.resample(dst, gain * g, li, m, carr_freq=center_freq, first_tick=first)
+    dst.set_sampling_freq(res.out_rate)
+    return res, SimpleNamespace(samplingFreq=res.out_rate, IF=float(center_freq) - f_used, f_used=f_used, gain=gain, interp=li, decim=m,
+                                delay=(T - 1) / 2.0 - first)
+
+
 def cancel_tracked(fid: Engine, trackResults, channel, settings, which=None, signal: str = "GPS_L1CA", epochs=None, dst: Engine | None = None,
                    mode: str = "subtract", amp=None):
     """What lies under the signals a tracking run followed: every chosen channel's tracked component rebuilt from the state tracking.m

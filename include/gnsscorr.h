@@ -997,6 +997,64 @@ int gc_downconvert(gc_context* src, gc_context* dst, const gc_ddc_params* p,
 /* Test hook (host code only, no context): outputs a workgroup of the kernel takes (a tile); 0 for a decim or ntaps out of range. */
 long long gc_debug_ddc_tile_outputs(int decim, int ntaps);
 
+/* ---- a record at a rational multiple of its rate: the polyphase resampler -------------------------------------------------------------
+ * gc_resample is gc_downconvert at the rate change L / M (csrc/resample.hip): the record is taken as if L - 1 zeros stood between its
+ * samples, filtered with a complex FIR given at the rate fs * L (the prototype), every M-th of those outputs is kept, rotated by the NCO
+ * and requantised into a SECOND record at the rate fs * L / M: 18 Msps become 4 or 8 Msps, 50 Msps become 20, the records of two front
+ * ends meet at one rate.  Only the taps that meet a record sample are multiplied.  src, dst, the stream, the buffers (its own, released
+ * by gc_destroy) and the detection by symbol are gc_downconvert's.
+ *
+ * Definition, in float64, every operation rounded by itself (no fused multiply-add).  fs = src's gc_set_sampling_freq, L = interp,
+ * M = decim, T = ntaps, g[k] = (gr[k], gi[k]) = taps[k]; a TICK is 1 / L of an input sample.
+ *   input     x[n] as in gc_downconvert: zero for n < 0 and for n >= the record's sample count
+ *   position  u_m = first_tick + m * M for output m, 0 <= m < noutputs;  n_m = u_m div L,  p_m = u_m mod L
+ *   filter    a_r = a_i = +0.0; for j = 0, 1, .. in ascending order while k = j * L + p_m < T, with x = x[n_m - j] and g = g[k]:
+ *               pr = gr*xr - gi*xi,  pi = gr*xi + gi*xr,  a_r = a_r + pr,  a_i = a_i + pi
+ *             The kernel pads the prototype with zero taps up to J * L, J = ceil(T / L), and runs j = 0 .. J-1 for every output: a
+ *             zero tap adds +-0 to a sum that started at +0.0, which changes no stored integer and no statistic.
+ *   NCO       exact integers modulo 2^64, addressed by the absolute TICK:
+ *               phase_step = (uint64)(int64) llrint(ldexp(carr_freq / (fs * (double)L), 64))
+ *               phase0 as in gc_downconvert (the NCO's phase at tick 0)
+ *               ph_m = phase0 + phase_step * (uint64) u_m
+ *   ang, (sn, cs), rotation, store, result: gc_downconvert's, operation for operation.
+ *   res->carr_freq = ldexp((double)(int64) phase_step, -64) * (fs * (double)L);  res->out_rate = (fs * (double)L) / (double)M.
+ * Guarantees: gc_downconvert's.  dst's bytes outside [dst_first, dst_first + noutputs) are untouched; the same input gives the same
+ * bytes and statistics; an output depends on its own samples and on u_m only - not on the tile (gc_debug_rs_tile_outputs), not on the
+ * call: two calls on [u_0, u_0 + a M) and from u_0 + a M on, with dst_first moved by a, write the bytes of the single call.  With
+ * interp == 1 every byte and every field of the result is gc_downconvert's with first_sample = first_tick and decim = M (out_rate is
+ * the one field more).
+ *
+ * Refusals (a refused call writes nothing): gc_downconvert's, status for status and in its order, with these among the argument
+ * checks: GC_E_INVALID for interp outside [1, GC_RS_MAX_INTERP], decim outside [1, GC_DDC_MAX_DECIM * interp], ntaps outside
+ * [1, GC_RS_MAX_TAPS] and reserved != 0; |carr_freq| is held against fs / 2; after dst's range, GC_E_INVALID for a last tick
+ * first_tick + (noutputs - 1) * M that does not fit in 63 bits; then GC_E_RANGE when the last output has no record sample under it
+ * (n_last - (J-1) >= src's sample count). */
+#define GC_RS_MAX_INTERP 64
+#define GC_RS_MAX_TAPS   2048
+typedef struct gc_rs_params {
+  int64_t first_tick;    /* u_0 >= 0: position of output 0 in ticks of 1 / L input sample */
+  int64_t noutputs;      /* >= 1 */
+  int64_t dst_first;     /* output m is written to sample dst_first + m of dst's record, >= 0 */
+  int32_t interp;        /* L, 1 .. GC_RS_MAX_INTERP */
+  int32_t decim;         /* M, 1 .. GC_DDC_MAX_DECIM * L: the rate falls to no less than 1 / 64 */
+  int32_t ntaps;         /* T, 1 .. GC_RS_MAX_TAPS: the prototype at the rate fs * L */
+  int32_t reserved;      /* 0 */
+  double  carr_freq;     /* Hz, |carr_freq| < fs / 2 */
+  double  carr_phase;    /* radians, the NCO's phase at tick 0 */
+} gc_rs_params;          /* 56 bytes */
+typedef struct gc_rs_result {
+  uint64_t phase_step;   /* NCO increment per TICK, turns * 2^64 */
+  uint64_t phase0;       /* NCO phase at tick 0, turns * 2^64 */
+  int64_t  clipped;      /* stored components whose rint(y) lay outside dst's integer range */
+  uint64_t sum_sq;       /* exact sum of the squares of the stored components */
+  double   carr_freq;    /* the frequency the NCO runs at */
+  double   out_rate;     /* (fs * L) / M, each operation rounded by itself: dst's sampling frequency */
+} gc_rs_result;          /* 48 bytes */
+int gc_resample(gc_context* src, gc_context* dst, const gc_rs_params* p,
+                const double* taps /* [ntaps][2] = {re, im} */, gc_rs_result* res /* may be NULL */);
+/* Test hook (host code only, no context): outputs a workgroup of the kernel takes (a tile); 0 for an interp, decim or ntaps out of range. */
+long long gc_debug_rs_tile_outputs(int interp, int decim, int ntaps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,11 @@
  *          % hSrc's record through the complex FIR taps (2 x T doubles: re; im), every decim-th output rotated by an NCO of carrFreq Hz
  *          and rounded into hDst's record from sample dstFirst0 (gc_downconvert); nOutputs absent or [] = every output with a record
  *          sample under it, up to hDst's capacity; r = [clipped sumSq carrFreqUsed nOutputs], nco = uint64 [phaseStep phase0]
+ *   [r, nco] = gnsscorr_mex('resample', hSrc, hDst, taps, interp, decim[, carrFreq[, carrPhase[, firstTick0[, nOutputs[, dstFirst0]]]]])
+ *          % hSrc's record at interp / decim times its rate (gc_resample): taps (2 x T doubles: re; im) is the prototype at the rate
+ *          fs * interp, output m sits at tick firstTick0 + m * decim (a tick is 1 / interp input sample), is rotated by an NCO of
+ *          carrFreq Hz and rounded into hDst's record from sample dstFirst0; nOutputs absent or [] = every output with a record sample
+ *          under it, up to hDst's capacity; r = [clipped sumSq carrFreqUsed nOutputs outRate], nco = uint64 [phaseStep phase0]
  *   n    = gnsscorr_mex('device_count')                                              % HIP devices visible: one context per device
  *   prev = gnsscorr_mex('set_precision', h, 'double'|'single')                    % float64 correlations for every later correlate /
  *          track call of this context (gc_set_precision), 'single' = the float32 kernels (default); returns the previous setting
@@ -875,6 +880,50 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     plhs[0] = mxCreateDoubleMatrix(1, 4, mxREAL);
     double* o = mxGetDoubles(plhs[0]);
     o[0] = (double)res.clipped, o[1] = (double)res.sum_sq, o[2] = res.carr_freq, o[3] = (double)p.noutputs;
+    if (nlhs > 1) {
+      plhs[1] = mxCreateNumericMatrix(1, 2, mxUINT64_CLASS, mxREAL);
+      uint64_t* u = (uint64_t*)mxGetData(plhs[1]);
+      u[0] = res.phase_step, u[1] = res.phase0;
+    }
+  } else if (!strcmp(cmd, "resample")) {
+    /* [r, nco] = gnsscorr_mex('resample', hSrc, hDst, taps, interp, decim[, carrFreq[, carrPhase[, firstTick0[, nOutputs[, dstFirst0]]]]]) */
+    if (nrhs < 6) mexErrMsgIdAndTxt("gnsscorr:usage", "resample: hSrc, hDst, taps 2 x T, interp, decim[, carrFreq[, carrPhase[, firstTick0[, nOutputs[, dstFirst0]]]]]");
+    const size_t nel = mxGetNumberOfElements(prhs[3]);
+    if (!mxIsDouble(prhs[3]) || mxGetM(prhs[3]) != 2 || nel < 2 || nel > 2u * GC_RS_MAX_TAPS)
+      mexErrMsgIdAndTxt("gnsscorr:usage", "resample: taps must be 2 x T real doubles (re; im), 1 <= T <= %d", GC_RS_MAX_TAPS);
+    double whole[5] = {mxGetScalar(prhs[4]), mxGetScalar(prhs[5]), 0.0, -1.0, 0.0}; /* interp, decim, firstTick0, nOutputs (-1: all), dstFirst0 */
+    for (int i = 8; i < nrhs && i < 11; ++i)
+      if (mxGetNumberOfElements(prhs[i]) > 0) whole[i - 6] = mxGetScalar(prhs[i]);
+    for (int i = 0; i < 5; ++i)
+      if (!(whole[i] >= -9007199254740992.0 && whole[i] <= 9007199254740992.0) || whole[i] != (double)(int64_t)whole[i] ||
+          (i < 2 && (whole[i] < -2147483648.0 || whole[i] > 2147483647.0)))
+        mexErrMsgIdAndTxt("gnsscorr:usage", "resample: interp, decim, firstTick0, nOutputs and dstFirst0 must be whole numbers that fit their fields");
+    gc_rs_params p;
+    p.first_tick = (int64_t)whole[2];
+    p.noutputs = (int64_t)whole[3];
+    p.dst_first = (int64_t)whole[4];
+    p.interp = (int32_t)whole[0];
+    p.decim = (int32_t)whole[1];
+    p.ntaps = (int32_t)(nel / 2);
+    p.reserved = 0;
+    p.carr_freq = nrhs > 6 ? mxGetScalar(prhs[6]) : 0.0;
+    p.carr_phase = nrhs > 7 ? mxGetScalar(prhs[7]) : 0.0;
+    if (whole[3] < 0) { /* every output that has a record sample under it, up to hDst's capacity */
+      void* ptr = NULL;
+      uint64_t have = 0, room = 0;
+      if (gc_if_buffer(handle(prhs[1]), &ptr, &have) || gc_if_buffer(handle(prhs[2]), &ptr, &room)) fail("gc_if_buffer");
+      const int64_t li = p.interp > 0 ? p.interp : 1, d = p.decim > 0 ? p.decim : 1, branches = (p.ntaps + li - 1) / li;
+      const int64_t num = ((int64_t)have + branches - 1) * li - 1 - p.first_tick;
+      const int64_t fit = (num >= 0 ? num / d : -((-num + d - 1) / d)) + 1, cap = (int64_t)room - p.dst_first;
+      p.noutputs = fit < cap ? fit : cap;
+    }
+    gc_rs_result res;
+    int rc = gc_resample(handle(prhs[1]), handle(prhs[2]), &p, mxGetDoubles(prhs[3]), &res);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
+    if (rc) fail("gc_resample");
+    plhs[0] = mxCreateDoubleMatrix(1, 5, mxREAL);
+    double* o = mxGetDoubles(plhs[0]);
+    o[0] = (double)res.clipped, o[1] = (double)res.sum_sq, o[2] = res.carr_freq, o[3] = (double)p.noutputs, o[4] = res.out_rate;
     if (nlhs > 1) {
       plhs[1] = mxCreateNumericMatrix(1, 2, mxUINT64_CLASS, mxREAL);
       uint64_t* u = (uint64_t*)mxGetData(plhs[1]);
