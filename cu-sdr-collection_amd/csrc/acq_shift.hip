@@ -5,6 +5,7 @@
 #include <functional>
 
 #include "acq_internal.h"
+#include "shift_pick.h"
 
 using namespace gcacq;
 
@@ -378,46 +379,11 @@ extern "C" int gc_acq_shift_row(gc_context* ctx, int row, float* out) {
 
 // ---- the whole search of a package in one call -------------------------------------------------------------------------------
 namespace {
-// What shift_pick_kernel leaves per PRN (device-internal; the public gc_acq_shift_pick is filled from it and from the float64 guard)
-struct ShiftPickDev {
-  int row;          // in: the winning row (-1: none)
-  int code_phase;   // 0-based first maximum of the row
-  int second_col;   // 0-based first position of the second peak (-1: no second peak asked for or range empty)
-  int near_peak;    // cells of the row at or above peak * (1 - eps), the maximum itself included
-  int near_second;  // cells of the second-peak range at or above second * (1 - eps)
-  float peak, second;
-  int pad_;
-};
-
-// Where the second peak is looked for: the row's first `period` samples outside +-exclude samples of the first maximum `cp` - the
-// reference's three range cases (B1I :141-156, L2C :77-91; 1-based there as here: e1 = codePhase - exclude, e2 = codePhase + exclude;
-// e1 < 2: e2 .. period + e1; e2 >= period: e2 - period + 1 .. e1; else 1 .. e1 and e2 .. period).  period <= 0: nowhere.
-struct SecondWindow {
-  int lo0 = 1, hi0 = 0, lo1 = 1, hi1 = 0;  // 1-based inclusive ranges
-  __host__ __device__ bool holds(int c1) const { return (c1 >= lo0 && c1 <= hi0) || (c1 >= lo1 && c1 <= hi1); }
-};
-__host__ __device__ inline SecondWindow second_window(int cp, int exclude, int period) {
-  SecondWindow w;
-  if (period <= 0) return w;
-  const int e1 = cp - exclude, e2 = cp + exclude;
-  if (e1 < 2) {
-    w.lo0 = e2;
-    w.hi0 = period + e1;
-  } else if (e2 >= period) {
-    w.lo0 = e2 - period + 1;
-    w.hi0 = e1;
-  } else {
-    w.lo0 = 1;
-    w.hi0 = e1;
-    w.lo1 = e2;
-    w.hi1 = period;
-  }
-  return w;
-}
-
 // One workgroup per PRN: the first maximum of the winning row (BDS/B1I acquisition.m:126, GPS_L2C :72) and the largest value of the
 // row inside second_window() of it.  period <= 0: no second peak (GC_SHIFT_PICK_GLOBAL).  For the float64 guard: how many cells lie
-// within eps (relative) of either value - more than one means the float32 ordering decided something it cannot.
+// within eps (relative) of either value - more than one means the float32 ordering decided something it cannot.  A pick that comes with
+// forced_cp > 0 has its first maximum there (1-based): the float64 guard moved it, and the window with it (resolve_peaks, shift_pick.h,
+// which also states serially what this kernel leaves: shift_pick_serial).
 __global__ __launch_bounds__(1024) void shift_pick_kernel(const float* __restrict__ rows, long long row_stride, int n, int exclude, int period, float eps,
                                                          ShiftPickDev* __restrict__ picks) {
   __shared__ float sv[1024];
@@ -448,8 +414,9 @@ __global__ __launch_bounds__(1024) void shift_pick_kernel(const float* __restric
     }
     __syncthreads();
   }
-  const float peak = sv[0];
-  const int cp = si[0] + 1;  // 1-based, as the reference's ranges
+  const int forced = pk.forced_cp;  // (never written here)
+  const float peak = forced > 0 ? r[forced - 1] : sv[0];
+  const int cp = forced > 0 ? forced : si[0] + 1;  // 1-based, as the reference's ranges
   __syncthreads();
   const SecondWindow w = second_window(cp, exclude, period);
   const int lo0 = w.lo0, hi0 = w.hi0, lo1 = w.lo1, hi1 = w.hi1;
@@ -527,54 +494,16 @@ __global__ __launch_bounds__(256) void shift_expand_codes_kernel(const int8_t* _
   for (int k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) o[k] = k < n_index ? c[index[k]] : (int8_t)0;
 }
 
-// The reference's sequential selection over the (carrier, bin) grid (BDS/B1I acquisition.m:87-122, GPS_L2C :46-66): a value is taken
-// only if it EXCEEDS the largest so far, starting from 0, and the last bin of every carrier but the first is not looked at - the
-// first position, in scan order, of the largest value, if that is above 0.  v(carrier, bin) = rowmax, or the larger of the two signal
-// blocks' (pairs).  Returns the public row index, or -1.
-template <class T>
-int pick_sequential(const gc_acq_shift_params& p, const T* rmax, bool pairs) {
-  T best = 0;
-  int row = -1;
-  for (int c = 0; c < p.n_carriers; ++c)
-    for (int b = 0; b < p.n_bins; ++b) {
-      if (c > 0 && b == p.n_bins - 1) continue;
-      if (!pairs) {
-        const int r = c * p.n_bins + b;
-        if (rmax[r] > best) {
-          best = rmax[r];
-          row = r;
-        }
-      } else {
-        const int r1 = (c * 2 + 0) * p.n_bins + b, r2 = (c * 2 + 1) * p.n_bins + b;
-        const T v = std::max(rmax[r1], rmax[r2]);
-        if (v > best) {
-          best = v;
-          row = rmax[r1] > rmax[r2] ? r1 : r2;
-        }
-      }
-    }
-  return row;
-}
-
 // ---- the float64 guard of the batch call (acq_guard.h) ---------------------------------------------------------------------------
 // Row maxima, first maxima and second peaks come out of float32 transforms; the reference's sequential `>` tests (B1I :98-119,
 // L2C :46-66), `[~, codePhase] = max(corr)` and `max_peak / second > threshold` (B1I :126-166) are float64.  Wherever two candidates
 // are closer than eps the cells that close are evaluated again as float64 correlations at one lag, and peak / second_peak of every
 // PRN always are (the two numbers the caller divides and thresholds).
 //
-// The decisions below (pick_row, resolve_peaks) are the same for both ways the batch call runs; what differs is where a row's float32
-// sums come from, so that comes in as `row_cells`.  They launch nothing themselves.
-struct ShiftGuard {
-  const gc_acq_shift_params& p;
-  int rule, exclude, period;
-  bool guard;  // false (GC_ACQ_NO_GUARD in the tuning build): the float32 decisions stand
-  double eps;  // gc_acq_tie_eps of the transform
+// The decisions (pick_row, pick_from_dev, resolve_peaks: shift_pick.h) are the same for both ways the batch call runs; what differs is
+// where a row's float32 sums come from, so that comes in as `row_cells` and `pick_forced`.  They launch nothing themselves.
+struct ShiftGuard : ShiftPickRules {
   GcExactSetup ex;
-  // cells {row, col} of PRN k's public row `row` at or above thr (<= kGuardListCap of them, else *overflow and none)
-  std::function<int(int k, int row, float thr, std::vector<int2>& list, bool* overflow)> row_cells;
-  // float64 values of cells {row, col} of PRN k's results
-  std::function<int(int k, const std::vector<int2>& cells, std::vector<double>& vals)> exact_values;
-  bool second() const { return rule != GC_SHIFT_PICK_GLOBAL; }
 };
 
 // the cell (public row, col) of PRN k's results
@@ -591,10 +520,18 @@ GcExactCell shift_exact_cell(const gc_acq_shift_params& p, int k, int row, int c
 }
 
 // The guard of the search in place: replicas in b_codes ([nprn * narms][p.n], the first code_samples entries of each are not zero
-// padding), every arm's weight (nullptr: 1).  row_cells is the caller's to set.
+// padding), every arm's weight (nullptr: 1).  row_cells and pick_forced are the caller's to set.
 ShiftGuard shift_guard(gc_context* ctx, AcqScratch* s, int narms, const double* arm_weight, int code_samples, int rule, int exclude, int period) {
   const gc_acq_shift_params& p = s->shift;
-  ShiftGuard g{p, rule, exclude, period, GC_TUNE_ENV("GC_ACQ_NO_GUARD") == nullptr, gc_acq_tie_eps(s->plan.n)};
+  ShiftGuard g;
+  g.n_carriers = p.n_carriers;
+  g.n_signals = p.n_signals;
+  g.n_bins = p.n_bins;
+  g.rule = rule;
+  g.exclude = exclude;
+  g.period = period;
+  g.guard = GC_TUNE_ENV("GC_ACQ_NO_GUARD") == nullptr;
+  g.eps = gc_acq_tie_eps(s->plan.n);
   const bool cond = p.source == GC_ACQ_SOURCE_CONDITIONED;
   g.ex.if_i8 = cond ? nullptr : (const int8_t*)ctx->d_if;
   g.ex.if_f32 = cond ? (const float2*)ctx->acqbuf[gc_context::ACQ_COND_SIG].p : nullptr;
@@ -629,91 +566,20 @@ int shift_collect_row(gc_context* ctx, AcqScratch* s, const float* sums, int row
   return rc;
 }
 
-// the largest of the cells' float64 values and the smallest column that holds it (MATLAB's first occurrence)
-void first_maximum(const std::vector<int2>& cells, const std::vector<double>& vals, double* best, int* col) {
-  *best = -1.0;
-  *col = 0;
-  for (size_t i = 0; i < cells.size(); ++i)
-    if (vals[i] > *best || (vals[i] == *best && cells[i].y < *col)) {
-      *best = vals[i];
-      *col = cells[i].y;
-    }
+// shift_pick_kernel on ONE row's sums with the first maximum forced to column `col` (0-based) of public row `row`, through the first
+// slot of b_pick (whatever the search's own picks left there has been read back)
+int shift_pick_forced(gc_context* ctx, AcqScratch* s, const ShiftGuard& g, const float* sums, int row, int col, ShiftPickDev& d) {
+  std::memset(&d, 0, sizeof d);
+  d.row = row;
+  d.second_col = -1;
+  d.forced_cp = col + 1;
+  GC_HIP(hipMemcpyAsync(s->b_pick.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(shift_pick_kernel, dim3(1), dim3(1024), 0, ctx->stream, sums, (long long)s->plan.n, s->shift.n, g.exclude, g.second() ? g.period : 0,
+                     (float)g.eps, (ShiftPickDev*)s->b_pick.p);
+  GC_HIP(hipGetLastError());
+  return shift_read_back(ctx, s, &d, s->b_pick.p, sizeof d);
 }
 
-// the package's selection rule on the row maxima rmd and their columns rad (public row order)
-void apply_rule(const ShiftGuard& g, const std::vector<double>& rmd, const std::vector<int>& rad, gc_acq_shift_pick& pk) {
-  if (g.rule == GC_SHIFT_PICK_GLOBAL) {
-    // BDS/B1C acquisition.m:193-197: the row of max(max(results,[],2)) (first), the first column holding the global maximum
-    const int rows = (int)rmd.size();
-    int best = 0;
-    for (int r = 1; r < rows; ++r)
-      if (rmd[(size_t)r] > rmd[(size_t)best]) best = r;
-    int col = rad[(size_t)best];
-    for (int r = 0; r < rows; ++r)
-      if (rmd[(size_t)r] == rmd[(size_t)best] && rad[(size_t)r] < col) col = rad[(size_t)r];
-    pk.row = best;
-    pk.code_phase = col;
-    pk.peak = rmd[(size_t)best];
-  } else {
-    pk.row = pick_sequential(g.p, rmd.data(), g.rule == GC_SHIFT_PICK_SEQUENTIAL_PAIRS);
-  }
-}
-
-// PRN k's row: the rule on the float32 row maxima, then rows whose maximum is within eps of the chosen one - which of them the rule
-// takes is decided on their float64 maxima (rmd / rad are overwritten with those).  More than 64 such rows: the float32 choice stands.
-int pick_row(const ShiftGuard& g, int k, std::vector<double>& rmd, std::vector<int>& rad, gc_acq_shift_pick& pk, int& ties) {
-  pk.row = -1;
-  pk.code_phase = 0;
-  pk.peak = 0.0;
-  pk.second_peak = 0.0;
-  apply_rule(g, rmd, rad, pk);
-  if (!g.guard || pk.row < 0) return GC_OK;
-  const double near = rmd[(size_t)pk.row] * (1.0 - g.eps);
-  std::vector<int> tied;
-  for (int r = 0; r < (int)rmd.size(); ++r)
-    if (rmd[(size_t)r] >= near && rmd[(size_t)r] > 0.0) tied.push_back(r);
-  if (tied.size() <= 1 || tied.size() > 64) return GC_OK;
-  ++ties;
-  for (int r : tied) {
-    std::vector<int2> list;
-    bool overflow = false;
-    int rc = g.row_cells(k, r, (float)(rmd[(size_t)r] * (1.0 - g.eps)), list, &overflow);
-    if (rc) return rc;
-    if (overflow || list.empty()) continue;  // a plateau: the float32 maximum stands for this row
-    std::vector<double> vals;
-    rc = g.exact_values(k, list, vals);
-    if (rc) return rc;
-    first_maximum(list, vals, &rmd[(size_t)r], &rad[(size_t)r]);
-  }
-  apply_rule(g, rmd, rad, pk);
-  return GC_OK;
-}
-
-// PRN k's first maximum and second peak when shift_pick_kernel (or the row's runner-up) found another cell within eps of either, `d`
-// holding the float32 values: every cell of the chosen row that could be the first maximum or the second peak - all those at or
-// above the smaller of the two float32 values less eps (the peak's lobe is among them) - then the reference's rules on the float64
-// values.  An overflowed or empty list: pk stays.  No collected cell in the window around the new first maximum: second_peak stays.
-int resolve_peaks(const ShiftGuard& g, int k, const ShiftPickDev& d, gc_acq_shift_pick& pk, int& ties) {
-  if (d.near_peak <= 1 && d.near_second <= 1) return GC_OK;
-  ++ties;
-  const float low = g.second() && d.second_col >= 0 ? std::min(d.peak, d.second) : d.peak;
-  std::vector<int2> list;
-  bool overflow = false;
-  int rc = g.row_cells(k, pk.row, (float)((double)low * (1.0 - g.eps)), list, &overflow);
-  if (rc) return rc;
-  if (overflow || list.empty()) return GC_OK;
-  std::vector<double> vals;
-  rc = g.exact_values(k, list, vals);
-  if (rc) return rc;
-  first_maximum(list, vals, &pk.peak, &pk.code_phase);
-  if (!g.second()) return GC_OK;
-  const SecondWindow w = second_window(pk.code_phase + 1, g.exclude, g.period);
-  double sec = -1.0;
-  for (size_t i = 0; i < list.size(); ++i)
-    if (w.holds(list[i].y + 1)) sec = std::max(sec, vals[i]);
-  if (sec >= 0.0) pk.second_peak = sec;
-  return GC_OK;
-}
 }  // namespace
 
 // gc_acq_shift_search_batch where the passes WRITE the rows (no per-tile candidates): PRN by PRN inside the call - rows and columns
@@ -741,6 +607,7 @@ static int shift_batch_written(gc_context* ctx, AcqScratch* s, int nprn, int nar
   g.row_cells = [&](int, int row, float thr, std::vector<int2>& list, bool* overflow) {
     return shift_collect_row(ctx, s, s->results + (size_t)irow_of(row) * N, row, thr, list, overflow);
   };
+  g.pick_forced = [&](int, int row, int col, ShiftPickDev& d) { return shift_pick_forced(ctx, s, g, s->results + (size_t)irow_of(row) * N, row, col, d); };
   std::vector<float> hm((size_t)rows), hs((size_t)rows);
   std::vector<int> ha((size_t)rows);
   std::vector<double> rmd((size_t)rows);
@@ -776,20 +643,14 @@ static int shift_batch_written(gc_context* ctx, AcqScratch* s, int nprn, int nar
     GC_HIP(hipGetLastError());
     rc = shift_read_back(ctx, s, &d, s->b_pick.p, sizeof d);
     if (rc) return rc;
-    if (g.second()) pk.code_phase = d.code_phase;
-    pk.peak = (double)d.peak;
-    pk.second_peak = g.second() ? (double)d.second : 0.0;
+    int2 two[2];
+    const int ntwo = pick_from_dev(g, d, pk, two);
     if (!g.guard) continue;
     {
-      std::vector<int2> two;
-      two.push_back(make_int2(pk.row, pk.code_phase));
-      if (g.second() && d.second_col >= 0) two.push_back(make_int2(pk.row, d.second_col));
       std::vector<double> vals;
-      rc = g.exact_values(k, two, vals);
+      rc = g.exact_values(k, std::vector<int2>(two, two + ntwo), vals);
       if (rc) return rc;
-      if (vals[0] > 0.0) s->guard_max_dev = std::max(s->guard_max_dev, std::fabs(pk.peak - vals[0]) / vals[0]);
-      pk.peak = vals[0];
-      if (two.size() > 1) pk.second_peak = vals[1];
+      pick_set_exact(vals.data(), ntwo, pk, s->guard_max_dev);
     }
     rc = resolve_peaks(g, k, d, pk, s->guard_ties);
     if (rc) return rc;
@@ -960,9 +821,12 @@ extern "C" int gc_acq_shift_search_batch(gc_context* ctx, int nprn, int narms, c
     const int rc2 = row_again(k, row);
     return rc2 ? rc2 : shift_collect_row(ctx, s, (const float*)s->b_rows.p + (size_t)k * N, row, thr, list, overflow);
   };
+  // (resolve_peaks asks right after row_cells(k, row, ...): the row is in the PRN's slot)
+  g.pick_forced = [&](int k, int row, int col, ShiftPickDev& d) { return shift_pick_forced(ctx, s, g, (const float*)s->b_rows.p + (size_t)k * N, row, col, d); };
   // the package's selection rule on the row maxima (host: nprn x rows numbers)
   std::vector<double> rmd((size_t)rows);
   std::vector<int> rad((size_t)rows);
+  std::vector<ShiftPickDev> dev((size_t)nprn);
   for (int k = 0; k < nprn; ++k) {
     for (int r = 0; r < rows; ++r) {
       rmd[(size_t)r] = (double)hmax[(size_t)k * rows + r];
@@ -970,14 +834,12 @@ extern "C" int gc_acq_shift_search_batch(gc_context* ctx, int nprn, int narms, c
     }
     rc = pick_row(g, k, rmd, rad, out[k], s->guard_ties);
     if (rc) return rc;
-  }
-  // phase 2: the winning rows again, first maximum and second peak on the device, one read-back
-  std::vector<ShiftPickDev> dev((size_t)nprn);
-  for (int k = 0; k < nprn; ++k) {
     std::memset(&dev[(size_t)k], 0, sizeof(ShiftPickDev));
     dev[(size_t)k].row = out[k].row;
     dev[(size_t)k].second_col = -1;
+    if (out[k].row >= 0) dev[(size_t)k].code_phase = rad[(size_t)out[k].row];  // (the chosen row's own first maximum)
   }
+  // phase 2: the winning rows again, first maximum and second peak on the device, one read-back
   if (!g.second() && !g.guard) return GC_OK;
   if (g.second()) {
     GC_HIP(hipMemcpyAsync(s->b_pick.p, dev.data(), (size_t)nprn * sizeof(ShiftPickDev), hipMemcpyHostToDevice, ctx->stream));
@@ -991,48 +853,35 @@ extern "C" int gc_acq_shift_search_batch(gc_context* ctx, int nprn, int narms, c
     GC_HIP(hipGetLastError());
     rc = shift_read_back(ctx, s, dev.data(), s->b_pick.p, (size_t)nprn * sizeof(ShiftPickDev));
     if (rc) return rc;
-    for (int k = 0; k < nprn; ++k) {
-      if (out[k].row < 0) continue;
-      const ShiftPickDev& d = dev[(size_t)k];
-      out[k].code_phase = d.code_phase;
-      out[k].peak = (double)d.peak;
-      out[k].second_peak = (double)d.second;
-    }
   } else {
     // GC_SHIFT_PICK_GLOBAL has no second peak and took its column from the row maxima: the winning row is not transformed again -
     // whether another of its cells lies within eps of the maximum is known from the row's runner-up (PeakTrack::m2 through the
     // per-tile slots, rowkeys_reduce_kernel)
     for (int k = 0; k < nprn; ++k) {
       if (out[k].row < 0) continue;
-      ShiftPickDev& d = dev[(size_t)k];
       const size_t at = (size_t)k * rows + (size_t)out[k].row;
-      d.code_phase = out[k].code_phase;
-      d.peak = (float)out[k].peak;
-      d.near_peak = (double)hsecond[at] >= (double)hmax[at] * (1.0 - g.eps) ? 2 : 1;
-      d.near_second = 0;
+      pick_dev_from_runner_up(g, out[k], dev[(size_t)k].code_phase, hmax[at], hsecond[at], dev[(size_t)k]);
     }
   }
-  if (!g.guard) return GC_OK;
   // every PRN's peak and second-peak cells in float64 (one launch), then the PRNs whose row holds another cell within eps of either
   {
     std::vector<GcExactCell> cells;
-    std::vector<double*> dst;
+    std::vector<int> ncells((size_t)nprn, 0);
     for (int k = 0; k < nprn; ++k) {
       if (out[k].row < 0) continue;
-      cells.push_back(shift_exact_cell(p, k, out[k].row, out[k].code_phase));
-      dst.push_back(&out[k].peak);
-      if (dev[(size_t)k].second_col >= 0) {
-        cells.push_back(shift_exact_cell(p, k, out[k].row, dev[(size_t)k].second_col));
-        dst.push_back(&out[k].second_peak);
-      }
+      int2 two[2];
+      ncells[(size_t)k] = pick_from_dev(g, dev[(size_t)k], out[k], two);
+      for (int i = 0; i < ncells[(size_t)k]; ++i) cells.push_back(shift_exact_cell(p, k, two[i].x, two[i].y));
     }
+    if (!g.guard) return GC_OK;
     if (!cells.empty()) {
       std::vector<double> vals;
       rc = guard_exact_values(ctx, s, g.ex, cells, vals);
       if (rc) return rc;
-      for (size_t i = 0; i < cells.size(); ++i) {
-        if (vals[i] > 0.0) s->guard_max_dev = std::max(s->guard_max_dev, std::fabs(*dst[i] - vals[i]) / vals[i]);
-        *dst[i] = vals[i];
+      size_t at = 0;
+      for (int k = 0; k < nprn; ++k) {
+        pick_set_exact(vals.data() + at, ncells[(size_t)k], out[k], s->guard_max_dev);
+        at += (size_t)ncells[(size_t)k];
       }
     }
   }

@@ -712,6 +712,10 @@ int gc_debug_acq_surface(gc_context* ctx, const gc_acq_params* p, int narms, con
  * 141-166 max_peak / second).  Every PRN's winning cell is evaluated again in float64 as a circular correlation at one lag, so peak
  * and peak_metric leave the library without the transforms' rounding; a PRN whose runner-up lies within *eps (relative) of its winner
  * has every cell that close re-evaluated and the reference's first-occurrence rule applied to the float64 values.
+ * Three cases keep a float32 decision (the values returned are still the float64 values of the cells named): more than 64 rows of a
+ * circshift search within *eps of the chosen one (the float32 choice of the row stands), one of such tied rows with more than 4096
+ * cells within *eps of its maximum (that row competes with its float32 maximum), and more than 4096 cells of the chosen row within *eps
+ * of its first maximum or second peak (the float32 first maximum and second peak stand) - plateaus, as a record of zeros gives.
  * ties: PRNs of the last search resolved that way; max_dev: largest |float32 peak - float64 peak| / float64 peak over its PRNs. */
 int gc_acq_guard_stats(gc_context* ctx, int32_t* ties, double* max_dev, double* eps);
 
