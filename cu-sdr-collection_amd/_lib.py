@@ -26,6 +26,7 @@ GC_EXCISE_MAX_GUARD = 4096   # gc_excise_pulses: longest guard in front of and b
 GC_EXCISE_MAX_WIDEN = 64     # gc_excise_sweep: most bins cut on either side of a hot one
 GC_DDC_MAX_TAPS, GC_DDC_MAX_DECIM = 2048, 64   # gc_downconvert: longest filter, largest decimation
 GC_RS_MAX_INTERP, GC_RS_MAX_TAPS = 64, 2048    # gc_resample: largest L, longest prototype (decim goes up to GC_DDC_MAX_DECIM * L)
+GC_ARRAY_MAX_RECORDS, GC_ARRAY_MAX_TAPS = 8, 32  # gc_array_covariance / gc_array_combine: most records; most taps (combine) and lags (covariance)
 GC_PLL_2ND_ORDER, GC_PLL_3_STATE = 0, 1
 GC_CNO_VSM, GC_CNO_PLD, GC_CNO_PLD_PILOT_SWAPPED, GC_CNO_PLD_PILOT = 0, 1, 2, 3   # gc_cno_mode
 GC_CNO_NPLD = 5
@@ -182,6 +183,21 @@ class gc_rs_params(C.Structure):
                 ("ntaps", C.c_int32), ("reserved", C.c_int32), ("carr_freq", C.c_double), ("carr_phase", C.c_double)]
 
 
+class gc_array_cov_params(C.Structure):
+    """gc_array_covariance: lags 0 .. nlags-1 of nrecords records over the samples first_sample .. first_sample + nsamples - 1."""
+    _fields_ = [("first_sample", C.c_int64), ("nsamples", C.c_int64), ("nrecords", C.c_int32), ("nlags", C.c_int32)]
+
+
+class gc_array_combine_params(C.Structure):
+    """gc_array_combine: output m is the weighted sum at record sample first_sample + m and is written to sample dst_first + m of dst."""
+    _fields_ = [("first_sample", C.c_int64), ("noutputs", C.c_int64), ("dst_first", C.c_int64), ("nrecords", C.c_int32), ("ntaps", C.c_int32)]
+
+
+class gc_array_combine_result(C.Structure):
+    """gc_array_combine: clipped components and the sum of squares of what was stored."""
+    _fields_ = [("clipped", C.c_int64), ("sum_sq", C.c_uint64)]
+
+
 class gc_rs_result(C.Structure):
     """gc_resample: gc_ddc_result's fields (phase_step per tick) and the rate of the record written."""
     _fields_ = [("phase_step", C.c_uint64), ("phase0", C.c_uint64), ("clipped", C.c_int64), ("sum_sq", C.c_uint64), ("carr_freq", C.c_double),
@@ -297,6 +313,9 @@ SYMBOLS = {
     "gc_debug_ddc_tile_outputs": (C.c_longlong, [C.c_int, C.c_int]),
     "gc_resample": (C.c_int, [_P, _P, C.POINTER(gc_rs_params), C.POINTER(C.c_double), C.POINTER(gc_rs_result)]),
     "gc_debug_rs_tile_outputs": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "gc_array_covariance": (C.c_int, [C.POINTER(_P), C.POINTER(gc_array_cov_params), C.POINTER(C.c_int64)]),
+    "gc_array_combine": (C.c_int, [C.POINTER(_P), _P, C.POINTER(gc_array_combine_params), C.POINTER(C.c_double), C.POINTER(gc_array_combine_result)]),
+    "gc_debug_array_tile_outputs": (C.c_longlong, [C.c_int, C.c_int]),
 }
 
 _lib = None

@@ -50,7 +50,9 @@ _CORR_UNITS = ["gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.h
                                   # gc_excise_bins: a gain per frequency bin by weighted overlap-add on seg_fft.hip's transform;
                                   # gc_excise_sweep: the same overlap-add with a decision per segment and bin (mark, apply, integer counts)
                "ddc.hip",         # gc_downconvert: complex FIR, decimation, a 64-bit NCO and requantisation into a second record, float64
-               "resample.hip"]    # gc_resample: the same at a rational rate change L / M, the taps staged phase-major (polyphase), float64
+               "resample.hip",    # gc_resample: the same at a rational rate change L / M, the taps staged phase-major (polyphase), float64
+               "array.hip"]       # gc_array_covariance: K records' lagged covariance in exact integers; gc_array_combine: their weighted sum
+                                  # over K x T complex taps into a second record, float64 (antenna-array null steering)
 
 
 def _tuned(spec: str) -> str:
@@ -64,7 +66,7 @@ LIBS = {
     "libgnsscorr_tuning.so": [_tuned(u) for u in _CORR_UNITS],
     "libgnsssynth.so": ["synth.hip"],
 }
-HEADERS = ["gc_internal.h", "corr_common.h", "record_fmt.h", "record_check.h", "replica_f64.h", "launch_plan.h", "bank_plan.h", "probe_plan.h", "excise_plan.h", "ddc_plan.h", "resample_plan.h", "fir_common.h", "devloop.h", "acq_guard.h", "shift_pick.h", "acq_internal.h", "fft_plan.h", "seg_fft.h", os.path.join("..", "..", "include", "gnsscorr.h")]
+HEADERS = ["gc_internal.h", "corr_common.h", "record_fmt.h", "record_check.h", "replica_f64.h", "launch_plan.h", "bank_plan.h", "probe_plan.h", "excise_plan.h", "ddc_plan.h", "resample_plan.h", "array_plan.h", "fir_common.h", "devloop.h", "acq_guard.h", "shift_pick.h", "acq_internal.h", "fft_plan.h", "seg_fft.h", os.path.join("..", "..", "include", "gnsscorr.h")]
 # --offload-compress: the gfx950 code objects inside the fat binary are zstd-compressed (10.1 -> ~1.6 MB; the HIP runtime inflates them
 # when the library is loaded: ~20 ms once per process)
 FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
@@ -77,7 +79,8 @@ FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-f
 NO_CONTRACT = {"gnsscorr.hip", "corr_kernel.hip", "corr_fast.hip", "corr_multi.hip", "corr_cboc.hip", "corr_lane.hip", "track.hip", "corr_f64.hip", "corr_bank.hip", "cancel.hip",
                "excise.hip",   # excise.hip: y = s v + s v' and P = re re + im im are two products and a sum, each rounded by itself
                "ddc.hip",      # ddc.hip: a tap is four products, a difference and three sums, each rounded by itself
-               "resample.hip"} # resample.hip: ddc.hip's arithmetic over the taps of one phase
+               "resample.hip", # resample.hip: ddc.hip's arithmetic over the taps of one phase
+               "array.hip"}    # array.hip: the combine is ddc.hip's tap arithmetic over K records (the covariance is integers)
 
 
 def _hipcc() -> str:

@@ -202,6 +202,8 @@ struct gc_context {
                              // counts (excise.hip: ExciseState)
   void* ddc = nullptr;       // gc_downconvert: the taps and the two result counters on the device (ddc.hip: DdcState)
   void* rs = nullptr;        // gc_resample: the phase-major taps and the two result counters on the device (resample.hip: RsState)
+  void* arr = nullptr;       // gc_array_covariance / gc_array_combine with this context as srcs[0]: the covariance's slot copies, the weights and
+                             // the two result counters on the device (array.hip: ArrState)
 
   // gc_track_multi: this context's tracking call runs next to other contexts' on the same device.  Its persistent kernels
   // are then launched with a plain launch instead of a cooperative one (gc_launch_persistent below).
@@ -282,7 +284,7 @@ void gc_fill_cno_host(gc_context* ctx, const gc_track_params* p, int nch, const 
 
 inline int gc_bytes_per_sample(int dtype, int layout) { return (layout == GC_REAL ? 1 : 2) * (dtype == GC_I16 ? 2 : 1); }
 
-// The state a unit keeps in its void* slot of the context (probe, cancel, excise, ddc, rs), made on first use; nullptr: no memory
+// The state a unit keeps in its void* slot of the context (probe, cancel, excise, ddc, rs, arr), made on first use; nullptr: no memory
 template <class S>
 S* gc_unit_state(void*& slot) {
   if (!slot) slot = new (std::nothrow) S();
@@ -302,6 +304,7 @@ void gc_cancel_free(gc_context* ctx);  // cancel.hip
 void gc_excise_free(gc_context* ctx);  // excise.hip
 void gc_ddc_free(gc_context* ctx);  // ddc.hip
 void gc_rs_free(gc_context* ctx);  // resample.hip
+void gc_array_free(gc_context* ctx);  // array.hip
 int gc_sync_channels(gc_context* ctx);
 // Launches the correlator for `nblocks` descriptors of scope `s` already on the device: plans (launch_plan.h), fills the
 // kernel arguments from the plan, dispatches on its kernel, combines the partial sums where splits > 1.

@@ -103,6 +103,7 @@ int gc_destroy(gc_context* ctx) {
   gc_excise_free(ctx);
   gc_ddc_free(ctx);
   gc_rs_free(ctx);
+  gc_array_free(ctx);
   (void)hipEventDestroy(ctx->ev_start);
   (void)hipEventDestroy(ctx->ev_stop);
   (void)hipStreamDestroy(ctx->stream);

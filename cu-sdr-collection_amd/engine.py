@@ -537,6 +537,78 @@ class Engine:
         """gc_debug_rs_tile_outputs (test hook, host code only): outputs a workgroup of resample() takes; 0 for a refused (interp, decim, ntaps)."""
         return int(L.load().gc_debug_rs_tile_outputs(int(interp), int(decim), int(ntaps)))
 
+    @staticmethod
+    def _array_whole(name, v, bits):
+        if isinstance(v, (bool, str, bytes)) or v is None or v != int(v) or not -(1 << (bits - 1)) <= int(v) < 1 << (bits - 1):
+            raise ValueError(f"array: {name} must be a whole number of {bits} bits, not {v!r}")
+        return int(v)
+
+    @staticmethod
+    def _array_records(records):
+        """The engines of an array call as a ctypes array of their contexts; ValueError for anything but 1 .. GC_ARRAY_MAX_RECORDS of them."""
+        try:
+            recs = list(records)
+        except TypeError:
+            raise ValueError(f"array: records must be a list of engines, not {records!r}") from None
+        if not 1 <= len(recs) <= L.GC_ARRAY_MAX_RECORDS or not all(isinstance(r, Engine) for r in recs):
+            raise ValueError(f"array: records must be 1 .. {L.GC_ARRAY_MAX_RECORDS} engines, not {len(recs)} entries of {sorted({type(r).__name__ for r in recs})}")
+        return recs, (C.c_void_p * len(recs))(*[r._ctx for r in recs])
+
+    @staticmethod
+    def _array_weights(weights, nrecords) -> np.ndarray:
+        """array_combine()'s weights as contiguous float64 [K, T, 2] = (re, im); ValueError for anything but a [K] or [K, T] real or
+        complex array or a [K, T, 2] real one with 1 <= T <= GC_ARRAY_MAX_TAPS - before any library call."""
+        w = np.asarray(weights)
+        numeric = np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)
+        if w.ndim in (1, 2) and (numeric or np.issubdtype(w.dtype, np.complexfloating)):
+            w = w.astype(np.complex128).reshape(w.shape[0], -1)
+            w = np.stack([w.real, w.imag], axis=-1)
+        elif not (w.ndim == 3 and w.shape[2] == 2 and numeric):
+            raise ValueError(f"array_combine(): weights must be [K] or [K, T] complex or [K, T, 2] real, not {w.dtype} {w.shape}")
+        if w.shape[0] != nrecords or not 1 <= w.shape[1] <= L.GC_ARRAY_MAX_TAPS:
+            raise ValueError(f"array_combine(): weights for {nrecords} records and 1 .. {L.GC_ARRAY_MAX_TAPS} taps, not {w.shape[0]} x {w.shape[1]}")
+        return np.ascontiguousarray(w, dtype=np.float64)
+
+    @staticmethod
+    def array_covariance(records, first_sample: int, nsamples: int, nlags: int = 1) -> np.ndarray:
+        """gc_array_covariance: C[l][a][b] = sum over the nsamples samples from first_sample of x_a[n] conj(x_b[n - l]) for the records
+        of the K engines `records` (one device, one dtype and layout) and the lags 0 .. nlags-1, in exact integers.
+        Returns int64 [L, K, K, 2] = (re, im) (include/gnsscorr.h)."""
+        recs, ctxs = Engine._array_records(records)
+        first = Engine._array_whole("first_sample", first_sample, 64)
+        n = Engine._array_whole("nsamples", nsamples, 64)
+        lags = Engine._array_whole("nlags", nlags, 32)
+        if not 1 <= lags <= L.GC_ARRAY_MAX_TAPS:
+            raise ValueError(f"array_covariance(): nlags must lie in 1 .. {L.GC_ARRAY_MAX_TAPS}, not {lags}")
+        p = L.gc_array_cov_params(first, n, len(recs), lags)
+        cov = np.zeros((lags, len(recs), len(recs), 2), dtype=np.int64)
+        L.check(recs[0]._lib.gc_array_covariance(ctxs, C.byref(p), cov.ctypes.data_as(C.POINTER(C.c_int64))))
+        return cov
+
+    @staticmethod
+    def array_combine(records, dst: "Engine", weights, first_sample: int = 0, noutputs: int | None = None, dst_first: int = 0):
+        """gc_array_combine: output m = sum over the K engines `records` and the taps k of weights[a][k] * x_a[first_sample + m - k], in
+        float64, rounded into sample dst_first + m of `dst`'s record (another engine on the same device; any dtype and layout).
+        `weights` is [K] or [K, T] complex, or [K, T, 2] real; it is applied as given (conjugate for w^H x).  noutputs=None: what both
+        sides hold.  Returns SimpleNamespace(clipped, sum_sq, noutputs) (include/gnsscorr.h)."""
+        recs, ctxs = Engine._array_records(records)
+        w = Engine._array_weights(weights, len(recs))
+        first = Engine._array_whole("first_sample", first_sample, 64)
+        dfirst = Engine._array_whole("dst_first", dst_first, 64)
+        if noutputs is None:
+            nout = min(min(int(r.if_buffer()[1]) for r in recs) - first, int(dst.if_buffer()[1]) - dfirst)
+        else:
+            nout = Engine._array_whole("noutputs", noutputs, 64)
+        p = L.gc_array_combine_params(first, nout, dfirst, len(recs), w.shape[1])
+        r = L.gc_array_combine_result()
+        L.check(recs[0]._lib.gc_array_combine(ctxs, dst._ctx, C.byref(p), w.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)))
+        return SimpleNamespace(clipped=int(r.clipped), sum_sq=int(r.sum_sq), noutputs=nout)
+
+    @staticmethod
+    def debug_array_tile_outputs(nrecords: int, ntaps: int) -> int:
+        """gc_debug_array_tile_outputs (test hook, host code only): samples a workgroup of either array kernel takes; 0 for a refused (nrecords, ntaps)."""
+        return int(L.load().gc_debug_array_tile_outputs(int(nrecords), int(ntaps)))
+
     def last_kernel(self) -> int:
         """gc_debug_last_kernel: 0 lane, 1 fast (one wave), 2 fast (four waves, int8 pairs), 3 fast (four waves, floats), 4 multi-transition
         (corr_multi.hip), 5 hybrid for channels with a derived six-fold arm (corr_cboc.hip), 6 float64 (corr_f64.hip), -1 mixed

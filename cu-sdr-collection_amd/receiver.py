@@ -752,6 +752,90 @@ def resample_record(engine: Engine, dst: Engine, fs_out: float | None = None, ra
                                 delay=(T - 1) / 2.0 - first)
 
 
+def array_covariance_matrix(cov, ntaps: int) -> np.ndarray:
+    """The Hermitian K T x K T complex128 covariance of the stacked snapshot z[n] = (x_a[n - s]), a = 0 .. K-1, s = 0 .. T-1 (index
+    a T + s), from Engine.array_covariance's int64 [L, K, K, 2] with L >= T: block-Toeplitz,
+        R[(a, s), (b, t)] = C[t - s][a][b]  for t >= s,   conj(C[s - t][b][a])  otherwise.
+    This is the range-shift approximation: the exact sum over n of x_a[n - s] conj(x_b[n - t]) runs over a range moved back by s
+    samples, so each entry differs from it by edge terms of at most T - 1 samples at either end of the range (none for T = 1)."""
+    c = np.asarray(cov)
+    T = int(ntaps)
+    if c.ndim != 4 or c.shape[1] != c.shape[2] or c.shape[3] != 2 or not 1 <= T <= c.shape[0]:
+        raise ValueError(f"array_covariance_matrix(): cov must be [L, K, K, 2] with L >= ntaps = {ntaps!r}, not {c.shape}")
+    K = c.shape[1]
+    z = c[..., 0].astype(np.float64) + 1j * c[..., 1].astype(np.float64)
+    R = np.empty((K, T, K, T), dtype=np.complex128)
+    for s in range(T):
+        for t in range(T):
+            R[:, s, :, t] = z[t - s] if t >= s else np.conj(z[s - t].T)
+    return R.reshape(K * T, K * T)
+
+
+def _array_loaded(R, loading: float) -> np.ndarray:
+    R = np.asarray(R, dtype=np.complex128)
+    if R.ndim != 2 or R.shape[0] != R.shape[1]:
+        raise ValueError(f"array weights: R must be a square matrix, not {R.shape}")
+    return R + float(loading) * np.eye(R.shape[0])
+
+
+def power_inversion_weights(R, nrecords: int, ntaps: int, ref: int = 0, loading: float = 0.0) -> np.ndarray:
+    """w = (R + loading I)^-1 e / (e^H (R + loading I)^-1 e) with e the unit vector at (record ref, tap 0): the output power w^H R w
+    is least among the weights with w[ref, tap 0] = 1.  Returns w as complex128 [K T]; Engine.array_combine takes
+    conj(w).reshape(K, T)."""
+    K, T, r = int(nrecords), int(ntaps), int(ref)
+    A = _array_loaded(R, loading)
+    if A.shape[0] != K * T or not 0 <= r < K:
+        raise ValueError(f"power_inversion_weights(): R must be {K * T} x {K * T} and ref in 0 .. {K - 1}, not {A.shape} and {ref!r}")
+    e = np.zeros(K * T, dtype=np.complex128)
+    e[r * T] = 1.0
+    u = np.linalg.solve(A, e)
+    return u / np.vdot(e, u)
+
+
+def mvdr_weights(R, steering, loading: float = 0.0) -> np.ndarray:
+    """w = (R + loading I)^-1 v / (v^H (R + loading I)^-1 v): least output power among the weights with w^H v = 1."""
+    A = _array_loaded(R, loading)
+    v = np.asarray(steering, dtype=np.complex128).reshape(-1)
+    if v.shape[0] != A.shape[0]:
+        raise ValueError(f"mvdr_weights(): a steering vector of {A.shape[0]} entries, not {v.shape[0]}")
+    u = np.linalg.solve(A, v)
+    return u / np.vdot(v, u)
+
+
+def null_steer(records, dst: Engine, settings, ntaps: int = 1, ref: int = 0, first_sample: int = 0, nsamples: int | None = None,
+               loading: float = 0.0, target_rms: float | None = None):
+    """Wide-band interference out of the records of an antenna array: one gc_array_covariance over the K engines `records`
+    (nsamples=None: what every record and dst hold from first_sample), the power-inversion weights for the reference element `ref`
+    over ntaps taps per element, and one gc_array_combine of conj(w) into `dst` (another engine on the same device with a record from
+    alloc_if; any dtype and layout) from its sample 0.
+      loading     added to R's diagonal, in the covariance's units (squared counts summed over the range).
+      target_rms  None: gain 1.  Else the rms a stored component should have: a trial combine on the first min(nsamples, 65536)
+                  outputs, the weights scaled by target_rms / the rms sum_sq gives, then the whole range - as downconvert_band() scales.
+    The reference tap is tap 0, so the delay is 0: sample indices, samplingFreq and IF of `settings` hold for dst, whose sampling
+    frequency is set to settings.samplingFreq.
+    Returns (result of Engine.array_combine, w: complex128 [K, T] before the gain, gain, cov: int64 [T, K, K, 2])."""
+    recs = list(records)
+    K, T = len(recs), int(ntaps)
+    first = int(first_sample)
+    if nsamples is None:
+        n = min(min(int(r.if_buffer()[1]) for r in recs) - first, int(dst.if_buffer()[1]))
+    else:
+        n = int(nsamples)
+    cov = Engine.array_covariance(recs, first, n, T)
+    w = power_inversion_weights(array_covariance_matrix(cov, T), K, T, ref, loading).reshape(K, T)
+    gain = 1.0
+    comps = 1 if dst.if_format()[1] == L.GC_REAL else 2
+    if target_rms is not None:
+        trial = Engine.array_combine(recs, dst, np.conj(w), first_sample=first, noutputs=min(n, 65536))
+        rms = math.sqrt(trial.sum_sq / (comps * trial.noutputs))
+        if not rms > 0.0:
+            raise ValueError("null_steer(): the records hold nothing to scale (every stored component of the trial is zero)")
+        gain = float(target_rms) / rms
+    res = Engine.array_combine(recs, dst, gain * np.conj(w), first_sample=first, noutputs=n)
+    dst.set_sampling_freq(settings.samplingFreq)
+    return res, w, gain, cov
+
+
 def cancel_tracked(fid: Engine, trackResults, channel, settings, which=None, signal: str = "GPS_L1CA", epochs=None, dst: Engine | None = None,
                    mode: str = "subtract", amp=None):
     """What lies under the signals a tracking run followed: every chosen channel's tracked component rebuilt from the state tracking.m

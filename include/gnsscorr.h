@@ -1059,6 +1059,76 @@ int gc_resample(gc_context* src, gc_context* dst, const gc_rs_params* p,
 /* Test hook (host code only, no context): outputs a workgroup of the kernel takes (a tile); 0 for an interp, decim or ntaps out of range. */
 long long gc_debug_rs_tile_outputs(int interp, int decim, int ntaps);
 
+/* ---- several antennas, one front end: the records' covariance and their weighted sum -------------------------------------------------
+ * gc_array_covariance and gc_array_combine are the two halves of antenna-array null steering that run over every sample (csrc/array.hip):
+ * the covariance of K records tells the receiver where wide-band interference comes from, a weighted sum of the records puts a null
+ * there.  What lies between them - a K T x K T solve, the power-inversion rule - is host arithmetic (receiver.null_steer,
+ * matlab/gnsscorr_null_steer.m).  `srcs` are K contexts on one device whose records share one dtype and layout (the same context may
+ * appear twice); `dst` is another context on that device with a record of any sample count, dtype and layout.  Both calls are
+ * synchronous, on srcs[0]'s stream, after the pending work of every other source's stream and of dst's; their buffers are srcs[0]'s
+ * (released by gc_destroy).  No sampling frequency is needed.  New entry points are detected by symbol: GC_API_VERSION is unchanged.
+ *
+ * Shared by both calls
+ *   x_a[n] = (re, im) of sample n of srcs[a]'s record, as gc_downconvert reads it: I/Q as stored, Q/I swapped, real records im = 0;
+ *   x_a[n] = 0 for n < 0.  (No call reads behind a record's end: see the refusals.)
+ *
+ * gc_array_covariance, exact integers.  K = nrecords, L = nlags:
+ *   C[l][a][b] = sum over n = first_sample .. first_sample + nsamples - 1 of x_a[n] * conj(x_b[n - l]),  0 <= l < L,  0 <= a, b < K
+ *     re = sum (ar*br + ai*bi),  im = sum (ai*br - ar*bi)        with (ar, ai) = x_a[n], (br, bi) = x_b[n - l]
+ *   x_b[n - l] in front of first_sample is the record's own sample; it is zero only in front of sample 0.
+ *   cov[((l * K + a) * K + b) * 2 + {0, 1}] = {re, im}.  nsamples <= 2^31 keeps every sum inside 63 bits for int16 records
+ *   (2^31 samples * 2 products * 2^30).
+ * Guarantees: the same input gives the same numbers; they do not depend on the tile (gc_debug_array_tile_outputs); two calls on adjacent
+ * ranges add up to one call on the whole range; lag 0 is Hermitian, C[0][a][b] == conj(C[0][b][a]); C[0][a][a].re is the record's sum
+ * of squares over the range.
+ *
+ * gc_array_combine, in float64, every operation rounded by itself (no fused multiply-add).  K = nrecords, T = ntaps,
+ * w[a][k] = (wr, wi) = weights[(a * T + k) * 2 + {0, 1}]:
+ *   filter    for output m, 0 <= m < noutputs, with n = first_sample + m:  a_r = a_i = +0.0; for a = 0 .. K-1 in ascending order and,
+ *             within each a, k = 0 .. T-1 in ascending order, with x = x_a[n - k]:
+ *               pr = wr*xr - wi*xi,  pi = wr*xi + wi*xr,  a_r = a_r + pr,  a_i = a_i + pi
+ *   store     (a_r, a_i) into dst's record at sample dst_first + m, as gc_downconvert stores (yr, yi): clamp(rint(.)) per component
+ *             in dst's own format.
+ *   result    clipped and sum_sq as gc_downconvert counts them.
+ * There is no NCO and no decimation (gc_downconvert / gc_resample run on the result).  The weights are applied as given: a caller who
+ * wants w^H x conjugates.
+ * Guarantees: dst's bytes outside [dst_first, dst_first + noutputs) are untouched.  The same input gives the same bytes and statistics.
+ * An output depends on its own K T samples only - not on the tile, not on the call: pieces join to the whole.  With K = 1 every byte
+ * and both statistics are gc_downconvert's with decim = 1, carr_freq = 0, carr_phase = 0 and the same taps (its rotation by the exact
+ * angle 0 adds +-0, which changes no stored integer).
+ *
+ * Refusals (a refused call writes nothing: not cov, not dst, not res), in this order: GC_E_INVALID for a null srcs / p / cov / weights /
+ * dst or a null entry of srcs, nrecords outside [1, GC_ARRAY_MAX_RECORDS], nlags or ntaps outside [1, GC_ARRAY_MAX_TAPS], first_sample
+ * or dst_first < 0, nsamples outside [1, 2^31], noutputs < 1, a weight that is not finite, a source or dst on another device than
+ * srcs[0], sources of different dtype or layout, a dst record that is, or overlaps, any source's; GC_E_STATE for a source or dst
+ * without a record; GC_E_RANGE when first_sample + nsamples (or + noutputs) exceeds any source's sample count or dst_first + noutputs
+ * exceeds dst's; GC_E_NOMEM. */
+#define GC_ARRAY_MAX_RECORDS 8
+#define GC_ARRAY_MAX_TAPS    32      /* taps of gc_array_combine and lags of gc_array_covariance */
+typedef struct gc_array_cov_params {
+  int64_t first_sample;  /* >= 0 */
+  int64_t nsamples;      /* 1 .. 2^31 */
+  int32_t nrecords;      /* K, 1 .. GC_ARRAY_MAX_RECORDS */
+  int32_t nlags;         /* L, 1 .. GC_ARRAY_MAX_TAPS: lags 0 .. L-1 */
+} gc_array_cov_params;   /* 24 bytes */
+int gc_array_covariance(gc_context* const* srcs, const gc_array_cov_params* p, int64_t* cov /* [L][K][K][2] = {re, im} */);
+typedef struct gc_array_combine_params {
+  int64_t first_sample;  /* record index of output 0's newest input sample, >= 0 */
+  int64_t noutputs;      /* >= 1 */
+  int64_t dst_first;     /* output m is written to sample dst_first + m of dst's record, >= 0 */
+  int32_t nrecords;      /* K, 1 .. GC_ARRAY_MAX_RECORDS */
+  int32_t ntaps;         /* T, 1 .. GC_ARRAY_MAX_TAPS */
+} gc_array_combine_params;  /* 32 bytes */
+typedef struct gc_array_combine_result {
+  int64_t  clipped;      /* stored components whose rint(.) lay outside dst's integer range */
+  uint64_t sum_sq;       /* exact sum of the squares of the stored components */
+} gc_array_combine_result;  /* 16 bytes */
+int gc_array_combine(gc_context* const* srcs, gc_context* dst, const gc_array_combine_params* p,
+                     const double* weights /* [K][T][2] = {re, im} */, gc_array_combine_result* res /* may be NULL */);
+/* Test hook (host code only, no context): samples a workgroup of either kernel takes (a tile), ntaps standing for nlags too; 0 for an
+ * nrecords or ntaps out of range. */
+long long gc_debug_array_tile_outputs(int nrecords, int ntaps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,12 @@
  *          fs * interp, output m sits at tick firstTick0 + m * decim (a tick is 1 / interp input sample), is rotated by an NCO of
  *          carrFreq Hz and rounded into hDst's record from sample dstFirst0; nOutputs absent or [] = every output with a record sample
  *          under it, up to hDst's capacity; r = [clipped sumSq carrFreqUsed nOutputs outRate], nco = uint64 [phaseStep phase0]
+ *   cov  = gnsscorr_mex('array_covariance', hList, firstSample0, nSamples, nLags)        % the lagged covariance of the records of the K
+ *          contexts hList over nSamples samples from firstSample0 in exact integers (gc_array_covariance): 2 x K x K x L int64,
+ *          cov(:, b, a, l) = [re; im] of sum x_a[n] conj(x_b[n - (l - 1)])
+ *   r    = gnsscorr_mex('array_combine', hList, hDst, weights, firstSample0, nOutputs, dstFirst0)   % the weighted sum of the K records
+ *          (gc_array_combine): weights 2 x T x K doubles (re; im), applied as given; output m = sum_a sum_k w(k, a) x_a[firstSample0 +
+ *          m - k] rounded into hDst's record from sample dstFirst0; nOutputs [] = what both sides hold; r = [clipped sumSq nOutputs]
  *   n    = gnsscorr_mex('device_count')                                              % HIP devices visible: one context per device
  *   prev = gnsscorr_mex('set_precision', h, 'double'|'single')                    % float64 correlations for every later correlate /
  *          track call of this context (gc_set_precision), 'single' = the float32 kernels (default); returns the previous setting
@@ -108,6 +114,18 @@ static gc_context* handle(const mxArray* a) {
   int i = (int)mxGetScalar(a);
   if (i < 0 || i >= 16 || !g_ctx[i]) mexErrMsgIdAndTxt("gnsscorr:handle", "invalid context handle");
   return g_ctx[i];
+}
+
+/* the K contexts of a handle list (the array commands); K = 1 .. GC_ARRAY_MAX_RECORDS */
+static int handle_list(const mxArray* a, gc_context** out) {
+  const size_t n = mxGetNumberOfElements(a);
+  if (!mxIsDouble(a) || n < 1 || n > GC_ARRAY_MAX_RECORDS) mexErrMsgIdAndTxt("gnsscorr:usage", "hList must hold 1 .. %d context handles", GC_ARRAY_MAX_RECORDS);
+  for (size_t k = 0; k < n; ++k) {
+    const int i = (int)mxGetDoubles(a)[k];
+    if (i < 0 || i >= 16 || !g_ctx[i]) mexErrMsgIdAndTxt("gnsscorr:handle", "invalid context handle");
+    out[k] = g_ctx[i];
+  }
+  return (int)n;
 }
 
 static double field(const mxArray* s, const char* name) {
@@ -929,6 +947,70 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       uint64_t* u = (uint64_t*)mxGetData(plhs[1]);
       u[0] = res.phase_step, u[1] = res.phase0;
     }
+  } else if (!strcmp(cmd, "array_covariance")) {
+    /* cov = gnsscorr_mex('array_covariance', hList, firstSample0, nSamples, nLags) */
+    if (nrhs < 5) mexErrMsgIdAndTxt("gnsscorr:usage", "array_covariance: hList, firstSample0, nSamples, nLags");
+    gc_context* srcs[GC_ARRAY_MAX_RECORDS];
+    const int K = handle_list(prhs[1], srcs);
+    const double whole[3] = {mxGetScalar(prhs[2]), mxGetScalar(prhs[3]), mxGetScalar(prhs[4])};
+    for (int i = 0; i < 3; ++i)
+      if (!(whole[i] >= -9007199254740992.0 && whole[i] <= 9007199254740992.0) || whole[i] != (double)(int64_t)whole[i])
+        mexErrMsgIdAndTxt("gnsscorr:usage", "array_covariance: firstSample0, nSamples and nLags must be whole numbers");
+    if (whole[2] < 1 || whole[2] > GC_ARRAY_MAX_TAPS) mexErrMsgIdAndTxt("gnsscorr:usage", "array_covariance: 1 <= nLags <= %d", GC_ARRAY_MAX_TAPS);
+    gc_array_cov_params p;
+    p.first_sample = (int64_t)whole[0];
+    p.nsamples = (int64_t)whole[1];
+    p.nrecords = K;
+    p.nlags = (int32_t)whole[2];
+#ifndef GNSSCORR_TEST_MEX_H
+    const mwSize dims[4] = {2, (mwSize)K, (mwSize)K, (mwSize)p.nlags};
+    mxArray* out = mxCreateNumericArray(4, dims, mxINT64_CLASS, mxREAL);
+#else /* (the test-only mex.h holds three dimensions: the same numbers in the same order as 2 x K x (K L)) */
+    const mwSize dims[3] = {2, (mwSize)K, (mwSize)K * (mwSize)p.nlags};
+    mxArray* out = mxCreateNumericArray(3, dims, mxINT64_CLASS, mxREAL);
+#endif
+    int rc = gc_array_covariance(srcs, &p, (int64_t*)mxGetData(out));
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
+    if (rc) fail("gc_array_covariance");
+    plhs[0] = out;
+  } else if (!strcmp(cmd, "array_combine")) {
+    /* r = gnsscorr_mex('array_combine', hList, hDst, weights, firstSample0, nOutputs, dstFirst0) */
+    if (nrhs < 4) mexErrMsgIdAndTxt("gnsscorr:usage", "array_combine: hList, hDst, weights 2 x T x K[, firstSample0[, nOutputs[, dstFirst0]]]");
+    gc_context* srcs[GC_ARRAY_MAX_RECORDS];
+    const int K = handle_list(prhs[1], srcs);
+    const size_t nel = mxGetNumberOfElements(prhs[3]);
+    if (!mxIsDouble(prhs[3]) || mxGetM(prhs[3]) != 2 || nel < 2u * K || nel % (2u * K) != 0 || nel > 2u * K * GC_ARRAY_MAX_TAPS)
+      mexErrMsgIdAndTxt("gnsscorr:usage", "array_combine: weights must be 2 x T x K real doubles (re; im), 1 <= T <= %d", GC_ARRAY_MAX_TAPS);
+    double whole[3] = {0.0, -1.0, 0.0}; /* firstSample0, nOutputs (-1: all), dstFirst0 */
+    for (int i = 4; i < nrhs && i < 7; ++i)
+      if (mxGetNumberOfElements(prhs[i]) > 0) whole[i - 4] = mxGetScalar(prhs[i]);
+    for (int i = 0; i < 3; ++i)
+      if (!(whole[i] >= -9007199254740992.0 && whole[i] <= 9007199254740992.0) || whole[i] != (double)(int64_t)whole[i])
+        mexErrMsgIdAndTxt("gnsscorr:usage", "array_combine: firstSample0, nOutputs and dstFirst0 must be whole numbers");
+    gc_array_combine_params p;
+    p.first_sample = (int64_t)whole[0];
+    p.noutputs = (int64_t)whole[1];
+    p.dst_first = (int64_t)whole[2];
+    p.nrecords = K;
+    p.ntaps = (int32_t)(nel / (2u * K));
+    if (whole[1] < 0) { /* what both sides hold */
+      void* ptr = NULL;
+      uint64_t have = 0, room = 0;
+      if (gc_if_buffer(handle(prhs[2]), &ptr, &room)) fail("gc_if_buffer");
+      int64_t fit = (int64_t)room - p.dst_first;
+      for (int a = 0; a < K; ++a) {
+        if (gc_if_buffer(srcs[a], &ptr, &have)) fail("gc_if_buffer");
+        if ((int64_t)have - p.first_sample < fit) fit = (int64_t)have - p.first_sample;
+      }
+      p.noutputs = fit;
+    }
+    gc_array_combine_result res;
+    int rc = gc_array_combine(srcs, handle(prhs[2]), &p, mxGetDoubles(prhs[3]), &res);
+    if (rc == GC_E_RANGE) mexErrMsgIdAndTxt("gnsscorr:range", "%s", gc_last_error());
+    if (rc) fail("gc_array_combine");
+    plhs[0] = mxCreateDoubleMatrix(1, 3, mxREAL);
+    double* o = mxGetDoubles(plhs[0]);
+    o[0] = (double)res.clipped, o[1] = (double)res.sum_sq, o[2] = (double)p.noutputs;
   } else if (!strcmp(cmd, "device_count")) {
     int n = 0;
     if (gc_device_count(&n)) fail("gc_device_count");

@@ -1,0 +1,99 @@
+// The host plan of the antenna-array unit (csrc/array_plan.h) on the CPU: contexts that hold record FACTS only (an address that is
+// never read, the device, the length, the format - no device memory) for the argument checks of gc_array_covariance and
+// gc_array_combine, the tile and its LDS bytes, the tile walk and the accumulator constants, written out as plain integers.  Built by
+// tests/test_array_plan_cpu.py with the flags of array.hip; no GPU is touched.
+#include <cstdarg>
+
+#include "../cu-sdr-collection_amd/csrc/array_plan.h"
+
+void gc_set_error(const char*, ...) {}
+
+extern "C" {
+
+// `address` 0: no record; otherwise an address that is never read, so that two contexts can share, overlap or miss each other
+void* arr_shim_create(long long address, int device, unsigned long long if_nsamples, int dtype, int layout) {
+  gc_context* ctx = new gc_context();
+  ctx->d_if = address ? reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(address)) : nullptr;
+  ctx->device = device;
+  ctx->if_nsamples = if_nsamples;
+  ctx->if_dtype = dtype;
+  ctx->if_layout = layout;
+  return ctx;
+}
+
+void arr_shim_destroy(void* ctx) { delete static_cast<gc_context*>(ctx); }
+
+static void plan_out(const ArrPlan& pl, long long* out) {
+  out[0] = pl.tile;
+  out[1] = pl.ntiles;
+  out[2] = pl.span;
+  out[3] = pl.rec_bytes;
+  out[4] = pl.lds_bytes;
+  out[5] = pl.lds_budget;
+  out[6] = pl.src_bps;
+  out[7] = pl.dst_bps;
+}
+
+// gc_array_covariance up to its first HIP call; where the call is accepted
+// out = {tile, ntiles, span, rec_bytes, lds_bytes, lds_budget, src_bps, dst_bps}
+int arr_shim_cov_check(void* const* srcs, const gc_array_cov_params* p, const int64_t* cov, long long* out) {
+  ArrPlan pl;
+  const int rc = arr_cov_check(reinterpret_cast<gc_context* const*>(srcs), p, cov, &pl);
+  if (rc) return rc;
+  plan_out(pl, out);
+  return GC_OK;
+}
+
+// gc_array_combine up to its first HIP call; out as above
+int arr_shim_combine_check(void* const* srcs, void* dst, const gc_array_combine_params* p, const double* weights, long long* out) {
+  ArrPlan pl;
+  const int rc = arr_combine_check(reinterpret_cast<gc_context* const*>(srcs), static_cast<const gc_context*>(dst), p, weights, &pl);
+  if (rc) return rc;
+  plan_out(pl, out);
+  return GC_OK;
+}
+
+long long arr_shim_tile_outputs(int nrecords, int ntaps) { return arr_tile_outputs(nrecords, ntaps); }
+
+long long arr_shim_rec_bytes(long long tile, int ntaps, int bps) { return arr_rec_bytes(tile, ntaps, bps); }
+
+long long arr_shim_lds_bytes(long long tile, int nrecords, int ntaps, int bps, int weights) { return arr_lds_bytes(tile, nrecords, ntaps, bps, weights != 0); }
+
+// the walk over nsamples in tiles of arr_tile_outputs(nrecords, ntaps): per tile {m0, n, n_lo, n_hi}.  Returns the integers written
+// (or needed).
+long long arr_shim_walk(long long first_sample, long long nsamples, int nrecords, int ntaps, long long* out, long long cap) {
+  ArrPlan pl;
+  pl.tile = arr_tile_outputs(nrecords, ntaps);
+  if (pl.tile < 1) return 0;
+  pl.ntiles = (nsamples + pl.tile - 1) / pl.tile;
+  long long n = 0;
+  ArrTile t;
+  for (long long i = 0; arr_tile_at(pl, first_sample, nsamples, ntaps, i, &t); ++i)
+    for (long long v : {t.m0, t.n, t.n_lo, t.n_hi}) {
+      if (n < cap) out[n] = v;
+      ++n;
+    }
+  return n;
+}
+
+// what the kernels stage of one record for the samples [n_lo, n_hi]: out = {byte offset of the first vector, vectors}
+void arr_shim_stage(long long n_lo, long long n_hi, int bps, long long* out) {
+  out[0] = arr_stage_base(n_lo, bps);
+  out[1] = arr_stage_vecs(n_lo, n_hi, bps);
+}
+
+void arr_shim_constants(long long* out) {
+  out[0] = kArrWG;
+  out[1] = kArrChains;
+  out[2] = kArrMaxTile;
+  out[3] = kArrLdsBudget;
+  out[4] = kArrStaticLds;
+  out[5] = GC_ARRAY_MAX_RECORDS;
+  out[6] = GC_ARRAY_MAX_TAPS;
+  out[7] = kArrStageSlack;
+  out[8] = kArrCovI32Cap;
+  out[9] = kArrCovMaxSamples;
+  out[10] = kArrCovSlots;
+}
+
+}  // extern "C"
