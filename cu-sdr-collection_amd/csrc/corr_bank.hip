@@ -34,7 +34,8 @@
 //               entry 1 + mod(p - 1, n - 2), and since the pads are the period (checked on the host) c[k - 1] is the entry before.
 //               The entry's two table values, their comparison and e(k) - the float64 search that is the expensive part of a
 //               tap - do not depend on the carrier: computed once, then one read of P_g[e - i0] and two fmaf per bin.
-//   sums        float32 per chunk and (arm, bin, tap) - lanes by fixed shuffles -, written as float64 partials
+//   sums        per chunk and (arm, bin, tap) over the float32 P values, a lane's terms in float64, the lanes by fixed shuffles - in
+//               float64 too where the chunk crosses more than 64 entries, else in float32 -, written as float64 partials
 //               [chunk][arm][bin][tap][2] and added over a block's chunks in index order by bank_combine_kernel.  No atomics:
 //               the same input gives the same bits.
 #include <cstring>
@@ -192,9 +193,15 @@ __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
     const int8_t* __restrict__ tab = chn->tab[arm];
     const int L = chn->nent[arm] - 2;  // the code's period in entries
     const int k_lo = rp.index(i0), k_hi = rp.index(i_last);
-    float2 acc[G];
+    // A lane's terms add in float64.  The lanes of a pair take every 64th entry, so on a table that alternates (BOC(6,1): a
+    // transition at every entry) a lane's terms all have one sign and add up to ten times |P|, and the lanes' totals alternate: in
+    // float32 throughout that cost 2.4e-6 of sum |x| on a 1 024-sample block of an int16 record (tests/test_gpu_bank_edges.py).
+    // Where the chunk crosses at most 64 entries (GPS L1 C/A at 18 Msps: 58) a lane holds at most one product, the same number in
+    // either format, and the lanes are then added in float32, as they were while all of phase B was float32: the same bits.
+    const bool one_pass = k_hi - k_lo <= 64;  // uniform over the wavefront
+    double2 acc[G];
 #pragma unroll
-    for (int g = 0; g < G; ++g) acc[g] = make_float2(0.0f, 0.0f);
+    for (int g = 0; g < G; ++g) acc[g] = make_double2(0.0, 0.0);
     for (int k = k_lo + 1 + lane; k <= k_hi; k += 64) {
       int r = (k - 1) % L;
       if (r < 0) r += L;
@@ -202,32 +209,45 @@ __global__ __launch_bounds__(kBankWG) void bank_chunk_kernel(const BankArgs p) {
       if (c_prev == c_k) continue;
       // the smallest sample with index >= k lies in (i0, i_last]: index(i0) < k <= index(i_last)
       const int e = rp.boundary(k, i0, i_last);
-      const float d = (float)(c_prev - c_k);
+      const double d = (double)(c_prev - c_k);
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         if (g < gn) {
           const float2 v = P[g][e - i0];
-          acc[g].x = fmaf(d, v.x, acc[g].x);
-          acc[g].y = fmaf(d, v.y, acc[g].y);
+          acc[g].x = fma(d, (double)v.x, acc[g].x);
+          acc[g].y = fma(d, (double)v.y, acc[g].y);
         }
       }
     }
     int r = (k_hi - 1) % L;
     if (r < 0) r += L;
-    const float c_end = (float)tab[r + 1];
+    const double c_end = (double)tab[r + 1];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       if (g < gn) {
-        float2 a = acc[g];
+        double* dst = prow + 2 * (((long long)arm * p.nfreq + m0 + g) * p.ntaps + j);
+        if (one_pass) {
+          float2 a = make_float2((float)acc[g].x, (float)acc[g].y);
 #pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) {
-          a.x += __shfl_down(a.x, sh, 64);
-          a.y += __shfl_down(a.y, sh, 64);
-        }
-        if (lane == 0) {
-          double* dst = prow + 2 * (((long long)arm * p.nfreq + m0 + g) * p.ntaps + j);
-          dst[0] = (double)fmaf(c_end, P[g][n].x, a.x);
-          dst[1] = (double)fmaf(c_end, P[g][n].y, a.y);
+          for (int sh = 32; sh > 0; sh >>= 1) {
+            a.x += __shfl_down(a.x, sh, 64);
+            a.y += __shfl_down(a.y, sh, 64);
+          }
+          if (lane == 0) {
+            dst[0] = (double)fmaf((float)c_end, P[g][n].x, a.x);
+            dst[1] = (double)fmaf((float)c_end, P[g][n].y, a.y);
+          }
+        } else {
+          double2 a = acc[g];
+#pragma unroll
+          for (int sh = 32; sh > 0; sh >>= 1) {
+            a.x += __shfl_down(a.x, sh, 64);
+            a.y += __shfl_down(a.y, sh, 64);
+          }
+          if (lane == 0) {
+            dst[0] = fma(c_end, (double)P[g][n].x, a.x);
+            dst[1] = fma(c_end, (double)P[g][n].y, a.y);
+          }
         }
       }
     }

@@ -39,13 +39,19 @@ struct Ramp64 {
 };
 
 // The ramp of the tap `tap` chips from the prompt one (-el_spacing, 0, +el_spacing; any offset for the bank).  The prompt tap's
-// + 0.0 changes no value.
+// + 0.0 changes no value.  The end the second half is built from is MATLAB's: c = a + (N-1)*sp, and the written end point b in its
+// place only when c - b > -tol, tol = 2 eps max(|a|, |b|).  Where rem and tap nearly cancel, a and b carry the rounding of
+// intermediates many times their size and c < b - tol: the colon then ends at c, a few 1e-14 before b, and a sample on a table edge
+// gets the other index (tests/test_bank_edges_cpu.py).  A colon with N - 1 elements is outside every definition that uses this ramp.
 __device__ __forceinline__ Ramp64 ramp64(double rem, double tap, double step, double R, int N) {
   Ramp64 r;
   r.N = N;
   r.sp = __dmul_rn(step, R);
   r.a = __dmul_rn(__dadd_rn(rem, tap), R);
-  r.b = __dmul_rn(__dadd_rn(__dadd_rn(__dmul_rn((double)(N - 1), step), rem), tap), R);
+  const double b = __dmul_rn(__dadd_rn(__dadd_rn(__dmul_rn((double)(N - 1), step), rem), tap), R);
+  const double c = __dadd_rn(r.a, __dmul_rn((double)(N - 1), r.sp));
+  const double tol = __dmul_rn(2.0 * 2.220446049250313e-16, fmax(fabs(r.a), fabs(b)));
+  r.b = __dadd_rn(c, -b) > -tol ? b : c;
   return r;
 }
 

@@ -164,6 +164,11 @@ int gc_correlate(gc_context* ctx, int nblocks, const gc_block* blocks, double* o
  * (tracking.m:263-270; o = -d, 0, +d are the early, prompt and late ramps bit for bit), carrier and sums as gc_correlate.
  * The padded table of n entries is read PERIODICALLY - index p = ceil(t*m_a), 0-based as in gc_correlate (MATLAB's p + 1), reads entry 1 + mod(p - 1, n - 2) - so
  * offsets of several chips, negative phases and blocks longer than a code period are legal.  el_spacing is ignored.
+ * The ramp is MATLAB's colon a : d : b, its end-point rule included: element i is a + i*d below the middle and c - (N-1-i)*d above
+ * it, where c = a + (N-1)*d, and c = b only if c - b > -2 eps max(|a|, |b|) - which fails where rem and o_j nearly cancel (rem about
+ * a code period, o_j about minus one) and a, b carry the rounding of much larger intermediates.  A descriptor whose colon has N - 1
+ * elements for a tap (a + (N-1)*d - b > 2 eps max(|a|, |b|): tracking.m would stop on the size mismatch) is outside this definition;
+ * it is not refused, and what is returned for it is not specified.
  * Synchronous, float32 kernels, bitwise reproducible; the library may walk the list in sub-batches of blocks.
  * Accepted: what gc_correlate asks of a descriptor without its three conditions on el_spacing and the table's end, and instead
  *   1 <= ntaps <= GC_BANK_MAX_TAPS, finite offsets (any order, duplicates allowed) with |o_j| * R * m_a < n_a - 2 for every arm,

@@ -66,6 +66,55 @@ def _colon_has_n_elements(d, o, r=1.0):
     return O.colon((rem + o) * r, step * r, (((n - 1) * step + rem) + o) * r).shape[0] == n
 
 
+def ramp_model(rem, o, step, n, r=1.0, matlab_end=True):
+    """csrc/replica_f64.h restated in numpy, every operation rounded by itself: ramp64's start, end and spacing, then colon_at's
+    element i - forwards from the start below the middle, backwards from the end above it, the mean of both in the middle.
+    matlab_end: the end point is MATLAB's (c = a + (N-1)*sp, snapped to b when c - b > -tol); False: b itself, as ramp64 took it
+    before the tap bank's edge sweep."""
+    f = np.float64
+    rem, o, step, r = f(rem), f(o), f(step), f(r)
+    sp = step * r
+    a = (rem + o) * r
+    b = (((f(n - 1) * step) + rem) + o) * r
+    if matlab_end:
+        c = a + f(n - 1) * sp
+        tol = 2.0 * np.finfo(np.float64).eps * max(abs(a), abs(b))
+        b = b if c - b > -tol else c
+    i = np.arange(n, dtype=np.int64)
+    back = n - 1 - i
+    fi, fb = i.astype(np.float64), back.astype(np.float64)
+    return np.where(i < back, a + fi * sp, np.where(i > back, b - fb * sp, (a + b) / 2.0))
+
+
+def ramp_index(t, mult=1.0):
+    """code_step of csrc/replica_f64.h: ceil(fl(t * arm_mult))."""
+    return np.ceil(np.asarray(t, dtype=np.float64) * np.float64(mult)).astype(np.int64)
+
+
+def oracle_ramp(rem, o, step, n, r=1.0):
+    """The definition's ramp of a tap: MATLAB's colon, as `reference` takes it (N or N - 1 elements)."""
+    return O.colon((rem + o) * r, step * r, (((n - 1) * step + rem) + o) * r)
+
+
+def bank_refusal(tables_len, mult, r, n, rem, step, offsets):
+    """bank_validate's numeric conditions (csrc/bank_plan.h) restated, in its order: the status name a descriptor is refused with
+    and the class of the refusal, or None where the library accepts it.  tables_len: entries of each arm's padded table."""
+    omax = max(abs(float(o)) for o in offsets)
+    for nent, m in zip(tables_len, mult):
+        if not omax * r * m < float(nent - 2):
+            return "GC_E_INVALID", "period"
+    if not (n >= 1 and step > 0 and rem > -1.0 and math.isfinite(rem)):
+        return "GC_E_INVALID", "descriptor"
+    rate = step * r * max(max(mult), 1.0)
+    if rate > 1.0:
+        return "GC_E_UNSUPPORTED", "rate_high"
+    if not rate >= 1.0 / 65536.0:
+        return "GC_E_INVALID", "rate_low"
+    if not ((float(n) * step + abs(rem) + omax) * r * max(max(mult), 1.0)) < 2147483000.0:
+        return "GC_E_INVALID", "int32"
+    return None
+
+
 def _blocks(engine, descs, df=None):
     """The descriptors of a call; `df`: carr_freq replaced by the float64 sum carr_freq + df (None: carr_freq as it is)."""
     b = engine.make_blocks(len(descs))

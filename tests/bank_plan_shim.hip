@@ -59,6 +59,15 @@ void bank_shim_set_channel(void* vctx, int channel, int arms, int nent, int wind
   }
 }
 
+// ... and then the channel's index scale, and one arm's table length (pads included) and ramp multiplier
+void bank_shim_set_ramp(void* vctx, int channel, double index_scale, int arm, int nent, double mult) {
+  HostChannel& c = static_cast<gc_context*>(vctx)->ch[channel];
+  c.index_scale = index_scale;
+  c.nent[arm] = nent;
+  c.mult[arm] = mult;
+  c.h_tab[arm].assign((size_t)nent, (int8_t)1);
+}
+
 // gc_correlate_bank (freqs == nullptr) and gc_correlate_ddm up to the first device call
 int bank_shim_check(void* ctx, int nblocks, const gc_block* blocks, int ntaps, const double* taps, int nfreq, const double* freqs) {
   int arms = 1;
