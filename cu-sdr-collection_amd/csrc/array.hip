@@ -14,8 +14,9 @@
 //                     passes of a lag meet in LDS, and one 64-bit integer atomic per output and workgroup adds them into one of
 //                     kArrCovSlots copies, which the host adds.  Integer sums: the order changes nothing.
 // array_combine_kernel  ddc_kernel's shape at D = 1 (ddc.hip): the K T weights as double2 in LDS, kArrChains independent add chains
-//                     that share every broadcast weight read, a ascending and k ascending within it, the per-output finish written
-//                     out here without the NCO (fir_common.h says why it is no function), wave_sum and the slotted counters.
+//                     that share every broadcast weight read, a ascending and k ascending within it, then fir_common.h's per-output
+//                     finish without the NCO and its hand-over of the two counters.
+// The staging of a span and the read of a staged sample are fir_common.h's too; the tile and its span are fir_plan.h's at D = 1.
 // The unit's buffers are its own (ArrState, kept in gc_context::arr of srcs[0], grow-only, released by gc_destroy).
 #include "array_plan.h"
 #include "fir_common.h"
@@ -36,7 +37,7 @@ struct ArrArgs {
   long long src_bytes[kArrK];    // of each record: samples * bytes per sample
   uint8_t* dst;                  // combine
   const double* weights;         // combine: [K][T][2]
-  unsigned long long* out;       // covariance: [kArrCovSlots][L][K][K][2]; combine: [kArrCovSlots]{clipped, sum_sq}.  Workgroup b adds to slot b mod kArrCovSlots
+  unsigned long long* out;       // covariance: [kArrCovSlots][L][K][K][2], workgroup b adds to copy b mod kArrCovSlots; combine: [kFirStatSlots]{clipped, sum_sq} (fir_common.h)
   long long first, n, dst_first;
   int nrecords, ntaps, tile;     // ntaps: T, or L
   int rec_bytes;                 // LDS bytes of one record's span
@@ -45,43 +46,17 @@ struct ArrArgs {
 
 // the K spans of the tile into `vecs`; returns the byte offset in the record of the first staged vector
 template <int MODE>
-__device__ __forceinline__ long long stage_spans(const ArrArgs& p, const ArrTile& tile, uint4* vecs) {
+__device__ __forceinline__ long long stage_spans(const ArrArgs& p, const FirTile& tile, uint4* vecs) {
   using F = Fmt<MODE>;
-  const long long base16 = arr_stage_base(tile.n_lo, F::bps);
-  const int nvec = (int)arr_stage_vecs(tile.n_lo, tile.n_hi, F::bps);  // <= (span * bps + 15 + 15 + 15) / 16: inside rec_bytes
+  const long long base16 = fir_stage_base(tile.n_lo, F::bps);
+  const int nvec = (int)fir_stage_vecs(tile.n_lo, tile.n_hi, F::bps);  // <= (span * bps + 15 + 15 + 15) / 16: inside rec_bytes
   const int rec_vecs = p.rec_bytes / 16;
   for (int a = 0; a < p.nrecords; ++a) {
     const uint8_t* const rec = p.src[a];
     const long long nbytes = p.src_bytes[a];
-    for (int i = (int)threadIdx.x; i < nvec; i += kArrWG) {
-      RecVec<MODE> q;
-      q.load(rec, base16 + 16LL * i, nbytes);
-      vecs[a * rec_vecs + i] = q.words();
-    }
+    stage_span<MODE, kArrWG>(rec, nbytes, base16, nvec, vecs + a * rec_vecs);
   }
   return base16;
-}
-
-// staged_sample (fir_common.h) as integers
-template <int MODE>
-__device__ __forceinline__ void staged_ints(const uint8_t* lds, int off, int& re, int& im) {
-  using F = Fmt<MODE>;
-  int v0, v1 = 0;
-  if constexpr (F::values == 2 && F::value_bytes == 1) {
-    const unsigned int w = *(const unsigned short*)(lds + off);
-    v0 = (int)(signed char)(w & 0xffu);
-    v1 = (int)(signed char)(w >> 8);
-  } else if constexpr (F::values == 2) {
-    const unsigned int w = *(const unsigned int*)(lds + off);
-    v0 = (int)(short)(w & 0xffffu);
-    v1 = (int)(short)(w >> 16);
-  } else if constexpr (F::value_bytes == 1) {
-    v0 = (int)*(const signed char*)(lds + off);
-  } else {
-    v0 = (int)*(const short*)(lds + off);
-  }
-  re = F::swap ? v1 : v0;
-  im = F::swap ? v0 : v1;
 }
 
 // The sums over the wave of v[0 .. 2 W): a step at lane distance d adds the pairs of lanes d apart, the lower lane going on with
@@ -121,7 +96,7 @@ __global__ __launch_bounds__(kArrWG) void array_cov_kernel(const ArrArgs p) {
   const int tid = (int)threadIdx.x, lane = tid & 63, K = p.nrecords, L = p.ntaps;
   const uint8_t* const bytes = reinterpret_cast<const uint8_t*>(arr_lds);
 
-  const ArrTile tile = arr_tile(p.tile, (long long)blockIdx.x, p.first, p.n, L);
+  const FirTile tile = fir_tile(p.tile, (long long)blockIdx.x, p.first, p.n, 1, L);
   const int cnt = (int)tile.n;  // >= 1: the grid is ceil(n / tile)
   const long long base16 = stage_spans<MODE>(p, tile, arr_lds);
   __syncthreads();
@@ -174,13 +149,12 @@ template <int MODE>
 __global__ __launch_bounds__(kArrWG) void array_combine_kernel(const ArrArgs p) {
   using F = Fmt<MODE>;
   extern __shared__ uint4 arr_lds[];
-  __shared__ unsigned long long wave_part[kArrWG / 64][2];
   const int tid = (int)threadIdx.x, K = p.nrecords, T = p.ntaps;
   double2* const wts = reinterpret_cast<double2*>(arr_lds);  // 16 K T bytes
   uint4* const vecs = arr_lds + K * T;
   const uint8_t* const bytes = reinterpret_cast<const uint8_t*>(vecs);
 
-  const ArrTile tile = arr_tile(p.tile, (long long)blockIdx.x, p.first, p.n, T);
+  const FirTile tile = fir_tile(p.tile, (long long)blockIdx.x, p.first, p.n, 1, T);
   const long long m0 = tile.m0;
   const int cnt = (int)tile.n;  // >= 1: the grid is ceil(noutputs / tile)
   const long long base16 = stage_spans<MODE>(p, tile, vecs);
@@ -219,47 +193,13 @@ __global__ __launch_bounds__(kArrWG) void array_combine_kernel(const ArrArgs p) 
   }
 
   unsigned long long clipped = 0ull, sum_sq = 0ull;
-  const int dmode = p.dst_mode;
-  const bool d16 = dmode == I16_IQ || dmode == I16_QI || dmode == I16_REAL, dreal = dmode == I8_REAL || dmode == I16_REAL;
-  const bool dswap = dmode == I8_QI || dmode == I16_QI;
-  const double lo = d16 ? -32768.0 : -128.0, hi = d16 ? 32767.0 : 127.0;
 #pragma unroll
   for (int j = 0; j < kArrChains; ++j) {
     const int q = tid + j * kArrWG;
     if (q >= cnt) continue;
-    const double rr = rint(ar[j]), ri = rint(ai[j]);
-    const long long o_re = (long long)fmin(fmax(rr, lo), hi), o_im = (long long)fmin(fmax(ri, lo), hi);
-    clipped += (rr < lo || rr > hi) ? 1ull : 0ull;
-    sum_sq += (unsigned long long)(o_re * o_re);
-    if (!dreal) {
-      clipped += (ri < lo || ri > hi) ? 1ull : 0ull;
-      sum_sq += (unsigned long long)(o_im * o_im);
-    }
-    const long long s = p.dst_first + m0 + q;
-    const int o0 = (int)(dswap ? o_im : o_re), o1 = (int)(dswap ? o_re : o_im);
-    if (dreal) {
-      if (d16) reinterpret_cast<short*>(p.dst)[s] = (short)o0;
-      else reinterpret_cast<signed char*>(p.dst)[s] = (signed char)o0;
-    } else if (d16) {
-      reinterpret_cast<uint32_t*>(p.dst)[s] = ((uint32_t)o0 & 0xffffu) | ((uint32_t)o1 << 16);
-    } else {
-      reinterpret_cast<unsigned short*>(p.dst)[s] = (unsigned short)(((uint32_t)o0 & 0xffu) | (((uint32_t)o1 & 0xffu) << 8));
-    }
+    fir_finish<false>(ar[j], ai[j], 0ull, p.dst_mode, p.dst, p.dst_first + m0 + q, clipped, sum_sq);
   }
-  clipped = wave_sum(clipped);
-  sum_sq = wave_sum(sum_sq);
-  if ((tid & 63) == 0) {
-    wave_part[tid >> 6][0] = clipped;
-    wave_part[tid >> 6][1] = sum_sq;
-  }
-  __syncthreads();
-  if (tid == 0) {  // one pair of integer atomics per workgroup, spread over kArrCovSlots addresses: adds to one address queue up
-    clipped = sum_sq = 0ull;
-    for (int w = 0; w < kArrWG / 64; ++w) clipped += wave_part[w][0], sum_sq += wave_part[w][1];
-    unsigned long long* const slot = p.out + 2 * (blockIdx.x % kArrCovSlots);
-    if (clipped) atomicAdd(&slot[0], clipped);
-    if (sum_sq) atomicAdd(&slot[1], sum_sq);
-  }
+  fir_hand_over<kArrWG / 64>(clipped, sum_sq, p.out);
 }
 
 // what both drivers do after an accepted check: the device, the other streams' pending work, the records into the arguments
@@ -354,11 +294,10 @@ extern "C" int gc_array_combine(gc_context* const* srcs, gc_context* dst, const 
   ArrState* s = gc_unit_state<ArrState>(s0->arr);
   if (!s) return gc_nomem("gc_array_combine");
   const size_t w_bytes = (size_t)K * T * 2 * sizeof(double);
-  if (gc_buf_reserve(s->weights, w_bytes, false) != hipSuccess ||
-      gc_buf_reserve(s->stats, sizeof(unsigned long long[kArrCovSlots][2]), false) != hipSuccess)
-    return gc_nomem("gc_array_combine");
+  if (gc_buf_reserve(s->weights, w_bytes, false) != hipSuccess) return gc_nomem("gc_array_combine");
+  rc = fir_stats_begin("gc_array_combine", s->stats, s0->stream);
+  if (rc) return rc;
   GC_HIP(hipMemcpyAsync(s->weights.p, weights, w_bytes, hipMemcpyHostToDevice, s0->stream));
-  GC_HIP(hipMemsetAsync(s->stats.p, 0, sizeof(unsigned long long[kArrCovSlots][2]), s0->stream));
   a.weights = (const double*)s->weights.p;
   a.out = (unsigned long long*)s->stats.p;
   a.first = (long long)p->first_sample;
@@ -369,10 +308,9 @@ extern "C" int gc_array_combine(gc_context* const* srcs, gc_context* dst, const 
     hipLaunchKernelGGL(array_combine_kernel<decltype(m)::value>, dim3((unsigned int)pl.ntiles), dim3(kArrWG), (size_t)pl.lds_bytes, s0->stream, a);
   });
   GC_HIP(hipGetLastError());
-  unsigned long long slots[kArrCovSlots][2], host[2] = {0ull, 0ull};
-  GC_HIP(hipMemcpyAsync(slots, s->stats.p, sizeof slots, hipMemcpyDeviceToHost, s0->stream));
-  GC_HIP(hipStreamSynchronize(s0->stream));
-  for (int i = 0; i < kArrCovSlots; ++i) host[0] += slots[i][0], host[1] += slots[i][1];
+  unsigned long long host[2];
+  rc = fir_stats_end(s->stats, s0->stream, host);
+  if (rc) return rc;
   if (res) {
     res->clipped = (int64_t)host[0];
     res->sum_sq = host[1];

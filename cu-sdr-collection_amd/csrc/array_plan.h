@@ -1,12 +1,11 @@
 // array_plan.h — what the driver of the antenna-array unit (array.hip: gc_array_covariance, gc_array_combine) decides on the host: the
 // argument checks of both calls, the tile of consecutive samples a workgroup takes with each record's staged span and the LDS bytes
-// that go with it, the walk of the tiles over a range, and the constants that bound the covariance kernel's narrow accumulators.
+// that go with it, the walk of the tiles over a range, and the constants that bound the covariance kernel's narrow accumulators.  The
+// tile's span and its staging are fir_plan.h's, shared with the down-converter and the resampler.
 // Nothing here calls HIP, allocates on the device or launches; tests/array_plan_shim.hip runs all of it without a device.  From the
 // contexts the checks read d_if, device, if_nsamples, if_dtype and if_layout.
 #pragma once
-#include <cstdint>
-
-#include "record_check.h"
+#include "fir_plan.h"
 
 constexpr int kArrWG = 256;                 // threads of a workgroup
 constexpr int kArrChains = 4;               // samples a thread carries at most: the combine's independent float64 add chains, the covariance's samples per pass
@@ -17,20 +16,17 @@ constexpr long long kArrLdsBudget = 56 * 1024;
 // next to it, outside the budget: per wave the 2 K sums of K passes as 8-byte integers (covariance); the waves' two counters (combine)
 constexpr long long kArrStaticLds = (long long)(kArrWG / 64) * GC_ARRAY_MAX_RECORDS * 2 * GC_ARRAY_MAX_RECORDS * 8;
 static_assert(kArrLdsBudget + kArrStaticLds <= 64 * 1024, "a launch gets 64 KB of LDS without asking for more");
-constexpr int kArrMaxBps = 4;               // bytes per sample of the widest format: the tile is sized for it, whatever the records hold
-// A span is staged in whole 16-byte vectors of the record from the vector that holds its first byte: up to 15 bytes in front, 15 behind
-constexpr long long kArrStageSlack = 32;
 // The covariance of int8 records adds in int32 up to the wave's sum of a pass: a pass of the whole workgroup adds at most kArrMaxTile
 // samples, each two products of at most 128^2 = 2^14 in magnitude.  int16 records add in int64 throughout (a product pair reaches
 // 2^31).
 constexpr long long kArrCovI32Cap = kArrMaxTile;
 static_assert(kArrCovI32Cap * 2 * 128 * 128 < (1LL << 31), "an int8 pass stays inside int32");
 constexpr long long kArrCovMaxSamples = 1LL << 31;  // 2^31 samples * 2 products * 2^30 = 2^62: every int16 sum stays inside 63 bits
-constexpr int kArrCovSlots = 64;            // copies of the covariance (and of the combine's two counters) the workgroups add into; the host adds them
+constexpr int kArrCovSlots = 64;            // copies of the covariance the workgroups add into; the host adds them (the combine's two counters: fir_common.h)
 
 inline long long arr_weights_bytes(int nrecords, int ntaps) { return 16LL * nrecords * ntaps; }
 // LDS bytes of one record's span under `tile` consecutive samples with T - 1 samples of lead-in, at `bps` bytes per sample
-inline long long arr_rec_bytes(long long tile, int ntaps, int bps) { return ((tile + ntaps - 1) * bps + kArrStageSlack + 15) / 16 * 16; }
+inline long long arr_rec_bytes(long long tile, int ntaps, int bps) { return ((tile + ntaps - 1) * bps + kFirStageSlack + 15) / 16 * 16; }
 // LDS bytes of a tile: (combine) the weights, then the K spans
 inline long long arr_lds_bytes(long long tile, int nrecords, int ntaps, int bps, bool weights) {
   return (weights ? arr_weights_bytes(nrecords, ntaps) : 0) + nrecords * arr_rec_bytes(tile, ntaps, bps);
@@ -41,11 +37,11 @@ inline long long arr_lds_bytes(long long tile, int nrecords, int ntaps, int bps,
 inline long long arr_tile_outputs(int nrecords, int ntaps) {
   if (nrecords < 1 || nrecords > GC_ARRAY_MAX_RECORDS || ntaps < 1 || ntaps > GC_ARRAY_MAX_TAPS) return 0;
   const long long per_rec = (kArrLdsBudget - arr_weights_bytes(nrecords, ntaps)) / nrecords / 16 * 16;
-  long long tile = (per_rec - kArrStageSlack - 15) / kArrMaxBps - (ntaps - 1);
+  long long tile = (per_rec - kFirStageSlack - 15) / kFirMaxBps - (ntaps - 1);
   if (tile > kArrMaxTile) tile = kArrMaxTile;
   return tile;
 }
-static_assert(((kArrLdsBudget - 16LL * GC_ARRAY_MAX_RECORDS * GC_ARRAY_MAX_TAPS) / GC_ARRAY_MAX_RECORDS / 16 * 16 - kArrStageSlack - 15) / kArrMaxBps -
+static_assert(((kArrLdsBudget - 16LL * GC_ARRAY_MAX_RECORDS * GC_ARRAY_MAX_TAPS) / GC_ARRAY_MAX_RECORDS / 16 * 16 - kFirStageSlack - 15) / kFirMaxBps -
                       (GC_ARRAY_MAX_TAPS - 1) >= kArrMaxTile,
               "the largest (K, T) takes a full tile");
 
@@ -59,35 +55,13 @@ struct ArrPlan {
   int src_bps = 0, dst_bps = 0;  // dst_bps: 0 for the covariance
 };
 
-// Tile t of the walk: samples [m0, m0 + n) of the range, record samples [n_lo, n_hi] (n_lo may be negative: zeros).  The kernels stage
-// what these three functions say (they are the kernels' own arithmetic: array.hip calls them on the device): base = the byte offset
-// in the record, a multiple of 16 and possibly negative, of the vector that holds n_lo's first byte; vecs = the 16-byte vectors from
-// there to the one that holds n_hi's last byte.
-struct ArrTile {
-  long long m0 = 0, n = 0, n_lo = 0, n_hi = 0;
-};
-__host__ __device__ inline ArrTile arr_tile(long long tile, long long t, long long first_sample, long long nsamples, int ntaps) {
-  ArrTile r;
-  r.m0 = t * tile;
-  r.n = tile < nsamples - r.m0 ? tile : nsamples - r.m0;
-  r.n_lo = first_sample + r.m0 - (ntaps - 1);
-  r.n_hi = first_sample + r.m0 + r.n - 1;
-  return r;
-}
-__host__ __device__ inline long long arr_stage_base(long long n_lo, int bps) {
-  const long long b = n_lo * bps;
-  return (b >= 0 ? b / 16 : -((-b + 15) / 16)) * 16;
-}
-__host__ __device__ inline long long arr_stage_vecs(long long n_lo, long long n_hi, int bps) {
-  return ((n_hi + 1) * bps - arr_stage_base(n_lo, bps) + 15) / 16;
-}
-inline bool arr_tile_at(const ArrPlan& pl, long long first_sample, long long nsamples, int ntaps, long long t, ArrTile* out) {
+// Tile t of the walk: samples [m0, m0 + n) of the range, record samples [n_lo, n_hi] (n_lo may be negative: zeros) - fir_plan.h's
+// tile at a decimation of 1, which array.hip calls on the device and stages with fir_stage_base and fir_stage_vecs
+inline bool arr_tile_at(const ArrPlan& pl, long long first_sample, long long nsamples, int ntaps, long long t, FirTile* out) {
   if (t < 0 || t >= pl.ntiles) return false;
-  *out = arr_tile(pl.tile, t, first_sample, nsamples, ntaps);
+  *out = fir_tile(pl.tile, t, first_sample, nsamples, 1, ntaps);
   return true;
 }
-
-inline bool arr_finite(double v) { return v - v == 0.0; }
 
 // What both calls ask of their records, in the order of include/gnsscorr.h: one device, one source format, (dst) no overlap with a
 // source - GC_E_INVALID; a record everywhere - GC_E_STATE; [first, first + n) inside every source and [dst_first, dst_first + n)
@@ -108,18 +82,12 @@ inline int arr_check_records(const char* fn, gc_context* const* srcs, int K, con
       gc_set_error("%s: source %d differs from source 0 in dtype or layout", fn, a);
       return GC_E_INVALID;
     }
-  if (dst && dst->d_if) {
-    const uint64_t dbytes = dst->if_nsamples * (uint64_t)gc_record_bps(dst);
-    for (int a = 0; a < K; ++a) {
-      const gc_context* s = srcs[a];
-      if (!s->d_if) continue;
-      const uint64_t sbytes = s->if_nsamples * (uint64_t)gc_record_bps(s);
-      if (dst->d_if == s->d_if || (dst->d_if < s->d_if + sbytes && s->d_if < dst->d_if + dbytes)) {
+  if (dst && dst->d_if)
+    for (int a = 0; a < K; ++a)
+      if (srcs[a]->d_if && gc_records_overlap(dst, srcs[a])) {
         gc_set_error("%s: the destination record is source %d's or overlaps it", fn, a);
         return GC_E_INVALID;
       }
-    }
-  }
   for (int a = 0; a < K; ++a)
     if (!srcs[a]->d_if) {
       gc_set_error("%s: source %d has no IF record loaded", fn, a);
@@ -198,7 +166,7 @@ inline int arr_combine_check(gc_context* const* srcs, const gc_context* dst, con
     return GC_E_INVALID;
   }
   for (int k = 0; k < 2 * p->nrecords * p->ntaps; ++k)
-    if (!arr_finite(weights[k])) {
+    if (!fir_finite(weights[k])) {
       gc_set_error("gc_array_combine: weight %d of record %d is not finite", k / 2 % p->ntaps, k / 2 / p->ntaps);
       return GC_E_INVALID;
     }

@@ -1,11 +1,17 @@
-// record_check.h — what the record-to-record calls (gc_cancel, gc_excise_pulses, gc_excise_bins, gc_downconvert) and the probe ask of
-// their records on the host, once.  Nothing here calls HIP; the plan headers include it, and with them the CPU shims under tests/.
+// record_check.h — what the record-to-record calls (gc_cancel, gc_excise_pulses, gc_excise_bins, gc_downconvert, gc_resample,
+// gc_array_combine) and the probe ask of their records on the host, once.  Nothing here calls HIP; the plan headers include it, and with them the CPU shims under tests/.
 #pragma once
 #include <cstdint>
 
 #include "gc_internal.h"
 
 inline int gc_record_bps(const gc_context* c) { return gc_bytes_per_sample(c->if_dtype, c->if_layout); }
+
+// a's record is b's or shares bytes with it (both hold one)
+inline bool gc_records_overlap(const gc_context* a, const gc_context* b) {
+  const uint64_t abytes = a->if_nsamples * (uint64_t)gc_record_bps(a), bbytes = b->if_nsamples * (uint64_t)gc_record_bps(b);
+  return a->d_if == b->d_if || (a->d_if < b->d_if + bbytes && b->d_if < a->d_if + abytes);
+}
 
 // A source and the destination that takes its place: GC_E_STATE without a record on either side, GC_E_INVALID for a destination that
 // differs from the source in device, sample count, dtype or layout, or overlaps it without being it
@@ -18,8 +24,7 @@ inline int check_record_pair(const char* fn, const gc_context* src, const gc_con
     gc_set_error("%s: the destination record differs from the source's in device, sample count, dtype or layout", fn);
     return GC_E_INVALID;
   }
-  const uint64_t bytes = src->if_nsamples * (uint64_t)gc_record_bps(src);
-  if (dst->d_if != src->d_if && dst->d_if < src->d_if + bytes && src->d_if < dst->d_if + bytes) {
+  if (dst->d_if != src->d_if && gc_records_overlap(dst, src)) {
     gc_set_error("%s: the destination record overlaps the source without being the same record", fn);
     return GC_E_INVALID;
   }

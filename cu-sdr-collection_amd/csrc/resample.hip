@@ -15,8 +15,8 @@
 //            them; the zero taps at the end of a short row add +-0.
 //   finish   per output, and the result: ddc.hip's, with the tick in place of the sample index.
 // An output depends on its samples and on u_m only; the tile decides nothing but who computes it.
-// staged_sample and wave_sum are ddc.hip's (fir_common.h); the finish is written out in both units, because as a shared function it
-// changed the order of ddc_kernel's instructions.
+// The staging, the read of a staged sample, the finish and the hand-over of the result are fir_common.h's, shared with ddc.hip and
+// array.hip.
 // The unit's buffers are its own (RsState, kept in gc_context::rs, grow-only, released by gc_destroy).
 #include <new>
 #include <vector>
@@ -29,8 +29,6 @@ using namespace gcorr;
 
 namespace {
 
-constexpr int kRsStatSlots = 64;
-
 struct RsState {  // grow-only device buffers of the context (released by gc_destroy)
   GcBuf taps, stats;
 };
@@ -39,7 +37,7 @@ struct RsArgs {
   const uint8_t* src;
   uint8_t* dst;
   const double2* taps;         // [L][row]: phase-major, zero-padded
-  unsigned long long* stats;   // [kRsStatSlots]{clipped, sum_sq}: workgroup b adds to slot b mod kRsStatSlots, the host adds the slots
+  unsigned long long* stats;   // [kFirStatSlots]{clipped, sum_sq} (fir_common.h)
   long long first_tick, nout, dst_first;
   long long src_bytes;         // of the record: samples * bytes per sample
   unsigned long long phase_step, phase0;
@@ -52,7 +50,6 @@ template <int MODE>
 __global__ __launch_bounds__(kRsWG) void rs_kernel(const RsArgs p) {
   using F = Fmt<MODE>;
   extern __shared__ uint4 rs_lds[];
-  __shared__ unsigned long long wave_part[kRsWG / 64][2];
   const int tid = (int)threadIdx.x, L = p.interp, M = p.decim, J = p.branches;
   const int ntap = L * p.row;                                  // staged (re, im) pairs: 16 bytes each
   double2* const taps = reinterpret_cast<double2*>(rs_lds);
@@ -61,14 +58,10 @@ __global__ __launch_bounds__(kRsWG) void rs_kernel(const RsArgs p) {
 
   const RsTile tile = rs_tile(p.tile, (long long)blockIdx.x, p.first_tick, p.nout, L, M, p.ntaps);
   const int cnt = (int)tile.n;  // >= 1: the grid is ceil(nout / tile)
-  const long long base16 = ddc_stage_base(tile.n_lo, F::bps);
-  const int nvec = (int)ddc_stage_vecs(tile.n_lo, tile.n_hi, F::bps);  // <= (span * bps + 15 + 15) / 16: inside rs_lds_bytes
+  const long long base16 = fir_stage_base(tile.n_lo, F::bps);
+  const int nvec = (int)fir_stage_vecs(tile.n_lo, tile.n_hi, F::bps);  // <= (span * bps + 15 + 15) / 16: inside rs_lds_bytes
 
-  for (int i = tid; i < nvec; i += kRsWG) {
-    RecVec<MODE> q;
-    q.load(p.src, base16 + 16LL * i, p.src_bytes);
-    vecs[i] = q.words();
-  }
+  stage_span<MODE, kRsWG>(p.src, p.src_bytes, base16, nvec, vecs);
   for (int k = tid; k < ntap; k += kRsWG) taps[k] = p.taps[k];
   __syncthreads();
 
@@ -107,54 +100,14 @@ __global__ __launch_bounds__(kRsWG) void rs_kernel(const RsArgs p) {
   }
 
   unsigned long long clipped = 0ull, sum_sq = 0ull;
-  const int dmode = p.dst_mode;
-  const bool d16 = dmode == I16_IQ || dmode == I16_QI || dmode == I16_REAL, dreal = dmode == I8_REAL || dmode == I16_REAL;
-  const bool dswap = dmode == I8_QI || dmode == I16_QI;
-  const double lo = d16 ? -32768.0 : -128.0, hi = d16 ? 32767.0 : 127.0;
 #pragma unroll
   for (int c = 0; c < kRsChains; ++c) {
     const int q = tid + c * stride;
     if (tid >= stride || q >= cnt) continue;
     const unsigned long long u = (unsigned long long)(tile.u0 + (long long)q * M);
-    const unsigned long long phs = p.phase0 + p.phase_step * u;
-    const double ang = (double)(long long)phs * (kDdcTwoPi * 0x1p-64);  // the product of the constants is exact
-    double sn, cs;
-    sincos(ang, &sn, &cs);
-    const double yr = cs * ar[c] + sn * ai[c];
-    const double yi = cs * ai[c] - sn * ar[c];
-    const double rr = rint(yr), ri = rint(yi);
-    const long long o_re = (long long)fmin(fmax(rr, lo), hi), o_im = (long long)fmin(fmax(ri, lo), hi);
-    clipped += (rr < lo || rr > hi) ? 1ull : 0ull;
-    sum_sq += (unsigned long long)(o_re * o_re);
-    if (!dreal) {
-      clipped += (ri < lo || ri > hi) ? 1ull : 0ull;
-      sum_sq += (unsigned long long)(o_im * o_im);
-    }
-    const long long s = p.dst_first + tile.m0 + q;
-    const int o0 = (int)(dswap ? o_im : o_re), o1 = (int)(dswap ? o_re : o_im);
-    if (dreal) {
-      if (d16) reinterpret_cast<short*>(p.dst)[s] = (short)o0;
-      else reinterpret_cast<signed char*>(p.dst)[s] = (signed char)o0;
-    } else if (d16) {
-      reinterpret_cast<uint32_t*>(p.dst)[s] = ((uint32_t)o0 & 0xffffu) | ((uint32_t)o1 << 16);
-    } else {
-      reinterpret_cast<unsigned short*>(p.dst)[s] = (unsigned short)(((uint32_t)o0 & 0xffu) | (((uint32_t)o1 & 0xffu) << 8));
-    }
+    fir_finish<true>(ar[c], ai[c], p.phase0 + p.phase_step * u, p.dst_mode, p.dst, p.dst_first + tile.m0 + q, clipped, sum_sq);
   }
-  clipped = wave_sum(clipped);
-  sum_sq = wave_sum(sum_sq);
-  if ((tid & 63) == 0) {
-    wave_part[tid >> 6][0] = clipped;
-    wave_part[tid >> 6][1] = sum_sq;
-  }
-  __syncthreads();
-  if (tid == 0) {  // one pair of integer atomics per workgroup, spread over kRsStatSlots addresses
-    clipped = sum_sq = 0ull;
-    for (int w = 0; w < kRsWG / 64; ++w) clipped += wave_part[w][0], sum_sq += wave_part[w][1];
-    unsigned long long* const slot = p.stats + 2 * (blockIdx.x % kRsStatSlots);
-    if (clipped) atomicAdd(&slot[0], clipped);
-    if (sum_sq) atomicAdd(&slot[1], sum_sq);
-  }
+  fir_hand_over<kRsWG / 64>(clipped, sum_sq, p.stats);
 }
 
 }  // namespace
@@ -172,7 +125,7 @@ extern "C" long long gc_debug_rs_tile_outputs(int interp, int decim, int ntaps) 
 
 extern "C" int gc_resample(gc_context* src, gc_context* dst, const gc_rs_params* p, const double* taps, gc_rs_result* res) {
   RsPlan pl;
-  const int rc = rs_check(src, dst, p, taps, &pl);
+  int rc = rs_check(src, dst, p, taps, &pl);
   if (rc) return rc;
   if (pl.ntiles > 0x7fffffffLL) {
     gc_set_error("gc_resample: %lld tiles in one call", pl.ntiles);
@@ -198,10 +151,10 @@ extern "C" int gc_resample(gc_context* src, gc_context* dst, const gc_rs_params*
   RsState* s = gc_unit_state<RsState>(src->rs);
   if (!s) return gc_nomem("gc_resample");
   const size_t taps_bytes = rows.size() * sizeof(double);
-  if (gc_buf_reserve(s->taps, taps_bytes, false) != hipSuccess || gc_buf_reserve(s->stats, sizeof(unsigned long long[kRsStatSlots][2]), false) != hipSuccess)
-    return gc_nomem("gc_resample");
+  if (gc_buf_reserve(s->taps, taps_bytes, false) != hipSuccess) return gc_nomem("gc_resample");
+  rc = fir_stats_begin("gc_resample", s->stats, src->stream);
+  if (rc) return rc;
   GC_HIP(hipMemcpyAsync(s->taps.p, rows.data(), taps_bytes, hipMemcpyHostToDevice, src->stream));
-  GC_HIP(hipMemsetAsync(s->stats.p, 0, sizeof(unsigned long long[kRsStatSlots][2]), src->stream));
   RsArgs a;
   a.src = src->d_if;
   a.dst = dst->d_if;
@@ -225,10 +178,9 @@ extern "C" int gc_resample(gc_context* src, gc_context* dst, const gc_rs_params*
     hipLaunchKernelGGL(rs_kernel<decltype(m)::value>, dim3((unsigned int)pl.ntiles), dim3(kRsWG), (size_t)pl.lds_bytes, src->stream, a);
   });
   GC_HIP(hipGetLastError());
-  unsigned long long slots[kRsStatSlots][2], host[2] = {0ull, 0ull};
-  GC_HIP(hipMemcpyAsync(slots, s->stats.p, sizeof slots, hipMemcpyDeviceToHost, src->stream));
-  GC_HIP(hipStreamSynchronize(src->stream));  // also: `rows` is read by the copy above until here
-  for (int i = 0; i < kRsStatSlots; ++i) host[0] += slots[i][0], host[1] += slots[i][1];
+  unsigned long long host[2];
+  rc = fir_stats_end(s->stats, src->stream, host);  // synchronises; `rows` is read by the copy above until then
+  if (rc) return rc;
   if (res) {
     res->phase_step = pl.phase_step;
     res->phase0 = pl.phase0;

@@ -1,8 +1,9 @@
 // resample_plan.h — what the driver of the resampler (resample.hip: gc_resample) decides on the host: the argument checks, the NCO's
 // two integers, the branches J of the polyphase filter, the tile of consecutive outputs a workgroup takes with the input span and the
 // LDS bytes that go with it, and the walk of the tiles over noutputs.  Nothing here calls HIP, allocates on the device or launches;
-// tests/resample_plan_shim.hip runs all of it without a device.  phase0, the finiteness test, the record range and the staging of a
-// span in whole 16-byte vectors are the down-converter's (ddc_plan.h); with L = 1 the tile is ddc_tile_outputs(M, T).
+// tests/resample_plan_shim.hip runs all of it without a device.  The NCO's integers, the finiteness test, the checks of the two records
+// and the staging of a span in whole 16-byte vectors are fir_plan.h's; the workgroup's shape and the LDS budget are the
+// down-converter's (ddc_plan.h), and with L = 1 the tile is ddc_tile_outputs(M, T).
 #pragma once
 #include "ddc_plan.h"
 
@@ -44,7 +45,7 @@ inline long long rs_span(long long outs, int interp, int decim, int ntaps) {
   return ((outs - 1) * decim + (interp - 1)) / interp + rs_branches(interp, ntaps);
 }
 inline long long rs_lds_bytes(long long outs, int interp, int decim, int ntaps, int bps) {
-  return rs_taps_bytes(interp, ntaps) + (rs_span(outs, interp, decim, ntaps) * bps + kDdcStageSlack + 15) / 16 * 16;
+  return rs_taps_bytes(interp, ntaps) + (rs_span(outs, interp, decim, ntaps) * bps + kFirStageSlack + 15) / 16 * 16;
 }
 inline bool rs_accepts(int interp, int decim, int ntaps) {
   return interp >= 1 && interp <= GC_RS_MAX_INTERP && decim >= 1 && decim <= GC_DDC_MAX_DECIM * interp && ntaps >= 1 && ntaps <= GC_RS_MAX_TAPS;
@@ -53,15 +54,15 @@ inline bool rs_accepts(int interp, int decim, int ntaps) {
 // is not accepted
 inline long long rs_tile_outputs(int interp, int decim, int ntaps) {
   if (!rs_accepts(interp, decim, ntaps)) return 0;
-  const long long span_max = (kRsLdsBudget - rs_taps_bytes(interp, ntaps) - kDdcStageSlack - 15) / kDdcMaxBps;
+  const long long span_max = (kRsLdsBudget - rs_taps_bytes(interp, ntaps) - kFirStageSlack - 15) / kFirMaxBps;
   long long outs = (span_max - rs_branches(interp, ntaps)) * interp / decim + 1;
   const long long most = (long long)kRsChains * rs_stride(interp, decim);
   return outs > most ? most : outs;
 }
 // one output fits whatever is accepted: the rows hold fewer than T + 2 L taps (J L < T + L, and one tap per row of padding), a branch
 // at most T samples
-static_assert((kRsLdsBudget - 16LL * (GC_RS_MAX_TAPS + 2 * GC_RS_MAX_INTERP) - kDdcStageSlack - 15) / kDdcMaxBps >= GC_RS_MAX_TAPS, "one output of the longest filter fits");
-static_assert((kRsLdsBudget - 16LL * GC_RS_MAX_INTERP * ((GC_RS_MAX_TAPS / GC_RS_MAX_INTERP) | 1) - kDdcStageSlack - 15) / kDdcMaxBps >= GC_RS_MAX_TAPS / GC_RS_MAX_INTERP,
+static_assert((kRsLdsBudget - 16LL * (GC_RS_MAX_TAPS + 2 * GC_RS_MAX_INTERP) - kFirStageSlack - 15) / kFirMaxBps >= GC_RS_MAX_TAPS, "one output of the longest filter fits");
+static_assert((kRsLdsBudget - 16LL * GC_RS_MAX_INTERP * ((GC_RS_MAX_TAPS / GC_RS_MAX_INTERP) | 1) - kFirStageSlack - 15) / kFirMaxBps >= GC_RS_MAX_TAPS / GC_RS_MAX_INTERP,
               "one output fits at the corner L = 64, T = 2048");
 
 struct RsPlan {
@@ -80,8 +81,8 @@ struct RsPlan {
 };
 
 // Tile t of the walk: outputs [m0, m0 + n), the first one at tick u0 = n0 L + p0, input samples [n_lo, n_hi] (n_lo may be negative,
-// n_hi may lie beyond the record: zeros).  The kernel calls rs_tile and rs_output on the device, and stages with ddc_stage_base and
-// ddc_stage_vecs.
+// n_hi may lie beyond the record: zeros).  The kernel calls rs_tile and rs_output on the device, and stages with fir_stage_base and
+// fir_stage_vecs.
 struct RsTile {
   long long m0 = 0, n = 0, u0 = 0, n0 = 0, n_lo = 0, n_hi = 0;
   int p0 = 0;
@@ -117,41 +118,19 @@ inline int rs_check(const gc_context* src, const gc_context* dst, const gc_rs_pa
     return GC_E_INVALID;
   }
   if (p->first_tick < 0 || p->dst_first < 0 || p->noutputs < 1 || !rs_accepts(p->interp, p->decim, p->ntaps) || p->reserved != 0 ||
-      !ddc_finite(p->carr_freq) || !ddc_finite(p->carr_phase)) {
+      !fir_finite(p->carr_freq) || !fir_finite(p->carr_phase)) {
     gc_set_error("gc_resample: bad arguments (first_tick %lld, noutputs %lld, dst_first %lld, interp %d, decim %d, ntaps %d, reserved %d, carr_freq %g, carr_phase %g)",
                  (long long)p->first_tick, (long long)p->noutputs, (long long)p->dst_first, p->interp, p->decim, p->ntaps, p->reserved, p->carr_freq, p->carr_phase);
     return GC_E_INVALID;
   }
   for (int k = 0; k < 2 * p->ntaps; ++k)
-    if (!ddc_finite(taps[k])) {
+    if (!fir_finite(taps[k])) {
       gc_set_error("gc_resample: tap %d is not finite", k / 2);
       return GC_E_INVALID;
     }
-  if (!src->d_if || !dst->d_if) {
-    gc_set_error("gc_resample: no IF record loaded");
-    return GC_E_STATE;
-  }
-  if (!(src->fs > 0.0)) {
-    gc_set_error("gc_resample: the source's sampling frequency is not set");
-    return GC_E_STATE;
-  }
   const double tick_rate = src->fs * (double)p->interp;
   uint64_t step = 0;
-  if (!(std::fabs(p->carr_freq) < src->fs / 2.0) || !ddc_phase_step(p->carr_freq, tick_rate, &step)) {
-    gc_set_error("gc_resample: |carr_freq| %g is not below half the sampling frequency %g", p->carr_freq, src->fs);
-    return GC_E_INVALID;
-  }
-  if (dst->device != src->device) {
-    gc_set_error("gc_resample: the destination is on another device");
-    return GC_E_INVALID;
-  }
-  const int sb = gc_record_bps(src), db = gc_record_bps(dst);
-  const uint64_t sbytes = src->if_nsamples * (uint64_t)sb, dbytes = dst->if_nsamples * (uint64_t)db;
-  if (dst->d_if == src->d_if || (dst->d_if < src->d_if + sbytes && src->d_if < dst->d_if + dbytes)) {
-    gc_set_error("gc_resample: the destination record is the source's or overlaps it");
-    return GC_E_INVALID;
-  }
-  const int rc = check_record_range("gc_resample (destination)", dst, (long long)p->dst_first, (long long)p->noutputs);
+  const int rc = fir_check_records("gc_resample", src, dst, p->carr_freq, tick_rate, (long long)p->dst_first, (long long)p->noutputs, &step);
   if (rc) return rc;
   // here, where dst's record bounds noutputs, not among the arguments: up to here every status is gc_downconvert's for the same call
   const __int128 last_tick = (__int128)p->first_tick + (__int128)(p->noutputs - 1) * p->decim;
@@ -167,15 +146,15 @@ inline int rs_check(const gc_context* src, const gc_context* dst, const gc_rs_pa
   }
   RsPlan q;
   q.phase_step = step;
-  q.phase0 = ddc_phase0(p->carr_phase);
-  q.carr_freq = ddc_nco_freq(step, tick_rate);
+  q.phase0 = fir_phase0(p->carr_phase);
+  q.carr_freq = fir_nco_freq(step, tick_rate);
   q.out_rate = tick_rate / (double)p->decim;
   q.tile = rs_tile_outputs(p->interp, p->decim, p->ntaps);
   q.ntiles = ((long long)p->noutputs + q.tile - 1) / q.tile;
   q.span = rs_span(q.tile, p->interp, p->decim, p->ntaps);
-  q.src_bps = sb;
-  q.dst_bps = db;
-  q.lds_bytes = rs_lds_bytes(q.tile, p->interp, p->decim, p->ntaps, sb);
+  q.src_bps = gc_record_bps(src);
+  q.dst_bps = gc_record_bps(dst);
+  q.lds_bytes = rs_lds_bytes(q.tile, p->interp, p->decim, p->ntaps, q.src_bps);
   q.lds_budget = kRsLdsBudget;
   q.branches = J;
   q.row = rs_row(p->interp, p->ntaps);

@@ -452,24 +452,25 @@ class Engine:
         return int(L.load().gc_debug_excise_tile_segments(int(nfft)))
 
     @staticmethod
-    def _ddc_taps(taps) -> np.ndarray:
-        """downconvert()'s taps as contiguous float64 [T, 2] = (re, im); ValueError for anything but a [T] real or complex array or a
-        [T][2] real one with 1 <= T <= GC_DDC_MAX_TAPS - before any library call."""
+    def _ddc_taps(taps, call="downconvert()") -> np.ndarray:
+        """The taps of downconvert() or resample() (`call`, for the messages) as contiguous float64 [T, 2] = (re, im); ValueError for
+        anything but a [T] real or complex array or a [T][2] real one with 1 <= T <= GC_DDC_MAX_TAPS - before any library call."""
         g = np.asarray(taps)
         numeric = np.issubdtype(g.dtype, np.floating) or np.issubdtype(g.dtype, np.integer)
         if g.ndim == 1 and (numeric or np.issubdtype(g.dtype, np.complexfloating)):
             g = g.astype(np.complex128)
             g = np.stack([g.real, g.imag], axis=-1)
         elif not (g.ndim == 2 and g.shape[1] == 2 and numeric):
-            raise ValueError(f"downconvert(): taps must be [T] complex or [T][2] real, not {g.dtype} {g.shape}")
+            raise ValueError(f"{call}: taps must be [T] complex or [T][2] real, not {g.dtype} {g.shape}")
         if not 1 <= g.shape[0] <= L.GC_DDC_MAX_TAPS:
-            raise ValueError(f"downconvert(): 1 .. {L.GC_DDC_MAX_TAPS} taps, not {g.shape[0]}")
+            raise ValueError(f"{call}: 1 .. {L.GC_DDC_MAX_TAPS} taps, not {g.shape[0]}")
         return np.ascontiguousarray(g, dtype=np.float64)
 
     @staticmethod
-    def _ddc_whole(name, v, bits):
+    def _whole(call, name, v, bits):
+        """Argument `name` of `call` as an int; ValueError for anything but a whole number of `bits` bits - before any library call."""
         if isinstance(v, (bool, str, bytes)) or v is None or v != int(v) or not -(1 << (bits - 1)) <= int(v) < 1 << (bits - 1):
-            raise ValueError(f"downconvert(): {name} must be a whole number of {bits} bits, not {v!r}")
+            raise ValueError(f"{call}: {name} must be a whole number of {bits} bits, not {v!r}")
         return int(v)
 
     def downconvert(self, dst: "Engine", taps, decim: int, carr_freq: float = 0.0, carr_phase: float = 0.0, first_sample: int = 0,
@@ -480,15 +481,15 @@ class Engine:
         layout).  noutputs=None: every output that still has a record sample under it, up to dst's capacity.
         Returns SimpleNamespace(phase_step, phase0, clipped, sum_sq, carr_freq, noutputs) (include/gnsscorr.h)."""
         g = self._ddc_taps(taps)
-        d = self._ddc_whole("decim", decim, 32)
-        first = self._ddc_whole("first_sample", first_sample, 64)
-        dfirst = self._ddc_whole("dst_first", dst_first, 64)
+        d = self._whole("downconvert()", "decim", decim, 32)
+        first = self._whole("downconvert()", "first_sample", first_sample, 64)
+        dfirst = self._whole("downconvert()", "dst_first", dst_first, 64)
         if noutputs is None:
             _, have = self.if_buffer()
             _, room = dst.if_buffer()
             nout = min((int(have) + g.shape[0] - 2 - first) // max(d, 1) + 1, int(room) - dfirst)
         else:
-            nout = self._ddc_whole("noutputs", noutputs, 64)
+            nout = self._whole("downconvert()", "noutputs", noutputs, 64)
         p = L.gc_ddc_params(first, nout, dfirst, d, g.shape[0], float(carr_freq), float(carr_phase))
         r = L.gc_ddc_result()
         L.check(self._lib.gc_downconvert(self._ctx, dst._ctx, C.byref(p), g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)))
@@ -508,15 +509,12 @@ class Engine:
         same device; any sample count, dtype and layout).  noutputs=None: every output that still has a record sample under it, up to
         dst's capacity.  With interp == 1 it is downconvert().
         Returns SimpleNamespace(phase_step, phase0, clipped, sum_sq, carr_freq, out_rate, noutputs) (include/gnsscorr.h)."""
-        try:
-            g = self._ddc_taps(taps)
-            li =self._ddc_whole("interp", interp, 32)
-            d = self._ddc_whole("decim", decim, 32)
-            first = self._ddc_whole("first_tick", first_tick, 64)
-            dfirst = self._ddc_whole("dst_first", dst_first, 64)
-            nout = None if noutputs is None else self._ddc_whole("noutputs", noutputs, 64)
-        except ValueError as e:
-            raise ValueError(str(e).replace("downconvert()", "resample()")) from None
+        g = self._ddc_taps(taps, "resample()")
+        li = self._whole("resample()", "interp", interp, 32)
+        d = self._whole("resample()", "decim", decim, 32)
+        first = self._whole("resample()", "first_tick", first_tick, 64)
+        dfirst = self._whole("resample()", "dst_first", dst_first, 64)
+        nout = None if noutputs is None else self._whole("resample()", "noutputs", noutputs, 64)
         if not 1 <= li <= L.GC_RS_MAX_INTERP:
             raise ValueError(f"resample(): interp must lie in 1 .. {L.GC_RS_MAX_INTERP}, not {li}")
         if not 1 <= d <= L.GC_DDC_MAX_DECIM * li:
@@ -536,12 +534,6 @@ class Engine:
     def debug_rs_tile_outputs(interp: int, decim: int, ntaps: int) -> int:
         """gc_debug_rs_tile_outputs (test hook, host code only): outputs a workgroup of resample() takes; 0 for a refused (interp, decim, ntaps)."""
         return int(L.load().gc_debug_rs_tile_outputs(int(interp), int(decim), int(ntaps)))
-
-    @staticmethod
-    def _array_whole(name, v, bits):
-        if isinstance(v, (bool, str, bytes)) or v is None or v != int(v) or not -(1 << (bits - 1)) <= int(v) < 1 << (bits - 1):
-            raise ValueError(f"array: {name} must be a whole number of {bits} bits, not {v!r}")
-        return int(v)
 
     @staticmethod
     def _array_records(records):
@@ -575,9 +567,9 @@ class Engine:
         of the K engines `records` (one device, one dtype and layout) and the lags 0 .. nlags-1, in exact integers.
         Returns int64 [L, K, K, 2] = (re, im) (include/gnsscorr.h)."""
         recs, ctxs = Engine._array_records(records)
-        first = Engine._array_whole("first_sample", first_sample, 64)
-        n = Engine._array_whole("nsamples", nsamples, 64)
-        lags = Engine._array_whole("nlags", nlags, 32)
+        first = Engine._whole("array", "first_sample", first_sample, 64)
+        n = Engine._whole("array", "nsamples", nsamples, 64)
+        lags = Engine._whole("array", "nlags", nlags, 32)
         if not 1 <= lags <= L.GC_ARRAY_MAX_TAPS:
             raise ValueError(f"array_covariance(): nlags must lie in 1 .. {L.GC_ARRAY_MAX_TAPS}, not {lags}")
         p = L.gc_array_cov_params(first, n, len(recs), lags)
@@ -593,12 +585,12 @@ class Engine:
         sides hold.  Returns SimpleNamespace(clipped, sum_sq, noutputs) (include/gnsscorr.h)."""
         recs, ctxs = Engine._array_records(records)
         w = Engine._array_weights(weights, len(recs))
-        first = Engine._array_whole("first_sample", first_sample, 64)
-        dfirst = Engine._array_whole("dst_first", dst_first, 64)
+        first = Engine._whole("array", "first_sample", first_sample, 64)
+        dfirst = Engine._whole("array", "dst_first", dst_first, 64)
         if noutputs is None:
             nout = min(min(int(r.if_buffer()[1]) for r in recs) - first, int(dst.if_buffer()[1]) - dfirst)
         else:
-            nout = Engine._array_whole("noutputs", noutputs, 64)
+            nout = Engine._whole("array", "noutputs", noutputs, 64)
         p = L.gc_array_combine_params(first, nout, dfirst, len(recs), w.shape[1])
         r = L.gc_array_combine_result()
         L.check(recs[0]._lib.gc_array_combine(ctxs, dst._ctx, C.byref(p), w.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)))

@@ -67,7 +67,7 @@ long long arr_shim_walk(long long first_sample, long long nsamples, int nrecords
   if (pl.tile < 1) return 0;
   pl.ntiles = (nsamples + pl.tile - 1) / pl.tile;
   long long n = 0;
-  ArrTile t;
+  FirTile t;
   for (long long i = 0; arr_tile_at(pl, first_sample, nsamples, ntaps, i, &t); ++i)
     for (long long v : {t.m0, t.n, t.n_lo, t.n_hi}) {
       if (n < cap) out[n] = v;
@@ -78,8 +78,8 @@ long long arr_shim_walk(long long first_sample, long long nsamples, int nrecords
 
 // what the kernels stage of one record for the samples [n_lo, n_hi]: out = {byte offset of the first vector, vectors}
 void arr_shim_stage(long long n_lo, long long n_hi, int bps, long long* out) {
-  out[0] = arr_stage_base(n_lo, bps);
-  out[1] = arr_stage_vecs(n_lo, n_hi, bps);
+  out[0] = fir_stage_base(n_lo, bps);
+  out[1] = fir_stage_vecs(n_lo, n_hi, bps);
 }
 
 void arr_shim_constants(long long* out) {
@@ -90,7 +90,7 @@ void arr_shim_constants(long long* out) {
   out[4] = kArrStaticLds;
   out[5] = GC_ARRAY_MAX_RECORDS;
   out[6] = GC_ARRAY_MAX_TAPS;
-  out[7] = kArrStageSlack;
+  out[7] = kFirStageSlack;
   out[8] = kArrCovI32Cap;
   out[9] = kArrCovMaxSamples;
   out[10] = kArrCovSlots;

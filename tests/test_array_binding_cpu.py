@@ -132,7 +132,7 @@ def test_engine_array_calls_refuse_what_does_not_fit_before_any_library_call():
     assert w.dtype == np.float64 and w.flags.c_contiguous and w.tolist() == [[[1.0, 0.0]], [[0.0, 2.0]]]
     assert E._array_weights(np.array([[1, 2j, 3], [0.5 - 0.25j, 0, 0]]), 2).tolist() == [[[1, 0], [0, 2], [3, 0]], [[0.5, -0.25], [0, 0], [0, 0]]]
     assert E._array_weights(np.ones((8, 32, 2)), 8).shape == (8, 32, 2)
-    assert E._array_whole("nsamples", 7.0, 64) == 7 and E._array_whole("first_sample", -1, 64) == -1   # the library's to refuse
+    assert E._whole("array", "nsamples", 7.0, 64) == 7 and E._whole("array", "first_sample", -1, 64) == -1   # the library's to refuse
 
 
 def test_mex_gateway_lists_and_handles_the_commands():

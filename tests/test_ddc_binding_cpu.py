@@ -110,7 +110,7 @@ def test_engine_downconvert_refuses_taps_and_numbers_that_do_not_fit_before_any_
     assert g.dtype == np.float64 and g.flags.c_contiguous and g.tolist() == [[1.0, 0.0], [0.0, 2.0], [0.5, -0.25]]
     assert P.Engine._ddc_taps([[1, 2], [3, 4]]).tolist() == [[1.0, 2.0], [3.0, 4.0]]          # [T][2] real
     assert P.Engine._ddc_taps(np.ones(2048)).shape == (2048, 2)
-    assert P.Engine._ddc_whole("decim", 7.0, 32) == 7 and P.Engine._ddc_whole("decim", -1, 32) == -1   # the library's to refuse
+    assert P.Engine._whole("downconvert()", "decim", 7.0, 32) == 7 and P.Engine._whole("downconvert()", "decim", -1, 32) == -1   # the library's to refuse
 
 
 def test_mex_gateway_lists_and_handles_the_command():
