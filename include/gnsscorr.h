@@ -807,7 +807,9 @@ long long gc_debug_probe_tile_segments(int nfft);
  * the rule above, not on the other blocks of the call.  The same input gives the same bytes.  The context's precision setting is
  * ignored: float64 always.
  * Accepted: what gc_correlate asks of a descriptor with el_spacing ignored (taken as 0); the blocks in any order; at most
- * GC_CANCEL_MAX_CHANNELS distinct channels per call.  GC_E_INVALID for two blocks of one channel that overlap, a dst record that
+ * GC_CANCEL_MAX_CHANNELS distinct channels per call.  Any finite carr_freq is accepted, but where carr_freq * 2.0 or its product
+ * with pi leaves the float64 range (|carr_freq| above about 2.8e307) trig_i is infinite or NaN and the output of the samples the
+ * block covers, and its projected amplitude, are unspecified (the call still returns GC_OK and writes inside the record only).  GC_E_INVALID for two blocks of one channel that overlap, a dst record that
  * differs from src's in device, sample count, dtype or layout (or overlaps it without being it), an unknown mode, a non-finite amp_in
  * of an arm the block's channel has, null src, dst, or blocks with nblocks > 0; GC_E_RANGE / GC_E_STATE as gc_correlate (GC_E_STATE
  * also for a dst without a record).  A refused call writes nothing.  nblocks == 0 is GC_OK: a plain copy (SUBTRACT) or zeros (MODEL). */

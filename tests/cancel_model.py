@@ -2,8 +2,15 @@
 by itself, as the header asks.  What may differ from the library: one ulp in each of sin and cos, and the order of additions in P.
 
 A channel is a dict {"tables": [int arrays], "r": index_scale, "mult": [arm_mult]}; a block a dict {"ch": channel index, "s0", "n",
-"rem", "step", "f", "phi"} and optionally "off": [table_offset per arm]."""
+"rem", "step", "f", "phi"} and optionally "off": [table_offset per arm].
+
+The code ramp is csrc/replica_f64.h's, restated in bank_cases.ramp_model: the colon's element rule with MATLAB's end point (c = a +
+(N-1)*sp, the written end point b in its place only where c - b > -tol).  Where MATLAB's colon of the block has N elements
+(oracle_ok) that ramp is the colon element for element (tests/test_cancel_edges_cpu.py); a block whose colon has N - 1 elements is
+outside the definition."""
 import numpy as np
+
+from bank_cases import oracle_ramp, ramp_index, ramp_model
 
 REAL, IQ, QI = 0, 1, 2
 HALF_EPS = 1e-9          # a sample whose value lies this close to a half-integer may round either way
@@ -25,28 +32,32 @@ def pack(re, im, dtype, layout):
     return out
 
 
-def replica(blk, chan, fs):
-    """(sn, cs, c[arms, N]) of a block: the carrier and every arm's code on its N samples."""
+def oracle_ok(blk, chan):
+    """MATLAB's colon of the block's ramp has N elements: the definition covers the block."""
+    return oracle_ramp(float(blk["rem"]), 0.0, float(blk["step"]), int(blk["n"]), float(chan["r"])).shape[0] == int(blk["n"])
+
+
+def replica(blk, chan, fs, matlab_end=True):
+    """(sn, cs, c[arms, N]) of a block: the carrier and every arm's code on its N samples.  matlab_end=False: the ramp's second half
+    from the written end point b, as this model took it before the tap bank's edge sweep."""
     n, rem, step, r = int(blk["n"]), float(blk["rem"]), float(blk["step"]), float(chan["r"])
     i = np.arange(n, dtype=np.float64)
     trig = ((blk["f"] * 2.0) * np.pi) * (i / fs) + blk["phi"]
     sn, cs = np.sin(trig), np.cos(trig)
-    a, sp = rem * r, step * r
-    b = ((n - 1) * step + rem) * r
-    k2 = 2 * np.arange(n)
-    t = np.where(k2 < n - 1, a + i * sp, np.where(k2 > n - 1, b - (n - 1 - i) * sp, (a + b) / 2.0))     # the colon's element rule
-    off = blk.get("off", [0] * len(chan["tables"]))
+    t = ramp_model(rem, 0.0, step, n, r, matlab_end=matlab_end)                                        # the colon's element rule
+    off = blk.get("off") or [0] * len(chan["tables"])
     c = np.empty((len(chan["tables"]), n))
     for arm, tab in enumerate(chan["tables"]):
-        k = np.ceil(t * float(chan["mult"][arm])).astype(np.int64) + int(off[arm])
+        k = ramp_index(t, float(chan["mult"][arm])) + int(off[arm])
         c[arm] = np.asarray(tab, dtype=np.float64)[np.clip(k, 0, len(tab) - 1)]
     return sn, cs, c
 
 
-def project(re, im, blk, chan, fs):
-    """(P complex [arms], E int [arms], sum |re| + |im| over the block) of one block on the record (re, im)."""
+def project(re, im, blk, chan, fs, rep=None):
+    """(P complex [arms], E int [arms], sum |re| + |im| over the block) of one block on the record (re, im); rep: the block's
+    replica() where the caller has it."""
     s0, n = int(blk["s0"]), int(blk["n"])
-    sn, cs, c = replica(blk, chan, fs)
+    sn, cs, c = replica(blk, chan, fs) if rep is None else rep
     x_re, x_im = re[s0:s0 + n], im[s0:s0 + n]
     ib = cs * x_re + sn * x_im
     qb = cs * x_im - sn * x_re
@@ -55,8 +66,10 @@ def project(re, im, blk, chan, fs):
     return P, E, float(np.sum(np.abs(x_re) + np.abs(x_im)))
 
 
-def cancel(raw, dtype, layout, blocks, chans, fs, amp=None, mode="subtract"):
+def cancel(raw, dtype, layout, blocks, chans, fs, amp=None, mode="subtract", reps=None):
     """gc_cancel on the record `raw` (file order, integer dtype).  amp: complex [nblocks, 3] or None (the projection).
+    reps: a dict the replicas of `blocks` are kept in from one call to the next on the same list (they do not depend on the record,
+    the amplitudes or the mode), or None.
     Returns (out record, amp used complex [nblocks, 3], P [nblocks, 3], E [nblocks, 3], sum|x| [nblocks],
     near: bool per sample - a component within HALF_EPS of a half-integer, covered: bool per sample)."""
     re, im = components(raw, layout)
@@ -71,11 +84,18 @@ def cancel(raw, dtype, layout, blocks, chans, fs, amp=None, mode="subtract"):
         chan = chans[blk["ch"]]
         arms = len(chan["tables"])
         s0, n = int(blk["s0"]), int(blk["n"])
-        sn, cs, c = replica(blk, chan, fs)
-        P, E, sx[k] = project(re, im, blk, chan, fs)
+        if reps is None or k not in reps:
+            rep = replica(blk, chan, fs)
+            if reps is not None:
+                reps[k] = rep
+        else:
+            rep = reps[k]
+        sn, cs, c = rep
+        P, E, sx[k] = project(re, im, blk, chan, fs, rep)
         P_all[k, :arms], E_all[k, :arms] = P, E
         if amp is None:
-            used[k, :arms] = [P[a] / E[a] if E[a] else 0.0 for a in range(arms)]
+            # per component, one division each (a complex quotient would multiply by 1 / E: an ulp off now and then)
+            used[k, :arms] = [complex(P[a].real / float(E[a]), P[a].imag / float(E[a])) if E[a] else 0.0 for a in range(arms)]
         else:
             used[k, :arms] = np.asarray(amp)[k, :arms]
         b_re, b_im = np.zeros(n), np.zeros(n)
