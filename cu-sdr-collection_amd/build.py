@@ -66,7 +66,7 @@ LIBS = {
     "libgnsscorr_tuning.so": [_tuned(u) for u in _CORR_UNITS],
     "libgnsssynth.so": ["synth.hip"],
 }
-HEADERS = ["gc_internal.h", "corr_common.h", "record_fmt.h", "record_check.h", "replica_f64.h", "launch_plan.h", "bank_plan.h", "probe_plan.h", "excise_plan.h", "fir_plan.h", "ddc_plan.h", "resample_plan.h", "array_plan.h", "fir_common.h", "devloop.h", "acq_guard.h", "shift_pick.h", "acq_internal.h", "fft_plan.h", "seg_fft.h", os.path.join("..", "..", "include", "gnsscorr.h")]
+HEADERS = ["gc_internal.h", "corr_common.h", "record_fmt.h", "record_check.h", "replica_f64.h", "launch_plan.h", "track_plan.h", "bank_plan.h", "probe_plan.h", "excise_plan.h", "fir_plan.h", "ddc_plan.h", "resample_plan.h", "array_plan.h", "fir_common.h", "devloop.h", "acq_guard.h", "shift_pick.h", "acq_internal.h", "fft_plan.h", "seg_fft.h", os.path.join("..", "..", "include", "gnsscorr.h")]
 # --offload-compress: the gfx950 code objects inside the fat binary are zstd-compressed (10.1 -> ~1.6 MB; the HIP runtime inflates them
 # when the library is loaded: ~20 ms once per process)
 FLAGS = ["--offload-arch=gfx950", "--offload-compress", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",

@@ -3,7 +3,7 @@
 // gc_plan_launch.  Built by tests/test_launch_plan_cpu.py with the flags of corr_kernel.hip; no GPU is touched.
 #include <cstdarg>
 
-#include "../cu-sdr-collection_amd/csrc/launch_plan.h"
+#include "../cu-sdr-collection_amd/csrc/track_plan.h"  // launch_plan.h + the closed loops' planners
 
 void gc_set_error(const char*, ...) {}
 
@@ -101,6 +101,30 @@ void plan_shim_plan_epoch(void* vctx, int nb, const gc_block* blocks, int splits
   LaunchPlan p;
   if ((o->status = gc_plan_launch(ctx, s, nb, splits, gc_epoch_polled(ctx, s, polled != 0), &p)) != GC_OK) return;
   put(o, p);
+}
+
+// ... and the splits gc_track gives that launch (gc_plan_track_host, track_plan.h) when the epoch's blocks are its channels' first:
+// blocks of `code_length` chips of a code of rate `code_freq_basis`, the channels' code frequencies taken back from the blocks' steps
+int plan_shim_track_splits(void* vctx, int nb, const gc_block* blocks, double sampling_freq, double code_freq_basis, double code_length) {
+  const gc_context* ctx = static_cast<const gc_context*>(vctx);
+  LaunchScope s;
+  ChannelMix mix;
+  std::vector<gc_channel_init> init((size_t)nb);
+  for (int k = 0; k < nb; ++k) {
+    gc_scope_add_channel(s, ctx->ch[blocks[k].channel]);
+    mix.add(ctx->ch[blocks[k].channel]);
+    init[k] = gc_channel_init();
+    init[k].channel = blocks[k].channel;
+    init[k].code_freq = blocks[k].code_phase_step * sampling_freq;
+  }
+  gc_scope_set_level(ctx, s, mix, 2);
+  gc_track_params p = gc_track_params();
+  p.sampling_freq = sampling_freq;
+  p.code_freq_basis = code_freq_basis;
+  p.code_length = code_length;
+  p.el_spacing = blocks[0].el_spacing;
+  p.n_epochs = 1;
+  return gc_plan_track_host(ctx, s, mix, p, nb, init.data(), false, TrackKnobs()).splits;
 }
 
 }  // extern "C"

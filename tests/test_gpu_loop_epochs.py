@@ -13,7 +13,7 @@ teacher-forced with the loop's own recorded sums, so each epoch is judged on the
 a. all 16 scenes of ref_scenes.TRACK_SCENES on the host loop and the device loop; GPS L1 C/A also with a launch per epoch and with
    three host threads (tuning build); the Galileo E1-C CBOC pilot (fold 5) across one C/N0 interval.
 b. the team sizes the shipping library picks.  Two levers only, channel count and block length; the compute-unit count comes from
-   engine.device_info() and the expected team from the formulae of csrc/track.hip, mirrored below and held against
+   engine.device_info() and the expected team from the formulae of csrc/track_plan.h, mirrored in tests/track_teams.py and held against
    gc_debug_last_track_team.  Fast device loop: ceil(4 CU / nch) over six values from 256 channels (4 on 256 CUs) to 32; blocks so
    short that chunks / 32 limits the team to 1, 2, 3, 6, 12.  The fast kernel needs more than 7 samples per chip, so a 1023-chip
    block never has fewer than 28 teams' worth of chunks: the short blocks are the first 50 .. 400 chips of the C/A code at 16 and
@@ -51,6 +51,7 @@ import pytest
 import loop_epochs as LE
 import ref_scenes as RS
 import test_gpu_ref_vectors as TRV
+from track_teams import _fast_device_team, _fast_host_team, _halvings, _lane_device_team, _lowrate
 from oracle import gnss_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -154,30 +155,8 @@ def test_every_epoch_of_the_cboc_pilot_loop(engine, device_loop):
 
 
 # ---- b. team sizes -----------------------------------------------------------------------------------------------------------------
-# csrc/launch_plan.h gc_block_lowrate_level and csrc/track.hip's team formulae, restated: what the accessor must report
-def _lowrate(step):
-    return 2 if 15.0 * step < 0.995 else 1 if 7.0 * step < 0.995 else 0
-
-
-def _fast_device_team(cu, nch, S, i8c=True):
-    lr = _lowrate(S.codeFreqBasis * 1.001 / S.samplingFreq)
-    assert lr > 0, "not a rate the fast kernel accepts"
-    spl = 16 if (lr == 2 and i8c) else 8
-    chunks = int(S.codeLength / (S.codeFreqBasis / S.samplingFreq) / spl) + 1
-    return max(1, min(32, (4 * cu + nch - 1) // nch, max(1, chunks // 32)))
-
-
-def _fast_host_team(cu, nch, S):
-    lr = _lowrate(S.codeFreqBasis * 1.001 / S.samplingFreq)
-    assert lr > 0, "not a rate the fast kernel accepts"
-    approx_chunks = int(S.codeLength / (S.codeFreqBasis / S.samplingFreq) / 8.0) + 1
-    return max(1, min(32, (4 * cu + nch - 1) // nch, max(1, approx_chunks * 8 // (16 if lr == 2 else 8) // 48)))
-
-
-def _lane_device_team(cu, nch, arms, blksize):
-    return max(1, min({1: 8, 2: 6}[arms], blksize // (64 * 8 * 2), max(1, 2 * cu // nch)))
-
-
+# csrc/launch_plan.h gc_block_lowrate_level and csrc/track_plan.h's team formulae, restated in tests/track_teams.py: what the accessor
+# must report
 def _channels(S, nch, span, code_freq=False):
     """nch channels over four PRNs, first blocks on every residue mod 16, acquiredFreq spread over +-5 kHz."""
     ch = []
@@ -206,14 +185,6 @@ def _ca_rig(chips, spc, n_ep):
                             carrier_phase=float(rng.uniform(0, 6.28)), cn0_dbhz=47.0) for p in PRNS]
     iq = P.synth.generate_if(sats, int((n_ep + 2.5) * 1e-3 * fs), fs, S.IF, lambda prn: P.codes.generateCAcode(prn)[:chips], S.codeFreqBasis, chips, seed=7)
     return S, iq
-
-
-def _halvings(team):
-    """A team and what gc_track / gc_track_device make of it while the persistent grid is not resident whole: halved until it fits."""
-    chain = [team]
-    while chain[-1] > 1:
-        chain.append((chain[-1] + 1) // 2)
-    return chain
 
 
 def _team_case(engine, name, S, rec, ch, signal, spec, device_loop, want_team, want_kernel, layout=RS.GC_IQ):

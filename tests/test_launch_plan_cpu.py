@@ -54,6 +54,7 @@ def _shim(tuning=False):
     lib.plan_shim_set_channel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]
     lib.plan_shim_plan.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Out)]
     lib.plan_shim_plan_epoch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(Out)]
+    lib.plan_shim_track_splits.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_double] * 3
     _LIBS[tuning] = lib
     return lib
 
@@ -92,6 +93,10 @@ class Ctx:
         o = Out()
         self.lib.plan_shim_plan(self.p, b.shape[0], b.ctypes.data, int(replay), splits, int(polled), C.byref(o))
         return o
+
+    def track_splits(self, b, fs, rate, chips):
+        """The splits gc_track's planner (csrc/track_plan.h) gives the launch per epoch of these channels' first blocks."""
+        return self.lib.plan_shim_track_splits(self.p, b.shape[0], b.ctypes.data, fs, rate, chips)
 
     def plan_epoch(self, b, splits, polled=True):
         o = Out()
@@ -287,8 +292,10 @@ def test_float64_precision_always_plans_the_float64_kernel():
         ctx.channel(1, nent=[2048, 2048, 12278], R=2.0, mult=[1.0, 1.0, 6.0], six_fold=True)
         step = 1.023e6 / 18e6
         assert ctx.plan(ctx.blocks([0, 0, 0], 17000, step, 0.5)).kernel == 6                   # gc_correlate
-        assert ctx.plan_epoch(ctx.blocks([0], 17000, step, 0.5), 8).kernel == 6                # gc_track's launch per epoch
-        assert ctx.plan_epoch(ctx.blocks([1], 17000, step, 0.05), 16).kernel == 6
+        for b in (ctx.blocks([0], 17000, step, 0.5), ctx.blocks([1], 17000, step, 0.05)):     # gc_track's launch per epoch
+            splits = ctx.track_splits(b, 18e6, 1.023e6, 1023.0)
+            assert 1 <= splits <= 32
+            assert ctx.plan_epoch(b, splits).kernel == 6
 
 
 # ---- every plan of a sweep: coverage and alignment -------------------------------------------------------------------------------
